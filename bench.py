@@ -177,6 +177,25 @@ def per_block(regs, marks, model, a):
     return out
 
 
+DUMP_SAMPLE = 1 << 21   # elements kept of a larger output (8 MB as float32): the dump stays far below 64 MB
+
+
+def dump_outputs(out_dir, arrays):
+    """DIR/<name>.npy per output: float32 (float64 for integer outputs such as predictions); an output with more than
+    DUMP_SAMPLE elements is flattened and sampled at DUMP_SAMPLE sorted positions drawn from a fixed seed, so two runs
+    with the same arguments sample the same positions"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+            t = t[idx.to(t.device)]
+        t = t.cpu().to(torch.float32 if t.is_floating_point() else torch.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), t.numpy())
+    log(f"dumped {sorted(arrays)} to {out_dir}")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -196,7 +215,12 @@ def main():
     ap.add_argument("--native-comm", action="store_true",
                     help="gradient all-reduce through include/mmvqa_comm.h (mmvqa_allreduce_bucket on an own RCCL communicator and "
                          "stream) instead of torch.distributed.all_reduce")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (loss, MLM statistics, predictions, logits, "
+                         "updated parameters) as DIR/<name>.npy; arrays larger than 2^21 elements as a fixed seeded sample")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     for k, v in (("NCCL_ALGO", a.nccl_algo), ("NCCL_PROTO", a.nccl_proto), ("NCCL_MIN_NCHANNELS", a.nccl_min_nchannels)):
         if v is not None:
             os.environ[k] = str(v)         # read by RCCL when the communicator is created (init_process_group below)
@@ -263,8 +287,9 @@ def main():
         img, ids, seg, mask, tgt = synth.roco_batch(B_PER_GPU, T, HW, VOCAB, seed=1234 + rank, device=dev)
 
     marks = {}   # torch events around the launches that Python enqueues itself (loss kernels, Adam): same stream
+    kept = {}    # --dump-outputs: what the last timed step hands its caller (references only, read after the timing)
 
-    def step(timed_parts=False):
+    def step(timed_parts=False, keep=False):
         ev = (lambda: torch.cuda.Event(enable_timing=True)) if timed_parts else None
 
         def mark(name):
@@ -274,21 +299,27 @@ def main():
                 marks[name] = e
 
         if CONFIG == 4:    # MLM on both views + SupCon over the (all-gathered) view set: mm-vqa_amd/train.py
-            loss, _, stats = TR.supcon_step(model, opt, red, world, (img, ids, seg, mask, tgt))
+            loss, pred, stats = TR.supcon_step(model, opt, red, world, (img, ids, seg, mask, tgt))
+            if keep:
+                kept.update(loss=loss.detach(), pred=pred, stats=stats)
             return [loss.detach()]
         if CONFIG == 5:    # VQA head + ASLSingleLabel
-            loss, _ = TR.vqa_step(model, opt, red, world, (img, ids, seg, mask, tgt), mmvqa_amd.asl_loss)
+            loss, pred = TR.vqa_step(model, opt, red, world, (img, ids, seg, mask, tgt), mmvqa_amd.asl_loss)
+            if keep:
+                kept.update(loss=loss.detach(), pred=pred)
             return [loss.detach()]
         mark("step_a")
         logits = model(img, ids, seg, mask)
         mark("loss_fwd_a")
-        loss, _, stats = mmvqa_amd.mlm_loss(logits, tgt)
+        loss, pred, stats = mmvqa_amd.mlm_loss(logits, tgt)
         mark("loss_fwd_b")
         loss.backward()
         red.allreduce()
         mark("adam_a")
         opt.step(grad_scale=1.0 / world, zero_grad=True)
         mark("adam_b")
+        if keep:
+            kept.update(logits=logits.detach(), loss=loss.detach(), pred=pred, stats=stats)
         return stats
 
     def sync():
@@ -305,8 +336,8 @@ def main():
         log(f"warm-up step {i} done")
     sync()
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        stats = step()
+    for i in range(a.steps):
+        stats = step(keep=a.dump_outputs is not None and i == a.steps - 1)
     sync()
     dt = time.perf_counter() - t0
     if world > 1:
@@ -316,6 +347,11 @@ def main():
     ms = dt / a.steps * 1e3
     log(f"timed {a.steps} steps: {ms:.2f} ms/step")
     value = B_PER_GPU * world * a.steps / dt
+    if a.dump_outputs is not None and rank == 0:
+        # before the profiled steps below, which move the parameters again
+        kept["params"] = model.flat_params
+        dump_outputs(a.dump_outputs, kept)
+    kept.clear()
 
     # Roofline of the dominant kernel class: one more step, identical to the timed ones (same two HIP streams), with
     # a HIP event pair around every launch recorded on the stream that launch goes to.  The weight-gradient GEMMs

@@ -1033,7 +1033,10 @@ static int resnet_backward(mmvqa_engine* e, hipStream_t st) {
   TRY(tap_bwd(e, ts, 4, WS(e->z0), &e->stem_bn, WS(e->tapgrad[4]), EpiOpt()));
   ev_tap[4] = sc.mark_on(ts);
   hipEvent_t ev_g1 = nullptr, ev_g2 = nullptr, ev_prevG = nullptr;   // side readers of g1buf / g2buf / previous G
-  long long hi_mark = e->enc_lo;    // gradients in [hi_mark, end) were announced by the caller; fc + taps sit below
+  // gradients in [enc_lo, end) were announced by the caller; the tap weights sit in [taps[0].w, enc_lo) (fc below them).
+  // Their gradients come from the tap stream, which notify() does not join: that range is announced after the stem,
+  // whose chain waits for the last tap, and the block ranges end below it
+  long long hi_mark = e->taps[0].w;
   for (int i = nb - 1; i >= 0; --i) {
     BlockRef& b = e->blocks[i];
     const float* G = WS(e->gbuf[cur]);
@@ -1127,6 +1130,7 @@ static int resnet_backward(mmvqa_engine* e, hipStream_t st) {
     RUN(PROF_IGEMM, 2.0 * (double)g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_WGRAD, 1, 0, st));
   }
   sc.need(sc.mark());   // join: everything after the backward (all-reduce, Adam) sees the side stream's gradients
+  notify(e, sc, e->taps[0].w, e->enc_lo);   // tap weights: the caller's stream is behind ev_tap[4], the last tap launch
   notify(e, sc, e->emb_hi, hi_mark);
   return MMVQA_OK;
 }
