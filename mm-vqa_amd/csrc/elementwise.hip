@@ -905,14 +905,18 @@ __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float*
   // again before the next optimizer step; the parameters are: the forward re-reads them)
   const long stride = (long)gridDim.x * blockDim.x;
   const float inv_bc2 = 1.0f / bc2_sqrt;
+  // Every rounding is spelled out (explicit fmaf, no contraction): the compiler contracted the unrolled loop and the
+  // tail loop below differently, so an element's update depended on which loop of which launch reached it, and the
+  // ranged updates of FusedAdam.overlap_backward() were not bit-identical to the one-launch form from the second step on.
   auto upd = [&](f32x4& pv, const f32x4& gv, f32x4& mv, f32x4& vv) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float gg = gv[e] * gscale;
-      mv[e] = mv[e] + (gg - mv[e]) * omb1;           // exp_avg.lerp_(grad, 1 - beta1)
-      vv[e] = vv[e] * b2 + gg * gg * omb2;           // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
+      mv[e] = fmaf(gg - mv[e], omb1, mv[e]);         // exp_avg.lerp_(grad, 1 - beta1)
+      vv[e] = fmaf(gg * gg, omb2, vv[e] * b2);       // exp_avg_sq.mul_(beta2).addcmul_(g, g, 1 - beta2)
       const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
-      pv[e] = pv[e] - step_size * (mv[e] / denom);
+      pv[e] = fmaf(-step_size, mv[e] / denom, pv[e]);
     }
   };
   (void)inv_bc2;
@@ -1979,6 +1983,24 @@ int k_act_bwd_stats(hipStream_t st, const float* t, const float* gate, const flo
 
 int k_mul_dact(hipStream_t st, const float* x, const float* pre, int act, float* y, long n) {
   hipLaunchKernelGGL(mul_dact_kernel, dim3(cdiv_i(n, 256)), dim3(256), 0, st, x, pre, act, y, n);
+  KERNEL_CHECK_RET();
+  return MMVQA_OK;
+}
+
+// Test-only delay (MMVQA_SIDE_LAG_US / MMVQA_MAIN_LAG_US, engine.cpp SideCtx): one wave that sleeps until `ticks` of the
+// 100 MHz s_memrealtime clock have passed.  It touches no memory; the loop is bounded by time and, should the clock not
+// advance, by an iteration cap (each round sleeps ~8 x 64 cycles: the cap is far above the 2 ms a caller may ask for).
+__global__ void __launch_bounds__(64) spin_kernel(unsigned long long ticks) {
+  const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+  for (int it = 0; it < (1 << 22); ++it) {
+    if (__builtin_amdgcn_s_memrealtime() - t0 >= ticks) break;
+    __builtin_amdgcn_s_sleep(8);
+  }
+}
+
+int k_spin(hipStream_t st, int us) {
+  if (us <= 0) return MMVQA_OK;
+  hipLaunchKernelGGL(spin_kernel, dim3(1), dim3(64), 0, st, 100ull * (unsigned long long)us);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }

@@ -791,6 +791,16 @@ static int tap_bwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
 }
 
 // --------------------------------------------------------------------------- side stream (backward overlap)
+// Test-only lag injection (tests/test_hip_schedule.py): MMVQA_SIDE_LAG_US=n enqueues an n-microsecond spin on the side /
+// tap stream right behind every fork, MMVQA_MAIN_LAG_US=n on the caller's stream right after the fork's event.  A missing
+// need() / SideReads::write() / join then loses its race every time instead of now and then.  Read once, clamped to
+// [0, 2000]; unset (the default) enqueues nothing.
+static int lag_us(const char* name) {
+  const char* v = getenv(name);
+  if (!v) return 0;
+  const int n = atoi(v);
+  return n < 0 ? 0 : (n > 2000 ? 2000 : n);
+}
 // The data-gradient chain (dgrad -> BN coefficients -> dgrad ...) is the critical path of the backward pass
 // and, on the 14x14 / 7x7 layers, fills well under one workgroup per CU; the weight-gradient GEMMs and
 // the tap backward only feed the optimizer, so they run on a second HIP stream and fill the idle CUs.
@@ -840,7 +850,14 @@ struct SideCtx {
     hipEvent_t ev = next_event();
     if (!ev) return;
     (void)hipEventRecord(ev, st);
+    lag(st, false);
     (void)hipStreamWaitEvent(s, ev, 0);
+    lag(s, true);
+  }
+  static void lag(hipStream_t s, bool side) {   // (test-only, see lag_us)
+    static const int side_us = lag_us("MMVQA_SIDE_LAG_US"), main_us = lag_us("MMVQA_MAIN_LAG_US");
+    const int us = side ? side_us : main_us;
+    if (us > 0) (void)k_spin(s, us);
   }
   hipEvent_t mark_on(hipStream_t s) {
     if (!on) return nullptr;
@@ -861,7 +878,9 @@ struct SideCtx {
     hipEvent_t ev = next_event();
     if (!ev) return;
     (void)hipEventRecord(ev, st);
+    lag(st, false);
     (void)hipStreamWaitEvent(sd, ev, 0);
+    lag(sd, true);
   }
   hipEvent_t mark() {
     if (!on) return nullptr;

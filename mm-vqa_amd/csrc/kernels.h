@@ -74,6 +74,8 @@ int k_colsum(hipStream_t st, const float* x, int ld, int rows, int cols, float* 
 int k_dropout(hipStream_t st, float* x, long n, float p, uint32_t seed);
 int k_pixmask(hipStream_t st, int* out, int N, int OH, int OW, int SH, int SW, int KH, int KW, int stride, int pad);
 int k_dropout_copy(hipStream_t st, const float* x, float* y, long n, float p, uint32_t seed);
+// test-only: one wave that waits `us` microseconds (s_memrealtime), no memory access; us <= 0 enqueues nothing
+int k_spin(hipStream_t st, int us);
 
 // EfficientNetV2 pieces (elementwise.hip)
 int k_bn_act_add(hipStream_t st, const float* z, const float* s, const float* b, int pre_act, const float* idn,
