@@ -456,6 +456,36 @@ int mmvqa_aug_jitter_round(mmvqa_stream_t s, unsigned char* img, const int* op_d
 /* ToTensor + Normalize: uint8 [B][npix][3] -> fp32 [B][3][npix], (x/255 - mean)/std; mean3/std3 are HOST pointers */
 int mmvqa_aug_to_tensor(mmvqa_stream_t s, const unsigned char* img, float* out, int B, int npix, const float* mean3,
                         const float* std3);
+/* Per-image parameters of mmvqa_aug_train_fused (the training chain after Resize + CenterCrop, in one launch).
+ * Table fields are offsets in int32 elements into tables_dev, whose contents come from mmvqa_resample_coeffs (host):
+ * hb / hk = bounds [S][2] / coefficients [S][hks] of resizing the box width to S, vb / vk the same for its height. */
+typedef struct mmvqa_aug_record {
+  int bx, by, bw, bh;                             /* RandomResizedCrop box in the S x S image (x, y, width, height) */
+  int ty0, tyn;                                   /* box rows [ty0, ty0+tyn) the vertical pass reads */
+  int hb, hk, hks;                                /* horizontal tables: offsets, taps per output */
+  int vb, vk, vks;                                /* vertical tables: offsets, taps per output */
+  int fix[6];                                     /* RandomRotation: affine_fixed 16.16 coefficients (mmvqa_aug_rotate) */
+  int op[4];                                      /* ColorJitter order: op of round r (0..3 as in jitter_round, < 0 none) */
+  float factor[4];                                /* factor of round r (hue: the uint8 shift) */
+} mmvqa_aug_record;
+size_t mmvqa_sizeof_aug_record(void);
+/* RandomResizedCrop -> RandomRotation -> 4 ColorJitter rounds -> ToTensor + Normalize of B images in ONE launch, bit
+ * for bit what mmvqa_aug_resample + _rotate + 4 x _jitter_round + _to_tensor compute.  src_u8 [B][S][S][3] is the
+ * Resize + CenterCrop output; it is overwritten with the last byte stage.  out_f32 [B][3][S][S]; mean3/std3 are HOST
+ * pointers.  Returns MMVQA_ERR_ARG for bad pointers or sizes and when S * S * 3 bytes do not fit the device's LDS.
+ * The records are device data the call cannot check: the caller keeps every box inside the S x S image and the row
+ * window [ty0, ty0 + tyn) inside the box.  An image whose record breaks that is skipped by the kernel: its slot of
+ * out_f32 and of src_u8 is left as it was (no error is reported). */
+int mmvqa_aug_train_fused(mmvqa_stream_t s, unsigned char* src_u8, float* out_f32, const mmvqa_aug_record* records_dev,
+                          const int* tables_dev, int B, int S, const float* mean3, const float* std3);
+/* 1 if mmvqa_aug_train_fused takes images of S x S on the current device (S * S * 3 bytes fit its LDS), else 0 */
+int mmvqa_aug_train_fused_fits(int S);
+/* A non-blocking stream of the current device's LEAST priority (HIP: 1 = low, 0 = normal, negative = high), created
+ * on first use and kept for the life of the process; *priority (may be NULL) receives the priority it has.  The input
+ * pipeline runs on it so that its kernels yield to the training step's whenever both are ready. */
+int mmvqa_low_priority_stream(mmvqa_stream_t* out, int* priority);
+/* the priority of stream s (hipStreamGetPriority) */
+int mmvqa_stream_priority(mmvqa_stream_t s, int* priority);
 
 #ifdef __cplusplus
 }

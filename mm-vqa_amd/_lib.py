@@ -81,6 +81,15 @@ class ResampleJob(C.Structure):
     ]
 
 
+class AugRecord(C.Structure):
+    """mirror of mmvqa_aug_record"""
+    _fields_ = [
+        ("bx", C.c_int), ("by", C.c_int), ("bw", C.c_int), ("bh", C.c_int), ("ty0", C.c_int), ("tyn", C.c_int),
+        ("hb", C.c_int), ("hk", C.c_int), ("hks", C.c_int), ("vb", C.c_int), ("vk", C.c_int), ("vks", C.c_int),
+        ("fix", C.c_int * 6), ("op", C.c_int * 4), ("factor", C.c_float * 4),
+    ]
+
+
 class ModelDesc(C.Structure):
     """mirror of mmvqa_model_desc"""
     _fields_ = [
@@ -151,6 +160,11 @@ SIGNATURES = {
     "mmvqa_aug_rotate": (_i, [_P, _P, _P, _P, _i, _i, _i]),
     "mmvqa_aug_jitter_round": (_i, [_P, _P, _P, _P, _P, _i, _i]),
     "mmvqa_aug_to_tensor": (_i, [_P, _P, _P, _i, _i, _P, _P]),
+    "mmvqa_sizeof_aug_record": (_sz, []),
+    "mmvqa_aug_train_fused": (_i, [_P, _P, _P, _P, _P, _i, _i, _P, _P]),
+    "mmvqa_aug_train_fused_fits": (_i, [_i]),
+    "mmvqa_low_priority_stream": (_i, [C.POINTER(_P), C.POINTER(_i)]),
+    "mmvqa_stream_priority": (_i, [_P, C.POINTER(_i)]),
     "mmvqa_engine_create": (_i, [C.POINTER(ModelDesc), C.POINTER(_P)]),
     "mmvqa_engine_destroy": (None, [_P]),
     "mmvqa_engine_num_tensors": (_i, [_P]),
@@ -192,11 +206,12 @@ def lib():
         fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
-    for nm, st in (("gemm", GemmDesc), ("attn", AttnDesc), ("model", ModelDesc), ("resample_job", ResampleJob)):
-        if nm == "resample_job":
-            got = L.mmvqa_sizeof_resample_job()
+    for nm, st in (("gemm", GemmDesc), ("attn", AttnDesc), ("model", ModelDesc), ("resample_job", ResampleJob),
+                   ("aug_record", AugRecord)):
+        if nm in ("resample_job", "aug_record"):
+            got = getattr(L, f"mmvqa_sizeof_{nm}")()
             if got != C.sizeof(st):
-                raise MMVQAError(f"ABI mismatch: sizeof(mmvqa_resample_job) = {got} in the library, {C.sizeof(st)} in Python")
+                raise MMVQAError(f"ABI mismatch: sizeof(mmvqa_{nm}) = {got} in the library, {C.sizeof(st)} in Python")
             continue
         got = getattr(L, f"mmvqa_sizeof_{nm}_desc")()
         if got != C.sizeof(st):

@@ -14,10 +14,15 @@ pinned against Pillow itself, tests/test_augment.py).
 
     aug = DeviceAugment(train=True)                      # ROCO pre-training settings
     x = aug(list_of_uint8_HWC_arrays)                    # -> float32 [B, 3, 224, 224] on the GPU
+
+For a training loop, run_packed() takes a ragged batch that is already on the device and only enqueues work on a
+stream: one pinned blob of tables / jobs / records goes up by one async copy, then Resize+CenterCrop (2 launches) and
+the rest of the train chain in ONE launch (mmvqa_aug_train_fused), no host sync.
 """
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -125,6 +130,21 @@ def coeffs(in_size, in0, in1, out_size):
     if r != ks:
         L.check(r if r < 0 else -1)
     return b, k, ks
+
+
+@functools.lru_cache(maxsize=4096)
+def _coeffs_cached(in_size, out_size):
+    b, k, ks = coeffs(in_size, 0, in_size, out_size)
+    b.setflags(write=False)
+    k.setflags(write=False)
+    return b, k, ks
+
+
+def _window_rows(vb, oy, S):
+    """rows [ty0, ty0 + tyn) of the box that the vertical pass of output rows [oy, oy + S) reads"""
+    w = vb[oy:oy + S]
+    ty0 = int(w[:, 0].min())
+    return ty0, int((w[:, 0] + w[:, 1]).max()) - ty0
 
 
 class _Pack:
@@ -243,3 +263,174 @@ class DeviceAugment:
         self._keep_all = keep + [final]
         self.last_uint8 = final                             # [B, S, S, 3] after the last byte-valued stage (tests)
         return out
+
+    def fused_fits(self):
+        """whether the library's one-launch train chain takes S x S images on this device (asked once per device)"""
+        key = (self.dev.index if self.dev.index is not None else torch.cuda.current_device(), self.size)
+        if key not in _FUSED_FITS:
+            with torch.cuda.device(key[0]):
+                rc = L.lib().mmvqa_aug_train_fused_fits(self.size)
+            if rc < 0:
+                L.check(rc)
+            _FUSED_FITS[key] = bool(rc)
+        return _FUSED_FITS[key]
+
+    # ---- non-blocking entry point (training loops): ragged device batch in, work enqueued on `stream` only
+    def run_packed(self, src_dev, offsets, shapes, params=None, stream=None, fused=True, out=None, generator=None):
+        """src_dev: uint8 device tensor holding B decoded RGB images back to back, image n = [h_n, w_n, 3] at byte
+        offsets[n]; shapes: [B, 2] (h, w).  Enqueues Resize+CenterCrop and, for training, the rest of the chain on
+        `stream` (default: the current stream) and returns fp32 [B, 3, S, S] (`out`, if given, is filled).  No host
+        sync: everything the kernels read (coefficient tables, jobs, records) goes up as ONE pinned blob with one async
+        copy.  fused=False runs the multi-launch stages of __call__ instead (the reference the tests compare with); they
+        also run when S x S images do not fit the device's LDS (fused_fits(), decided before anything is packed).
+        last_uint8 is the last byte stage."""
+        if self.dev.type != "cuda":
+            raise L.MMVQAError("DeviceAugment runs on the GPU only (no CPU fallback)")
+        S, lib = self.size, L.lib()
+        shapes = [(int(h), int(w)) for h, w in (shapes.tolist() if isinstance(shapes, torch.Tensor) else shapes)]
+        offsets = [int(o) for o in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
+        B = len(shapes)
+        if B == 0 or len(offsets) != B:
+            raise ValueError("run_packed: need one offset per image and at least one image")
+        if src_dev.dtype != torch.uint8 or src_dev.device.type != "cuda" or not src_dev.is_contiguous():
+            raise ValueError("run_packed: src_dev must be a contiguous uint8 tensor on the GPU")
+        for o, (h, w) in zip(offsets, shapes):
+            if h <= 0 or w <= 0 or o < 0 or o + h * w * 3 > src_dev.numel():
+                raise ValueError(f"run_packed: image ({h}, {w}) at offset {o} lies outside the {src_dev.numel()}-byte batch")
+        if self.train:
+            if params is None:
+                params = sample_params(B, S, self.scale, self.ratio, self.degrees, self.jitter, generator)
+            if len(params) != B:
+                raise ValueError("run_packed: one parameter set per image")
+            for p in params:
+                i, j, h, w = p["box"]
+                if not (0 <= i and 0 <= j and 0 < h and 0 < w and i + h <= S and j + w <= S):
+                    raise ValueError(f"run_packed: crop box {p['box']} outside the {S}x{S} image")
+        stream = stream if stream is not None else torch.cuda.current_stream(self.dev)
+        use_fused = self.train and fused and self.fused_fits()
+        with torch.cuda.stream(stream):
+            pack = _Pack()
+            tabs = {}
+
+            def tab(n_in, n_out):
+                if (n_in, n_out) not in tabs:
+                    b, k, ks = _coeffs_cached(n_in, n_out)
+                    tabs[(n_in, n_out)] = (pack.add(b), pack.add(k), ks, b)
+                return tabs[(n_in, n_out)]
+
+            st1 = []                                        # Resize(S) + CenterCrop(S) of the ragged sources
+            for (h, w) in shapes:
+                rw, rh = resized_size(w, h, S)
+                ox, oy = center_crop_offset(rw, rh, S)
+                ch, cv = tab(w, rw), tab(h, rh)
+                st1.append((h, w, rw, rh, ox, oy, ch, cv) + _window_rows(cv[3], oy, S))
+            st2 = []                                        # RandomResizedCrop box -> (S, S)
+            for p in (params if self.train else []):
+                i, j, h, w = p["box"]
+                ch, cv = tab(w, S), tab(h, S)
+                st2.append((j, i, w, h, ch, cv) + _window_rows(cv[3], 0, S))
+            tables = np.concatenate(pack.tabs)
+            njob = C.sizeof(L.ResampleJob)
+            lay = {}
+
+            def put(name, nbytes):
+                lay[name] = -(-sum_n[0] // 16) * 16
+                sum_n[0] = lay[name] + nbytes
+
+            sum_n = [0]
+            put("tables", tables.nbytes)
+            put("jobs1", B * njob)
+            if use_fused:
+                put("recs", B * C.sizeof(L.AugRecord))
+            elif self.train:
+                put("jobs2", B * njob)
+                put("fix", B * 6 * 4)
+                put("ops", 4 * B * 4)
+                put("facs", 4 * B * 4)
+            blob = torch.empty(sum_n[0], dtype=torch.uint8, device=self.dev)
+            base = blob.data_ptr()
+            rows1 = max(m[-1] for m in st1)
+            tmp1 = torch.empty(B, rows1, S, 3, dtype=torch.uint8, device=self.dev)
+            a0 = torch.empty(B, S, S, 3, dtype=torch.uint8, device=self.dev)
+            if out is None:
+                out = torch.empty(B, 3, S, S, dtype=torch.float32, device=self.dev)
+            elif out.shape != (B, 3, S, S) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != a0.device:
+                raise ValueError("run_packed: out must be a contiguous fp32 [B, 3, S, S] tensor on the device")
+            tb = base + lay["tables"]
+
+            def job(jb, src, sh, sw, box, rsz, off, ch, cv, ty0, tyn, tmp, dst):
+                jb.src, jb.sh, jb.sw, jb.spitch = src, sh, sw, sw * 3
+                (jb.bx, jb.by, jb.bw, jb.bh), (jb.rw, jb.rh), (jb.ox, jb.oy) = box, rsz, off
+                jb.ty0, jb.tyn, jb.tmp, jb.dst, jb.dpitch = ty0, tyn, tmp, dst, S * 3
+                jb.hb, jb.hk, jb.hks = tb + 4 * ch[0], tb + 4 * ch[1], ch[2]
+                jb.vb, jb.vk, jb.vks = tb + 4 * cv[0], tb + 4 * cv[1], cv[2]
+
+            jobs1 = (L.ResampleJob * B)()
+            for n, (h, w, rw, rh, ox, oy, ch, cv, ty0, tyn) in enumerate(st1):
+                job(jobs1[n], src_dev.data_ptr() + offsets[n], h, w, (0, 0, w, h), (rw, rh), (ox, oy), ch, cv, ty0, tyn,
+                    tmp1[n].data_ptr(), a0[n].data_ptr())
+            host = torch.empty(sum_n[0], dtype=torch.uint8, pin_memory=True)
+            hv = host.numpy()
+            hv[lay["tables"]:lay["tables"] + tables.nbytes] = tables.view(np.uint8)
+
+            def emit(name, obj):
+                raw = np.frombuffer(bytes(obj), np.uint8) if not isinstance(obj, np.ndarray) else obj.reshape(-1).view(np.uint8)
+                hv[lay[name]:lay[name] + raw.size] = raw
+
+            emit("jobs1", jobs1)
+            keep = [blob, tmp1, a0]
+            if use_fused:
+                recs = (L.AugRecord * B)()
+                for n, (p, (bx, by, bw, bh, ch, cv, ty0, tyn)) in enumerate(zip(params, st2)):
+                    r = recs[n]
+                    r.bx, r.by, r.bw, r.bh, r.ty0, r.tyn = bx, by, bw, bh, ty0, tyn
+                    r.hb, r.hk, r.hks, r.vb, r.vk, r.vks = ch[0], ch[1], ch[2], cv[0], cv[1], cv[2]
+                    r.fix[:] = rotate_fix(p["angle"], S, S)
+                    r.op[:] = list(p["order"])
+                    r.factor[:] = [_factor(p, o) for o in p["order"]]
+                emit("recs", recs)
+            elif self.train:
+                rows2 = max(m[-1] for m in st2)
+                tmp2 = torch.empty(B, rows2, S, 3, dtype=torch.uint8, device=self.dev)
+                a1 = torch.empty(B, S, S, 3, dtype=torch.uint8, device=self.dev)
+                a2 = torch.empty_like(a1)
+                lsum = torch.empty(B, dtype=torch.int64, device=self.dev)
+                jobs2 = (L.ResampleJob * B)()
+                for n, (bx, by, bw, bh, ch, cv, ty0, tyn) in enumerate(st2):
+                    job(jobs2[n], a0[n].data_ptr(), S, S, (bx, by, bw, bh), (S, S), (0, 0), ch, cv, ty0, tyn,
+                        tmp2[n].data_ptr(), a1[n].data_ptr())
+                emit("jobs2", jobs2)
+                emit("fix", np.array([rotate_fix(p["angle"], S, S) for p in params], np.int32))
+                emit("ops", np.array([[p["order"][r] for p in params] for r in range(4)], np.int32))
+                emit("facs", np.array([[_factor(p, p["order"][r]) for p in params] for r in range(4)], np.float32))
+                keep += [tmp2, a1, a2, lsum]
+            blob.copy_(host, non_blocking=True)             # the one upload (the pinned block is held until it is done)
+            sp = C.c_void_p(stream.cuda_stream)
+            L.check(lib.mmvqa_aug_resample(sp, C.c_void_p(base + lay["jobs1"]), B, rows1, S, S))
+            final = a0
+            if use_fused:
+                L.check(lib.mmvqa_aug_train_fused(sp, L.ptr(a0), L.ptr(out), C.c_void_p(base + lay["recs"]),
+                                                  C.c_void_p(tb), B, S, self.mean, self.std))
+            elif self.train:
+                L.check(lib.mmvqa_aug_resample(sp, C.c_void_p(base + lay["jobs2"]), B, rows2, S, S))
+                L.check(lib.mmvqa_aug_rotate(sp, L.ptr(a1), L.ptr(a2), C.c_void_p(base + lay["fix"]), B, S, S))
+                for r in range(4):
+                    L.check(lib.mmvqa_aug_jitter_round(sp, L.ptr(a2), C.c_void_p(base + lay["ops"] + 4 * B * r),
+                                                       C.c_void_p(base + lay["facs"] + 4 * B * r), L.ptr(lsum), B, S * S))
+                final = a2
+            if not use_fused:
+                L.check(lib.mmvqa_aug_to_tensor(sp, L.ptr(final), L.ptr(out), B, S * S, self.mean, self.std))
+        # Every buffer above was allocated on `stream` and is used on it only, so the caching allocator may hand its
+        # block out again as soon as it is freed: later work on `stream` is ordered after these launches.
+        self.last_fused = use_fused
+        self.last_uint8 = final                             # [B, S, S, 3] after the last byte-valued stage (tests)
+        self._packed_keep = keep
+        return out
+
+
+_FUSED_FITS = {}      # (device index, S) -> mmvqa_aug_train_fused_fits
+
+
+def _factor(p, op):
+    """the factor a ColorJitter round of op `op` applies (hue: the uint8 shift, as the kernels take it)"""
+    return (p["brightness"], p["contrast"], p["saturation"], float(hue_shift_u8(p["hue"])))[op]

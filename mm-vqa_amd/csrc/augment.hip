@@ -237,6 +237,142 @@ __global__ __launch_bounds__(256) void to_tensor_kernel(const u8* __restrict__ i
   }
 }
 
+// --------------------------------------------------------------------------- the whole train chain in one launch
+// One workgroup per image, the working image in LDS ([S][S][3] bytes, 147 KiB at S = 224).  The image's own slot of
+// img is its scratch once read: the two passes that read LDS while producing the next LDS contents write their
+// pixels there first (thread tid owns pixels tid, tid + 1024, ...), then copy them back after a barrier.  Holding
+// the ~49 pixels per thread in registers instead took the kernel past 128 VGPRs (spills) at 1024 threads.
+//   RandomResizedCrop  horizontal pass img -> LDS tmp [tyn][S][3]; vertical pass LDS -> img -> LDS
+//   RandomRotation     gather LDS -> img -> LDS
+//   ColorJitter        four rounds in LDS; contrast takes the exact integer L sum of the workgroup
+//   ToTensor+Normalize LDS -> out (fp32 NCHW); the final bytes also go back to img (the last byte stage)
+// Same arithmetic as resample_h/v, rotate_nearest, lsum + jitter and to_tensor above, so the result is bit-identical.
+#define AUG_FUSED_THREADS 1024
+
+__global__ __launch_bounds__(AUG_FUSED_THREADS) void aug_train_fused_kernel(u8* __restrict__ img, float* __restrict__ out,
+                                                                            const mmvqa_aug_record* __restrict__ recs,
+                                                                            const int* __restrict__ tabs, int S, float m0,
+                                                                            float m1, float m2, float s0, float s1,
+                                                                            float s2) {
+  extern __shared__ u8 lds[];                   // [S][S][3]
+  __shared__ unsigned red[AUG_FUSED_THREADS / 64];
+  const int tid = threadIdx.x, npix = S * S;
+  const mmvqa_aug_record r = recs[blockIdx.x];
+  u8* src = img + (size_t)blockIdx.x * npix * 3;
+  // a record whose box leaves the image would make the passes below index outside LDS: that image's outputs are left
+  // unwritten (documented in mmvqa.h; the host side validates every box before it packs the records)
+  if (r.bx < 0 || r.by < 0 || r.bw <= 0 || r.bh <= 0 || r.bx + r.bw > S || r.by + r.bh > S || r.ty0 < 0 || r.tyn <= 0 ||
+      r.ty0 + r.tyn > r.bh)
+    return;
+  // RandomResizedCrop, horizontal pass: box rows [ty0, ty0 + tyn) -> lds[yl][x]
+  {
+    const int* hb = tabs + r.hb;
+    const int* hk = tabs + r.hk;
+    for (int q = tid; q < r.tyn * S; q += AUG_FUSED_THREADS) {
+      const int yl = q / S, x = q - yl * S;
+      const int xmin = hb[x * 2], xn = hb[x * 2 + 1];
+      const int* k = hk + (size_t)x * r.hks;
+      const u8* row = src + (size_t)(r.by + r.ty0 + yl) * S * 3 + (size_t)(r.bx + xmin) * 3;
+      int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+      for (int t = 0; t < xn; ++t) {
+        const int c = k[t];
+        a0 += (int)row[t * 3] * c; a1 += (int)row[t * 3 + 1] * c; a2 += (int)row[t * 3 + 2] * c;
+      }
+      lds[q * 3] = clip8_22(a0); lds[q * 3 + 1] = clip8_22(a1); lds[q * 3 + 2] = clip8_22(a2);
+    }
+  }
+  __syncthreads();
+  // vertical pass: lds tmp -> img (its own bytes were read above: from here on it is this workgroup's scratch, L2-hot)
+  {
+    const int* vb = tabs + r.vb;
+    const int* vk = tabs + r.vk;
+    for (int p = tid; p < npix; p += AUG_FUSED_THREADS) {
+      const int y = p / S, x = p - y * S;
+      const int ymin = vb[y * 2], yn = vb[y * 2 + 1];
+      const int* kk = vk + (size_t)y * r.vks;
+      const u8* col = lds + ((ymin - r.ty0) * S + x) * 3;
+      int a0 = 1 << 21, a1 = 1 << 21, a2 = 1 << 21;
+      for (int t = 0; t < yn; ++t) {
+        const int c = kk[t];
+        const u8* q = col + t * S * 3;
+        a0 += (int)q[0] * c; a1 += (int)q[1] * c; a2 += (int)q[2] * c;
+      }
+      src[p * 3] = clip8_22(a0); src[p * 3 + 1] = clip8_22(a1); src[p * 3 + 2] = clip8_22(a2);
+    }
+  }
+  __syncthreads();                              // every read of tmp is done
+  // (each thread reads back only the bytes it wrote itself: program order, no fence needed)
+  for (int p = tid; p < npix; p += AUG_FUSED_THREADS) {
+    lds[p * 3] = src[p * 3]; lds[p * 3 + 1] = src[p * 3 + 1]; lds[p * 3 + 2] = src[p * 3 + 2];
+  }
+  __syncthreads();
+  // RandomRotation (affine_fixed, nearest, black fill): gather lds -> img, then back to lds
+  for (int p = tid; p < npix; p += AUG_FUSED_THREADS) {
+    const int y = p / S, x = p - y * S;
+    const int xx = r.fix[2] + r.fix[1] * y + r.fix[0] * x, yy = r.fix[5] + r.fix[4] * y + r.fix[3] * x;
+    const int xin = xx >> 16, yin = yy >> 16;
+    u8 c0 = 0, c1 = 0, c2 = 0;
+    if (xin >= 0 && xin < S && yin >= 0 && yin < S) {
+      const u8* q = lds + (yin * S + xin) * 3;
+      c0 = q[0]; c1 = q[1]; c2 = q[2];
+    }
+    src[p * 3] = c0; src[p * 3 + 1] = c1; src[p * 3 + 2] = c2;
+  }
+  __syncthreads();                              // every gather is done
+  for (int p = tid; p < npix; p += AUG_FUSED_THREADS) {
+    lds[p * 3] = src[p * 3]; lds[p * 3 + 1] = src[p * 3 + 1]; lds[p * 3 + 2] = src[p * 3 + 2];
+  }
+  // ColorJitter in LDS: round rnd applies op[rnd] (the image's own permutation).  Each thread keeps to the pixels it
+  // wrote just above, so only contrast's mean (a sum over the whole image) needs the workgroup.
+  for (int rnd = 0; rnd < 4; ++rnd) {
+    const int o = recs[blockIdx.x].op[rnd];       // (from memory: a dynamic index into r would put r in scratch)
+    if (o < 0) continue;
+    const float f = recs[blockIdx.x].factor[rnd];
+    const bool inside = f >= 0.0f && f <= 1.0f;
+    int mean = 0, shift = 0;
+    if (o == 1) {                               // exact integer sum of L: S * S * 255 < 2^32 for any S whose image fits LDS
+      unsigned s = 0;
+      for (int p = tid; p < npix; p += AUG_FUSED_THREADS) s += (unsigned)lum(lds[p * 3], lds[p * 3 + 1], lds[p * 3 + 2]);
+#pragma unroll
+      for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w, 64);
+      if ((tid & 63) == 0) red[tid >> 6] = s;
+      __syncthreads();
+      unsigned tot = 0;
+#pragma unroll
+      for (int w = 0; w < AUG_FUSED_THREADS / 64; ++w) tot += red[w];
+      __syncthreads();                          // red is free for the next contrast round
+      mean = (int)((double)tot / (double)npix + 0.5);
+    }
+    if (o == 3) shift = ((int)f) & 0xFF;
+    for (int p = tid; p < npix; p += AUG_FUSED_THREADS) {
+      int cr = lds[p * 3], cg = lds[p * 3 + 1], cb = lds[p * 3 + 2];
+      if (o == 0) {
+        cr = blend1(0, cr, f, inside); cg = blend1(0, cg, f, inside); cb = blend1(0, cb, f, inside);
+      } else if (o == 1) {
+        cr = blend1(mean, cr, f, inside); cg = blend1(mean, cg, f, inside); cb = blend1(mean, cb, f, inside);
+      } else if (o == 2) {
+        const int L = lum(cr, cg, cb);
+        cr = blend1(L, cr, f, inside); cg = blend1(L, cg, f, inside); cb = blend1(L, cb, f, inside);
+      } else {
+        int h, sat, val;
+        rgb2hsv(cr, cg, cb, h, sat, val);
+        h = (h + shift) & 0xFF;
+        hsv2rgb(h, sat, val, cr, cg, cb);
+      }
+      lds[p * 3] = (u8)cr; lds[p * 3 + 1] = (u8)cg; lds[p * 3 + 2] = (u8)cb;
+    }
+  }
+  // ToTensor + Normalize (coalesced fp32 planes) and the final bytes back to img
+  float* o = out + (size_t)blockIdx.x * npix * 3;
+  for (int p = tid; p < npix; p += AUG_FUSED_THREADS) {
+    const int cr = lds[p * 3], cg = lds[p * 3 + 1], cb = lds[p * 3 + 2];
+    o[p] = ((float)cr / 255.0f - m0) / s0;
+    o[npix + p] = ((float)cg / 255.0f - m1) / s1;
+    o[2 * npix + p] = ((float)cb / 255.0f - m2) / s2;
+    src[p * 3] = (u8)cr; src[p * 3 + 1] = (u8)cg; src[p * 3 + 2] = (u8)cb;
+  }
+}
+
 // --------------------------------------------------------------------------- C ABI
 extern "C" {
 
@@ -284,6 +420,73 @@ int mmvqa_aug_to_tensor(mmvqa_stream_t s, const unsigned char* img, float* out, 
   hipLaunchKernelGGL(to_tensor_kernel, dim3(gx, B), dim3(256), 0, (hipStream_t)s, img, out, npix, mean3[0], mean3[1],
                      mean3[2], std3[0], std3[1], std3[2]);
   KERNEL_CHECK_RET();
+  return MMVQA_OK;
+}
+
+size_t mmvqa_sizeof_aug_record(void) { return sizeof(mmvqa_aug_record); }
+
+// dynamic LDS the fused kernel may use on the current device (its attribute raised to that once per device)
+static int fused_lds_cap(int* cap_out) {
+  static int lds_cap[32] = {0};
+  int dev = 0;
+  HIP_CHECK_RET(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 32) return mmvqa_set_error(MMVQA_ERR_ARG, "aug_train_fused: device %d out of range", dev);
+  if (!lds_cap[dev]) {
+    int a = 0, b = 0;
+    HIP_CHECK_RET(hipDeviceGetAttribute(&a, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    HIP_CHECK_RET(hipDeviceGetAttribute(&b, hipDeviceAttributeSharedMemPerBlockOptin, dev));
+    const int cap = (a > b ? a : b) - (int)(sizeof(unsigned) * (AUG_FUSED_THREADS / 64));   // less the static LDS
+    HIP_CHECK_RET(hipFuncSetAttribute((const void*)aug_train_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+    lds_cap[dev] = cap;
+  }
+  *cap_out = lds_cap[dev];
+  return MMVQA_OK;
+}
+
+int mmvqa_aug_train_fused_fits(int S) {
+  if (S <= 0) return mmvqa_set_error(MMVQA_ERR_ARG, "aug_train_fused_fits: S = %d", S);
+  int cap = 0;
+  const int rc = fused_lds_cap(&cap);
+  if (rc != MMVQA_OK) return rc;
+  return (size_t)S * S * 3 <= (size_t)cap ? 1 : 0;
+}
+
+int mmvqa_aug_train_fused(mmvqa_stream_t s, unsigned char* src_u8, float* out_f32, const mmvqa_aug_record* records_dev,
+                          const int* tables_dev, int B, int S, const float* mean3, const float* std3) {
+  if (!src_u8 || !out_f32 || !records_dev || !tables_dev || !mean3 || !std3 || B <= 0 || S <= 0)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "aug_train_fused: bad arguments");
+  int cap = 0;
+  const int rc = fused_lds_cap(&cap);
+  if (rc != MMVQA_OK) return rc;
+  const size_t lds = (size_t)S * S * 3;
+  if (lds > (size_t)cap)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "aug_train_fused: S = %d needs %zu B of LDS, the device gives %d", S, lds, cap);
+  hipLaunchKernelGGL(aug_train_fused_kernel, dim3(B), dim3(AUG_FUSED_THREADS), lds, (hipStream_t)s, src_u8, out_f32,
+                     records_dev, tables_dev, S, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  KERNEL_CHECK_RET();
+  return MMVQA_OK;
+}
+
+// --------------------------------------------------------------------------- low-priority stream (input pipeline)
+int mmvqa_low_priority_stream(mmvqa_stream_t* out, int* priority) {
+  if (!out) return mmvqa_set_error(MMVQA_ERR_ARG, "low_priority_stream: null output");
+  static hipStream_t streams[32] = {nullptr};
+  int dev = 0;
+  HIP_CHECK_RET(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 32) return mmvqa_set_error(MMVQA_ERR_ARG, "low_priority_stream: device %d out of range", dev);
+  if (!streams[dev]) {
+    int least = 0, greatest = 0;
+    HIP_CHECK_RET(hipDeviceGetStreamPriorityRange(&least, &greatest));
+    HIP_CHECK_RET(hipStreamCreateWithPriority(&streams[dev], hipStreamNonBlocking, least));
+  }
+  *out = (mmvqa_stream_t)streams[dev];
+  if (priority) HIP_CHECK_RET(hipStreamGetPriority(streams[dev], priority));
+  return MMVQA_OK;
+}
+
+int mmvqa_stream_priority(mmvqa_stream_t s, int* priority) {
+  if (!priority) return mmvqa_set_error(MMVQA_ERR_ARG, "stream_priority: null output");
+  HIP_CHECK_RET(hipStreamGetPriority((hipStream_t)s, priority));
   return MMVQA_OK;
 }
 

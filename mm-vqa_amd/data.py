@@ -1,0 +1,392 @@
+"""Data layer: ROCO / VQA-Med 2019 files on disk -> device batches the hot path consumes.
+
+Tables follow the reference's on-disk layouts:
+  ROCO      pretrain/roco_utils.py:71-97, 567-587    <root>/<split>/radiology/<split>data.csv, images/<name>;
+                                                     rows whose image is missing are dropped; name = column 1,
+                                                     caption = column 2, stripped
+  VQA-Med   vqamed2019/utils.py:51-79, train.py:100-105, utils.py:234-257
+                                                     traindf / valdf / testdf.csv, {Train,Val,Test}/images/<img_id>.jpg;
+                                                     category and answer lower-cased; ans2idx over
+                                                     concat(train, val, test) in first-seen order
+(The reference also shuffles each table with DataFrame.sample(frac=pct); here the file order is kept and the epoch
+order is a seeded permutation, so ans2idx is the first-seen order of the files.)
+
+Two stages:
+  host    HostLoader: a torch DataLoader whose worker processes decode (Image.open(p).convert("RGB")) and tokenise;
+          collate packs a batch's images into one contiguous uint8 tensor + a [B, 2] shape table, pinned.  The
+          train-time augment parameters are drawn in the main process, per batch, from a generator seeded with
+          (seed, epoch, batch, rank), in torchvision's order (augment.sample_params).
+  device  DeviceFeeder: copies each pinned batch to the GPU and runs DeviceAugment.run_packed on its own low-priority
+          stream, `depth` batches ahead of the consumer; nothing on the host waits for the GPU.
+
+Workers start through "forkserver": they are children of a fresh server process, never forks of this process,
+which has the GPU open -- they inherit none of its GPU state and never touch the GPU themselves.
+
+Determinism: a batch is a function of (seed, epoch, batch index, rank) only.  The epoch order is a seeded
+permutation sharded across ranks like DistributedSampler (drop_last=False: the shard is padded from the head); the
+MLM masking rng is seeded per sample; worker count and timing do not enter.
+"""
+from __future__ import annotations
+
+import csv
+import math
+import os
+import pickle
+import random
+from collections import deque
+
+import numpy as np
+import torch
+
+from . import text
+from .augment import DeviceAugment, sample_params
+
+# torchvision settings of the two reference scripts (RandomResizedCrop scale / ratio, RandomRotation, ColorJitter)
+ROCO_AUG = dict(scale=(0.95, 1.05), ratio=(0.95, 1.05), degrees=5.0, jitter=(0.05,) * 4)     # roco_train.py:98-108
+VQA_AUG = dict(scale=(0.75, 1.25), ratio=(0.75, 1.25), degrees=10.0, jitter=(0.4,) * 4)      # vqamed2019/train.py:179-190
+
+
+def usable_host_threads():
+    """threads this process may really use: affinity mask capped by the cgroup CPU quota (os.cpu_count() reports the
+    whole host)"""
+    n = os.cpu_count() or 1
+    try:
+        n = len(os.sched_getaffinity(0))
+    except Exception:
+        pass
+    try:
+        q, per = open("/sys/fs/cgroup/cpu.max").read().split()
+        if q != "max":
+            n = min(n, max(1, int(int(q) / int(per))))
+    except Exception:
+        pass
+    return n
+
+
+def default_workers():
+    return min(4, usable_host_threads())
+
+
+def mix_seed(*parts):
+    """a 63-bit seed from a tuple of integers (independent of Python's hash randomisation)"""
+    return int(np.random.SeedSequence([int(p) & 0xFFFFFFFF for p in parts]).generate_state(1, np.uint64)[0]) >> 1
+
+
+def sample_rng(seed, epoch, index):
+    """the MLM masking rng of one sample"""
+    return random.Random(mix_seed(seed, epoch, index, 0x6D6C6D))
+
+
+def batch_generator(seed, epoch, batch, rank):
+    """the torch.Generator the augment parameters of one batch are drawn from"""
+    return torch.Generator().manual_seed(mix_seed(seed, epoch, batch, rank, 0x617567))
+
+
+# --------------------------------------------------------------------------- tables
+def _read_csv(path):
+    with open(path, newline="", encoding="utf-8") as f:
+        rows = list(csv.reader(f))
+    if not rows:
+        raise ValueError(f"{path}: empty table")
+    return rows[0], rows[1:]
+
+
+def roco_table(root, split):
+    """[(image path, caption)] of <root>/<split>/radiology/<split>data.csv, rows without an image dropped (in order)"""
+    d = os.path.join(root, split, "radiology")
+    names = set(os.listdir(os.path.join(d, "images")))
+    fname = {"validation": "valdata.csv"}.get(split, split + "data.csv")
+    _hdr, rows = _read_csv(os.path.join(d, fname))
+    return [(os.path.join(d, "images", r[1]), r[2].strip()) for r in rows if len(r) > 2 and r[1] in names]
+
+
+def vqa_tables(root):
+    """-> (columns, {"train", "val", "test": [row]}, idx2ans).  A row is (image path, question, answer index, category,
+    mode) -- the fields evaluate.write_test_files writes."""
+    splits = {}
+    for key, fname, folder in (("train", "traindf.csv", "Train"), ("val", "valdf.csv", "Val"), ("test", "testdf.csv", "Test")):
+        hdr, rows = _read_csv(os.path.join(root, fname))
+        col = {c: i for i, c in enumerate(hdr)}
+        for need in ("img_id", "question", "answer", "category"):
+            if need not in col:
+                raise ValueError(f"{fname}: no column {need!r}")
+        splits[key] = [(os.path.join(root, folder, "images", r[col["img_id"]] + ".jpg"), r[col["question"]],
+                        r[col["answer"]].lower(), r[col["category"]].lower(), r[col["mode"]] if "mode" in col else key)
+                       for r in rows]
+    ans2idx = {}
+    for key in ("train", "val", "test"):
+        for r in splits[key]:
+            ans2idx.setdefault(r[2], len(ans2idx))
+    out = {k: [(p, q, ans2idx[a], c, m) for (p, q, a, c, m) in v] for k, v in splits.items()}
+    return ["img_id", "question", "answer", "category", "mode"], out, {i: a for a, i in ans2idx.items()}
+
+
+def load_keywords(root):
+    with open(os.path.join(root, "vocab", "med_vocab.pkl"), "rb") as f:
+        return text.get_keywords(pickle.load(f))
+
+
+# --------------------------------------------------------------------------- datasets (run in the worker processes)
+def decode(path):
+    from PIL import Image
+    with Image.open(path) as im:
+        return np.asarray(im.convert("RGB"), dtype=np.uint8)
+
+
+class RocoDataset(torch.utils.data.Dataset):
+    """item (epoch, index) -> (uint8 [H, W, 3], ids, seg, mask, target) as roco_utils.py:573-587 returns it"""
+
+    def __init__(self, rows, tokenizer, keywords, num_vis=5, max_position_embeddings=75, mlm_prob=0.15, seed=0):
+        self.rows, self.tok, self.kw = list(rows), tokenizer, frozenset(keywords)
+        self.num_vis, self.T, self.mlm_prob, self.seed = num_vis, max_position_embeddings, mlm_prob, seed
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __getitem__(self, key):
+        epoch, idx = key
+        path, caption = self.rows[idx]
+        ids, seg, mask, tgt = text.encode_text(caption, self.tok, self.kw, self.num_vis, self.T, self.mlm_prob,
+                                               sample_rng(self.seed, epoch, idx))
+        return decode(path), ids, seg, mask, tgt, idx
+
+
+class VqaDataset(torch.utils.data.Dataset):
+    """item (epoch, index) -> (uint8 [H, W, 3], ids, seg, mask, answer index) as vqamed2019/utils.py:234-257"""
+
+    def __init__(self, rows, tokenizer, max_position_embeddings=28):
+        self.rows, self.tok, self.T = list(rows), tokenizer, max_position_embeddings
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __getitem__(self, key):
+        _epoch, idx = key
+        path, question, ans = self.rows[idx][:3]
+        ids, seg, mask = (torch.tensor(v, dtype=torch.long) for v in text.encode_text_vqa(question, self.tok, self.T))
+        return decode(path), ids, seg, mask, torch.tensor(ans, dtype=torch.long), idx
+
+
+def collate(items):
+    """-> dict: pixels (uint8, the images back to back), shapes [B, 2] (h, w), ids / seg / mask [B, T], target,
+    index [B] (dataset rows)"""
+    imgs = [it[0] for it in items]
+    pixels = torch.from_numpy(np.concatenate([np.ascontiguousarray(a).reshape(-1) for a in imgs]))
+    return dict(pixels=pixels, shapes=torch.tensor([a.shape[:2] for a in imgs], dtype=torch.int64),
+                ids=torch.stack([it[1] for it in items]), seg=torch.stack([it[2] for it in items]),
+                mask=torch.stack([it[3] for it in items]), target=torch.stack([it[4] for it in items]),
+                index=torch.tensor([it[5] for it in items], dtype=torch.int64))
+
+
+def unpack(batch):
+    """collate's pixels + shapes -> list of uint8 [h, w, 3] arrays (host)"""
+    px, out, o = batch["pixels"].numpy(), [], 0
+    for h, w in batch["shapes"].tolist():
+        out.append(px[o:o + h * w * 3].reshape(h, w, 3))
+        o += h * w * 3
+    return out
+
+
+def offsets(shapes):
+    """byte offset of each image in collate's pixels"""
+    sz = [h * w * 3 for h, w in shapes.tolist()]
+    return [0] + np.cumsum(sz)[:-1].tolist()
+
+
+class EpochBatchSampler(torch.utils.data.Sampler):
+    """batches of (epoch, index): seeded permutation per epoch (or file order), this rank's DistributedSampler shard,
+    partial last batch kept"""
+
+    def __init__(self, n, batch_size, shuffle, seed=0, rank=0, world=1):
+        self.n, self.bs, self.shuffle, self.seed, self.rank, self.world = n, batch_size, shuffle, seed, rank, world
+        self.epoch = 0
+
+    def indices(self):
+        if self.shuffle:
+            g = torch.Generator().manual_seed(self.seed + self.epoch)
+            idx = torch.randperm(self.n, generator=g).tolist()
+        else:
+            idx = list(range(self.n))
+        total = int(math.ceil(self.n / self.world)) * self.world
+        idx += (idx * int(math.ceil(total / max(self.n, 1))))[:total - self.n]
+        return idx[self.rank:total:self.world]
+
+    def __iter__(self):
+        idx = self.indices()
+        for lo in range(0, len(idx), self.bs):
+            yield [(self.epoch, i) for i in idx[lo:lo + self.bs]]
+
+    def __len__(self):
+        return -(-int(math.ceil(self.n / self.world)) // self.bs)
+
+
+class HostLoader:
+    """iterates one epoch of host batches: (batch dict, augment params or None, {"epoch", "batch"})"""
+
+    def __init__(self, dataset, batch_size, shuffle=True, seed=0, rank=0, world=1, num_workers=None, aug=None,
+                 size=224, pin_memory=True):
+        self.sampler = EpochBatchSampler(len(dataset), batch_size, shuffle, seed, rank, world)
+        self.seed, self.rank, self.aug, self.size = seed, rank, aug, size
+        self.num_workers = default_workers() if num_workers is None else int(num_workers)
+        kw = {}
+        if self.num_workers > 0:
+            kw = dict(multiprocessing_context="forkserver", persistent_workers=True, prefetch_factor=2)
+        self.loader = torch.utils.data.DataLoader(dataset, batch_sampler=self.sampler, num_workers=self.num_workers,
+                                                  collate_fn=collate,
+                                                  pin_memory=bool(pin_memory) and torch.cuda.is_available(), **kw)
+
+    def set_epoch(self, epoch):
+        self.sampler.epoch = int(epoch)
+
+    def __len__(self):
+        return len(self.sampler)
+
+    def __iter__(self):
+        epoch = self.sampler.epoch
+        for b, batch in enumerate(self.loader):
+            params = None
+            if self.aug is not None:
+                n = batch["shapes"].shape[0]
+                params = sample_params(n, self.size, generator=batch_generator(self.seed, epoch, b, self.rank), **self.aug)
+            yield batch, params, dict(epoch=epoch, batch=b)
+
+
+def low_priority_stream(device):
+    """(torch stream, priority): the library's least-priority stream of `device`, kept for the life of the process"""
+    import ctypes as C
+    from . import _lib as L
+    with torch.cuda.device(device):
+        h, prio = C.c_void_p(), C.c_int()
+        L.check(L.lib().mmvqa_low_priority_stream(C.byref(h), C.byref(prio)))
+        return torch.cuda.ExternalStream(h.value, device=device), prio.value
+
+
+class _Slot:
+    def __init__(self):
+        self.tensors = None       # device buffers of the batch in this slot (reused)
+        self.ready = None         # recorded on the feeder stream after the batch's copies and augment
+        self.free = None          # recorded on the consumer's stream when it moved past the batch
+
+
+class DeviceFeeder:
+    """Iterator over device batches (img fp32 [B, 3, S, S], ids, seg, mask, target) of one epoch of a HostLoader.
+
+    `depth` device slots rotate.  When batch n is handed out, batches up to n + depth - 1 are already enqueued on the
+    feeder's stream (pinned H2D copies with non_blocking=True, then DeviceAugment.run_packed), so batch n + 1's copy
+    and augment are in the queue before the step of batch n syncs the host.  __next__ makes the caller's current
+    stream wait on the batch's ready event.  A slot is refilled only after the feeder stream has waited on an event
+    the consumer's stream recorded when the consumer moved on (the next __next__): the batch it returned stays valid
+    on that stream until then.
+
+    The feeder stream has the LEAST priority the device offers (HIP priority 1, below the normal 0 of the step's
+    streams; the library creates it, as torch's own stream pools on ROCm stop at normal priority): the augment is there
+    to fill the gaps the step leaves, and should yield to the step's kernels when both are ready.
+
+    The refill (DataLoader get + run_packed's packing, ~2 ms of host time per batch) runs inside __next__: in a
+    loop that syncs every step it sits between one step's sync and the next step's first launch.
+
+    log: one entry per batch handed out -- epoch, batch, dataset rows and the augment params used (tests rebuild the
+    batch from it)."""
+
+    def __init__(self, host: HostLoader, device, train=True, depth=2, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5),
+                 fused=True):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("DeviceFeeder runs on the GPU only (no CPU fallback)")
+        if depth < 1:
+            raise ValueError("depth must be >= 1")
+        self.host, self.dev, self.depth, self.fused = host, device, int(depth), fused
+        aug = host.aug or {}
+        self.aug = DeviceAugment(size=host.size, train=train, mean=mean, std=std, device=device, **aug)
+        self.stream, self.priority = low_priority_stream(device)
+        self.slots = [_Slot() for _ in range(self.depth)]
+        self.log = []
+        self._it = None
+
+    def set_epoch(self, epoch):
+        self.host.set_epoch(epoch)
+
+    def __len__(self):
+        return len(self.host)
+
+    def __iter__(self):
+        self._release()                # a consumer that left the last epoch early is still done with its batch
+        self._it = iter(self.host)
+        self._queue = deque()          # (slot, batch tuple, log entry) enqueued and not yet handed out
+        self._next_slot = 0
+        self._out = None               # slot handed out last
+        self._done = False
+        while len(self._queue) < self.depth and self._enqueue():
+            pass
+        return self
+
+    def _buffers(self, slot, B, T):
+        t = slot.tensors
+        S = self.aug.size
+        if t is None or t["img"].shape[0] < B or t["ids"].shape[1] != T:
+            with torch.cuda.stream(self.stream):
+                t = slot.tensors = dict(
+                    img=torch.empty(B, 3, S, S, dtype=torch.float32, device=self.dev),
+                    **{k: torch.empty(B, T, dtype=torch.int64, device=self.dev) for k in ("ids", "seg", "mask")},
+                    target=None)
+        return t
+
+    def _enqueue(self):
+        if self._done:
+            return False
+        try:
+            batch, params, meta = next(self._it)
+        except StopIteration:
+            self._done = True
+            return False
+        slot = self.slots[self._next_slot]
+        self._next_slot = (self._next_slot + 1) % self.depth
+        s = self.stream
+        if slot.free is not None:
+            s.wait_event(slot.free)         # the consumer is done with what this slot held
+        B, T = batch["ids"].shape
+        buf = self._buffers(slot, B, T)
+        with torch.cuda.stream(s):
+            tgt = batch["target"]
+            if buf["target"] is None or buf["target"].shape[0] < B or buf["target"].shape[1:] != tgt.shape[1:]:
+                buf["target"] = torch.empty((max(B, buf["img"].shape[0]),) + tuple(tgt.shape[1:]), dtype=tgt.dtype,
+                                            device=self.dev)
+            pix = batch["pixels"].to(self.dev, non_blocking=True)
+            img = buf["img"][:B]
+            self.aug.run_packed(pix, offsets(batch["shapes"]), batch["shapes"], params, s, fused=self.fused, out=img)
+            out = [img]
+            for k in ("ids", "seg", "mask", "target"):
+                d = buf[k][:B]
+                d.copy_(batch[k], non_blocking=True)
+                out.append(d)
+            slot.ready = torch.cuda.Event()
+            slot.ready.record(s)
+        entry = dict(meta, index=batch["index"].tolist(), params=params, shapes=batch["shapes"].tolist())
+        self._queue.append((slot, tuple(out), entry))
+        return True
+
+    def _release(self):
+        """the slot handed out last is free once the consumer's stream reaches this point"""
+        if getattr(self, "_out", None) is None:
+            return False
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.dev))
+        self._out.free = ev
+        self._out = None
+        return True
+
+    def __next__(self):
+        if self._it is None:
+            iter(self)
+        cur = torch.cuda.current_stream(self.dev)
+        if self._release():                 # the consumer moved past the previous batch: its slot may be refilled
+            while len(self._queue) < self.depth and self._enqueue():
+                pass
+        if not self._queue:
+            self._it = None
+            raise StopIteration
+        slot, out, entry = self._queue.popleft()
+        cur.wait_event(slot.ready)
+        self._out = slot
+        self.log.append(entry)
+        return out

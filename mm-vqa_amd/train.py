@@ -10,13 +10,17 @@ Kept from the reference: option names and defaults, Adam(lr) + ReduceLROnPlateau
 validation loss, zero_grad -> forward -> loss -> backward -> step order, loss / accuracy definitions,
 half-batch x 2 views for SupCon, best-val-loss checkpoint, the 5-epoch "recorder" dict
 {epoch, optimizer, scheduler, scaler, model}, --resume, the VQA early-stop counter and classifier[2] surgery.
-Not kept (out of scope): real datasets/tokenizer/augmentation (synthetic batches with the same
-layout stand in: mmvqa_amd.synth), wandb, BLEU.  One process per GPU under torch.distributed (RCCL).
+Data: with --data_dir (and --vocab_file, a local WordPiece vocab.txt) the mlm / vqa / eval loops read ROCO or
+VQA-Med 2019 from disk through mmvqa_amd.data (host decode + tokenisation in worker processes, the image transforms
+on the GPU in a DeviceFeeder); without it they run on synthetic batches of the same layout (mmvqa_amd.synth).
+SupCon stays synthetic.  Not kept (out of scope): wandb, BLEU.  One process per GPU under
+torch.distributed (RCCL).
 
     python -m mmvqa_amd.train mlm    --run_name r --mlm_prob 0.15 --epochs 2 --steps_per_epoch 20
     python -m mmvqa_amd.train supcon --run_name r --mlm_prob 0.15 --batch_size 32
     python -m mmvqa_amd.train vqa    --run_name r --loss ASLSingleLabel --batch_size 64
     python -m mmvqa_amd.train eval   --model_dir save/MLM/r.pt --num_classes 1552 --batch_size 16
+    python -m mmvqa_amd.train mlm    --data_dir roco-dataset/data --vocab_file vocab.txt --num_workers 4
 """
 from __future__ import annotations
 
@@ -29,6 +33,7 @@ import torch.distributed as dist
 from torch.optim import lr_scheduler
 
 from . import FusedAdam, Model, asl_loss, checkpoint, evaluate, mlm_loss, split_feat, supcon_loss, synth
+from . import data as D
 from .ddp import GradReducer, comm_info, global_supcon_views, sync_replicas
 
 
@@ -66,6 +71,42 @@ def common_args(p):
     p.add_argument("--emb_vocab", type=int, default=30522)
     p.add_argument("--bucket_mb", type=float, default=64.0, help="all-reduce bucket size (data parallel)")
     p.add_argument("--overlap_adam", action="store_true", help="Adam per finished gradient range beside the backward pass (measured time-neutral; not with --clip)")
+    p.add_argument("--data_dir", type=str, default=None,
+                   help="ROCO (mlm) or VQA-Med 2019 (vqa, eval) tree on disk; without it the batches are synthetic")
+    p.add_argument("--vocab_file", type=str, default=None, help="WordPiece vocab.txt (with --data_dir)")
+    p.add_argument("--num_workers", type=int, default=None, help="decode / tokenise worker processes (default min(4, usable cores))")
+    p.add_argument("--feeder_depth", type=int, default=2, help="device batches prepared ahead of the step")
+
+
+def feeder(args, ctx, dataset, train, aug=None):
+    """DeviceFeeder over one split (shuffled and augmented for training, file order and val transforms otherwise)"""
+    host = D.HostLoader(dataset, args.batch_size, shuffle=train, seed=args.seed, rank=ctx.rank, world=ctx.world,
+                        num_workers=args.num_workers, aug=aug if train else None, size=args.image_size)
+    return D.DeviceFeeder(host, ctx.dev, train=train, depth=args.feeder_depth)
+
+
+def tokenizer(args):
+    if not args.vocab_file:
+        raise ValueError("--data_dir needs --vocab_file (a local WordPiece vocab.txt; nothing is downloaded)")
+    return D.text.BertWordPiece(args.vocab_file)
+
+
+def roco_feeders(args, ctx):
+    """(train, validation) feeders of the ROCO tree: roco_utils.py:71-97, 567-587"""
+    tok, kw = tokenizer(args), D.load_keywords(args.data_dir)
+    ds = lambda split: D.RocoDataset(D.roco_table(args.data_dir, split), tok, kw, args.num_vis,   # noqa: E731
+                                     args.max_position_embeddings, args.mlm_prob, args.seed)
+    return feeder(args, ctx, ds("train"), True, D.ROCO_AUG), feeder(args, ctx, ds("validation"), False)
+
+
+def epoch_batches(fd, epoch, synthetic):
+    """the batches of one epoch: from the feeder (--data_dir) or synthetic(i) for i < --steps_per_epoch"""
+    if fd is None:
+        for b in synthetic:
+            yield b
+        return
+    fd.set_epoch(epoch)
+    yield from fd
 
 
 class Ctx:
@@ -232,23 +273,24 @@ def run_mlm(args):
     args.dataset, args.task = "roco", "MLM"
     model, opt, sched, red = build(args, ctx)
     T, B, V = args.max_position_embeddings, args.batch_size, args.vocab_size
+    tr_fd, args.val_feeder = roco_feeders(args, ctx) if args.data_dir else (None, None)
     start, kept = maybe_resume(args, model, opt, sched, "mlm")
     best = kept.get("best", float("inf"))
     for epoch in range(start, args.epochs):
         model.train()
-        tl, nm, nc = 0.0, 0.0, 0.0
-        for i in range(args.steps_per_epoch):
-            img, ids, seg, mask, tgt = synth.roco_batch(B, T, args.image_size, min(V, args.emb_vocab),
-                                                        seed=args.seed + 7919 * (epoch * 100003 + i) + ctx.rank,
-                                                        device=ctx.dev, mlm_prob=args.mlm_prob)
+        tl, nm, nc, steps = 0.0, 0.0, 0.0, 0
+        synthetic = (synth.roco_batch(B, T, args.image_size, min(V, args.emb_vocab),
+                                      seed=args.seed + 7919 * (epoch * 100003 + i) + ctx.rank,
+                                      device=ctx.dev, mlm_prob=args.mlm_prob) for i in range(args.steps_per_epoch))
+        for img, ids, seg, mask, tgt in epoch_batches(tr_fd, epoch, synthetic):
             _, _, stats = mlm_step(model, opt, red, ctx.world, (img, ids, seg, mask, tgt))
             s = stats.tolist()               # per-step host sync, as roco_utils.py:267
-            tl, nm, nc = tl + s[0], nm + s[1], nc + s[2]
+            tl, nm, nc, steps = tl + s[0], nm + s[1], nc + s[2], steps + 1
         vl, va = validate_mlm(args, ctx, model, epoch)
         sched.step(vl)
         if (epoch + 1) % 5 == 0 and ctx.rank == 0:
             save_recorder(args, epoch, model, opt, sched, "mlm", {"best": min(best, vl)})
-        tl = ctx.mean(tl / args.steps_per_epoch)
+        tl = ctx.mean(tl / max(steps, 1))
         if ctx.rank == 0:
             print(f"Epoch {epoch + 1}/{args.epochs} Learning rate: {opt.param_groups[0]['lr']:.7f}, Train loss: {tl:.4f}, "
                   f"Train acc: {100.0 * nc / max(nm, 1):.4f} ,Val loss: {vl:.4f}, Val acc: {va:.4f}", flush=True)
@@ -261,17 +303,17 @@ def run_mlm(args):
 @torch.no_grad()
 def validate_mlm(args, ctx, model, epoch):
     model.eval()
-    vl, nm, nc = 0.0, 0.0, 0.0
-    for i in range(args.val_steps):
-        img, ids, seg, mask, tgt = synth.roco_batch(args.batch_size, args.max_position_embeddings, args.image_size,
-                                                    min(args.vocab_size, args.emb_vocab), seed=10 ** 6 + i + ctx.rank,
-                                                    device=ctx.dev, mlm_prob=args.mlm_prob)
+    vl, nm, nc, steps = 0.0, 0.0, 0.0, 0
+    synthetic = (synth.roco_batch(args.batch_size, args.max_position_embeddings, args.image_size,
+                                  min(args.vocab_size, args.emb_vocab), seed=10 ** 6 + i + ctx.rank,
+                                  device=ctx.dev, mlm_prob=args.mlm_prob) for i in range(args.val_steps))
+    for img, ids, seg, mask, tgt in epoch_batches(getattr(args, "val_feeder", None), epoch, synthetic):
         out = model(img, ids, seg, mask)
         logits = out[0] if isinstance(out, tuple) else out
         _, _, stats = mlm_loss(logits, tgt)
         s = stats.tolist()
-        vl, nm, nc = vl + s[0], nm + s[1], nc + s[2]
-    return ctx.mean(vl / args.val_steps), 100.0 * nc / max(nm, 1)
+        vl, nm, nc, steps = vl + s[0], nm + s[1], nc + s[2], steps + 1
+    return ctx.mean(vl / max(steps, 1)), 100.0 * nc / max(nm, 1)
 
 
 # ----------------------------------------------------------------------------------------- MLM + SupCon
@@ -312,6 +354,13 @@ def run_supcon(args):
 def run_vqa(args):
     ctx = Ctx(args)
     args.dataset, args.task = "VQA-Med", "MLM"
+    tr_fd = va_fd = None
+    if args.data_dir:                                   # train.py:100-105: the classes are the answers of the tables
+        tok = tokenizer(args)
+        _cols, tabs, idx2ans = D.vqa_tables(args.data_dir)
+        args.num_classes = len(idx2ans)
+        tr_fd = feeder(args, ctx, D.VqaDataset(tabs["train"], tok, args.max_position_embeddings), True, D.VQA_AUG)
+        va_fd = feeder(args, ctx, D.VqaDataset(tabs["val"], tok, args.max_position_embeddings), False)
     C = args.num_classes
     model, opt, sched, red = build(args, ctx, n_classes=C)
     T, B = args.max_position_embeddings, args.batch_size
@@ -322,25 +371,28 @@ def run_vqa(args):
     best_acc2, counter = kept.get("best_acc2", 0.0), kept.get("counter", 0)
     for epoch in range(start, args.epochs):
         model.train()
-        tl = 0.0
-        for i in range(args.steps_per_epoch):
-            img, ids, seg, mask, tgt = synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C,
-                                                       seed=args.seed + 7919 * (epoch * 100003 + i) + ctx.rank, device=ctx.dev)
+        tl, steps = 0.0, 0
+        synthetic = (synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C,
+                                     seed=args.seed + 7919 * (epoch * 100003 + i) + ctx.rank, device=ctx.dev)
+                     for i in range(args.steps_per_epoch))
+        for img, ids, seg, mask, tgt in epoch_batches(tr_fd, epoch, synthetic):
             loss, _ = vqa_step(model, opt, red, ctx.world, (img, ids, seg, mask, tgt), crit, clip=args.clip)
-            tl += float(loss.detach())
+            tl, steps = tl + float(loss.detach()), steps + 1
         model.eval()
-        vl, correct, total = 0.0, 0, 0
+        vl, correct, total, vsteps = 0.0, 0, 0, 0
         with torch.no_grad():
-            for i in range(args.val_steps):
-                img, ids, seg, mask, tgt = synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=10 ** 6 + i, device=ctx.dev)
+            synthetic = (synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=10 ** 6 + i, device=ctx.dev)
+                         for i in range(args.val_steps))
+            for img, ids, seg, mask, tgt in epoch_batches(va_fd, epoch, synthetic):
                 logits, _, _ = model(img, ids, seg, mask)
                 vl += float(crit(logits, tgt))
                 correct += int((logits.softmax(1).argmax(1) == tgt).sum())   # utils.py:673
-                total += B
-        vl, acc = ctx.mean(vl / args.val_steps), 100.0 * correct / total
+                total += tgt.shape[0]
+                vsteps += 1
+        vl, acc = ctx.mean(vl / max(vsteps, 1)), 100.0 * correct / max(total, 1)
         sched.step(vl)
         if ctx.rank == 0:
-            print(f"Epoch {epoch + 1}/{args.epochs} lr {opt.param_groups[0]['lr']:.7f} train_loss {tl / args.steps_per_epoch:.4f} "
+            print(f"Epoch {epoch + 1}/{args.epochs} lr {opt.param_groups[0]['lr']:.7f} train_loss {tl / max(steps, 1):.4f} "
                   f"val_loss {vl:.4f} val_total_acc {acc:.2f}", flush=True)
         if ctx.rank == 0:
             if vl < best_loss:                   # train.py:264-268 "save by val loss"
@@ -373,6 +425,11 @@ def run_eval(args):
     dataset and its tokenizer are not in the image); everything after the loader is the reference's sequence."""
     ctx = Ctx(args)
     args.dataset, args.task = "VQA-Med", "MLM"
+    if args.data_dir:                                   # the real test split (vqamed2019/utils.py:51-79)
+        tok = tokenizer(args)
+        cols, tabs, idx2ans = D.vqa_tables(args.data_dir)
+        rows = tabs["test"]
+        args.num_classes = len(idx2ans)
     C = args.num_classes
     torch.manual_seed(args.seed)
     model = Model(args)
@@ -382,8 +439,9 @@ def run_eval(args):
         model.load_state_dict(checkpoint.read_state_dict(args.model_dir))        # eval.py:112
     model.to(ctx.dev)
     crit = (lambda lg, t: asl_loss(lg, t)) if args.loss == "ASLSingleLabel" else (lambda lg, t: mlm_loss(lg, t)[0])
-    cols, rows, idx2ans = synth.vqa_test_table(args.test_samples, C, seed=args.seed)
     B, T = args.batch_size, args.max_position_embeddings
+    if not args.data_dir:
+        cols, rows, idx2ans = synth.vqa_test_table(args.test_samples, C, seed=args.seed)
 
     def loader():                                                                # DataLoader(testdataset, batch_size, shuffle=False)
         for lo in range(0, len(rows), B):
@@ -392,8 +450,13 @@ def run_eval(args):
             tgt = torch.tensor([r[2] for r in rows[lo:lo + n]], dtype=torch.long, device=ctx.dev)
             yield img, ids, seg, mask, tgt
 
+    if args.data_dir:            # file order, every row on every rank; test() keeps the targets, so they leave the slots
+        test_fd = feeder(args, argparse.Namespace(rank=0, world=1, dev=ctx.dev), D.VqaDataset(rows, tok, T), False)
+        batches = ((img, ids, seg, mask, tgt.clone()) for img, ids, seg, mask, tgt in epoch_batches(test_fd, 0, None))
+    else:
+        batches = loader()
     cats = [r[3] for r in rows]
-    test_loss, predictions, acc, bleu = evaluate.test(loader(), model, crit, cats, idx2ans, category=args.category)
+    test_loss, predictions, acc, bleu = evaluate.test(batches, model, crit, cats, idx2ans, category=args.category)
     model_name = (args.model_dir or args.run_name).split("/")[-1]               # eval.py:68
     if ctx.rank == 0:
         paths = evaluate.write_test_files(rows, cols, predictions, idx2ans, args.save_dir, model_name)   # eval.py:171-178

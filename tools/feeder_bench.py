@@ -1,0 +1,206 @@
+#!/usr/bin/env python3
+"""Config-2 training step (resnet152 + transformer, ROCO MLM, B 16, 224^2, T 32) fed synthetically vs by the
+DeviceFeeder from JPEG files, in one process, in alternating blocks; plus the augment's GPU time per batch, fused
+(3 launches) vs fused=False (the multi-launch chain).
+
+A local ROCO-like tree is generated first (sides 400-1200 px, mixed aspect, baseline JPEG): no dataset is needed.
+Host cores used = CPU time of this process and of the decode workers over the wall time of the fed blocks.
+
+    python tools/feeder_bench.py --out profiles/feeder_cfg2.json
+"""
+import argparse
+import json
+import os
+import pickle
+import statistics
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+B, T, HW, VOCAB = 16, 32, 224, 30522
+WORDS = ("axial ct of the chest showing a mass in the left upper lobe , mri of the brain with lesion and edema "
+         "bilateral pleural effusion on chest x - ray normal liver kidney fracture nodule").split()
+
+
+def make_tree(root, n, seed=0):
+    from PIL import Image
+    rng = np.random.default_rng(seed)
+    d = os.path.join(root, "train", "radiology")
+    os.makedirs(os.path.join(d, "images"))
+    with open(os.path.join(d, "traindata.csv"), "w") as f:
+        f.write("id,name,caption\n")
+        for i in range(n):
+            h, w = (int(v) for v in rng.integers(400, 1201, 2))
+            yy, xx = np.mgrid[0:h, 0:w]
+            img = np.stack([127 + 120 * np.sin(xx / (5 + i % 7) + yy / 17.0), 127 + 120 * np.cos(xx / 13.0 - yy / 7.0),
+                            (xx * 3 + yy * 5 + i) % 256], -1) + rng.normal(0, 20, (h, w, 3))
+            Image.fromarray(np.clip(img, 0, 255).astype(np.uint8)).save(os.path.join(d, "images", f"{i}.jpg"), quality=90)
+            cap = " ".join(rng.choice(WORDS, int(rng.integers(8, 30))))
+            f.write(f"ROCO_{i},{i}.jpg,\"{cap}\"\n")
+    os.makedirs(os.path.join(root, "vocab"))
+    with open(os.path.join(root, "vocab", "med_vocab.pkl"), "wb") as f:
+        pickle.dump({"organ": ["chest", "brain", "liver", "kidney"], "finding": ["mass", "lesion", "fracture"]}, f)
+
+
+def cpu_seconds(pid):
+    try:
+        v = open(f"/proc/{pid}/stat").read().rsplit(")", 1)[1].split()
+        return (int(v[11]) + int(v[12])) / os.sysconf("SC_CLK_TCK")
+    except OSError:
+        return 0.0
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--images", type=int, default=384)
+    ap.add_argument("--blocks", type=int, default=4, help="block pairs (synthetic, fed)")
+    ap.add_argument("--steps", type=int, default=12, help="steps per block")
+    ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--workers", type=int, default=None)
+    ap.add_argument("--aug_reps", type=int, default=20)
+    ap.add_argument("--out", type=str, default=None)
+    a = ap.parse_args()
+
+    import mmvqa_amd
+    from mmvqa_amd import data as D
+    from mmvqa_amd import synth, text
+    from mmvqa_amd.ddp import GradReducer
+    from mmvqa_amd.train import mlm_step
+    from types import SimpleNamespace
+
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    torch.set_num_threads(min(D.usable_host_threads(), 16))
+    tmp = tempfile.mkdtemp(prefix="feeder_bench_")
+    t0 = time.perf_counter()
+    make_tree(tmp, a.images)
+    print(f"generated {a.images} JPEGs in {time.perf_counter() - t0:.1f} s", flush=True)
+
+    torch.manual_seed(1234)
+    args = SimpleNamespace(task="MLM", dataset="roco", transformer_model="transformer", cnn_encoder="resnet152",
+                           num_vis=5, hidden_size=768, n_layers=4, heads=12, hidden_dropout_prob=0.3,
+                           vocab_size=VOCAB, use_relu=False, max_position_embeddings=T)
+    model = mmvqa_amd.Model(args).to(dev).train()
+    model.set_seed(1234)
+    opt = mmvqa_amd.FusedAdam(model, lr=2e-5)
+    red = GradReducer(model.flat_grads, bucket_mb=64.0)
+    syn = synth.roco_batch(B, T, HW, VOCAB, seed=1234, device=dev)
+    model.tune(*syn[:4])
+
+    tok = text.BertWordPiece(os.path.join(ROOT, "tests", "golden", "text_vocab.txt"))
+    ds = D.RocoDataset(D.roco_table(tmp, "train"), tok, D.load_keywords(tmp), 5, T, 0.15, seed=1)
+    host = D.HostLoader(ds, B, shuffle=True, seed=1, num_workers=a.workers, aug=D.ROCO_AUG, size=HW)
+    fd = D.DeviceFeeder(host, dev, depth=2)
+
+    def fed_batches():
+        epoch = 0
+        while True:
+            fd.set_epoch(epoch)
+            for b in fd:
+                if b[0].shape[0] == B:
+                    yield b
+            epoch += 1
+
+    fed = fed_batches()
+    next_ms = []
+
+    def run(n, feed):
+        for _ in range(n):
+            if feed:
+                t = time.perf_counter()
+                b = next(fed)                    # host time between step n's sync and step n + 1's first launch
+                next_ms.append(1e3 * (time.perf_counter() - t))
+            else:
+                b = syn
+            _, _, stats = mlm_step(model, opt, red, 1, b)
+            stats.tolist()                       # the per-step host sync of train.py
+    run(a.warmup, False)
+    run(a.warmup, True)
+    torch.cuda.synchronize()
+    next_ms.clear()
+    workers = [w.pid for w in fd.host.loader._iterator._workers]
+    res = {"synthetic": [], "fed": []}
+    cpu_fed, wall_fed = 0.0, 0.0
+    for _ in range(a.blocks):
+        for kind in ("synthetic", "fed"):
+            c0 = time.process_time() + sum(cpu_seconds(p) for p in workers)
+            t0 = time.perf_counter()
+            run(a.steps, kind == "fed")
+            torch.cuda.synchronize()
+            dt = time.perf_counter() - t0
+            res[kind].append(1e3 * dt / a.steps)
+            if kind == "fed":
+                cpu_fed += time.process_time() + sum(cpu_seconds(p) for p in workers) - c0
+                wall_fed += dt
+            print(f"{kind:9s} {res[kind][-1]:.2f} ms/step", flush=True)
+
+    # the augment alone: one ROCO-like batch.  A bounded ~20 ms matmul block goes first on the stream, so the GPU
+    # reaches e0 only after run_packed has finished its host-side packing: e0 -> e1 spans the blob upload and the
+    # launches alone (GPU time), not the Python work before them.
+    rows = D.roco_table(tmp, "train")[:B]
+    imgs = [D.decode(p) for p, _ in rows]
+    src = torch.from_numpy(np.concatenate([x.reshape(-1) for x in imgs])).to(dev)
+    offs = np.cumsum([0] + [x.size for x in imgs])[:-1].tolist()
+    shapes = [x.shape[:2] for x in imgs]
+    aug = mmvqa_amd.augment.DeviceAugment(train=True, **D.ROCO_AUG)
+    params = mmvqa_amd.augment.sample_params(B, HW, generator=torch.Generator().manual_seed(3), **D.ROCO_AUG)
+    s = torch.cuda.Stream()
+    m = torch.randn(4096, 4096, device=dev)
+    mo = torch.empty_like(m)
+    aug_ms, host_ms, margins = {}, {}, []
+    for fused in (True, False):
+        ts, hs = [], []
+        for r in range(a.aug_reps + 3):
+            ep, e0, e1 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+            ep.record(s)
+            with torch.cuda.stream(s):
+                for _ in range(12):
+                    torch.mm(m, m, out=mo)
+            e0.record(s)
+            t = time.perf_counter()
+            aug.run_packed(src, offs, shapes, params, s, fused=fused)
+            h = 1e3 * (time.perf_counter() - t)
+            e1.record(s)
+            e1.synchronize()
+            if r >= 3:
+                ts.append(e0.elapsed_time(e1))
+                hs.append(h)
+                margins.append(ep.elapsed_time(e0) - h)   # > 0: the packing was done before the GPU reached e0
+        key = "fused" if fused else "multi_launch"
+        aug_ms[key], host_ms[key] = statistics.median(ts), statistics.median(hs)
+    syn_ms, fed_ms = statistics.median(res["synthetic"]), statistics.median(res["fed"])
+    out = dict(
+        workload="config 2 (resnet152 + transformer, ROCO MLM), B 16, 224^2, T 32, one GPU; fed = DeviceFeeder "
+                 f"(depth 2) over {a.images} generated JPEGs, sides 400-1200 px",
+        synthetic_ms_per_step=round(syn_ms, 3), fed_ms_per_step=round(fed_ms, 3), ratio=round(fed_ms / syn_ms, 4),
+        target_ratio=1.03, target_met=fed_ms / syn_ms <= 1.03,
+        blocks=dict(synthetic=[round(x, 3) for x in res["synthetic"]], fed=[round(x, 3) for x in res["fed"]]),
+        steps_per_block=a.steps, workers=host.num_workers, usable_host_threads=D.usable_host_threads(),
+        host_cores_used_fed=round(cpu_fed / wall_fed, 3),
+        augment_gpu_ms_per_batch=dict({k: round(v, 4) for k, v in aug_ms.items()},
+                                      method="cuda events around the upload + launches of run_packed, the stream held "
+                                             "behind a ~20 ms matmul block so that host packing is done first; "
+                                             f"otherwise idle device, median of {a.aug_reps}"),
+        augment_timing_min_margin_ms=round(min(margins), 3),
+        augment_host_ms_per_batch={k: round(v, 3) for k, v in host_ms.items()},
+        feeder_next_host_ms=dict(median=round(statistics.median(next_ms), 3), mean=round(statistics.mean(next_ms), 3),
+                                 max=round(max(next_ms), 3),
+                                 note="host time of DeviceFeeder.__next__ in the fed blocks (refill: DataLoader get + "
+                                      "run_packed packing), spent after the step's sync while the GPU has no step work"),
+        feeder_stream_priority=fd.priority,
+        fused_launch_used=bool(fd.aug.last_fused))
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
