@@ -478,6 +478,16 @@ size_t mmvqa_sizeof_aug_record(void);
  * out_f32 and of src_u8 is left as it was (no error is reported). */
 int mmvqa_aug_train_fused(mmvqa_stream_t s, unsigned char* src_u8, float* out_f32, const mmvqa_aug_record* records_dev,
                           const int* tables_dev, int B, int S, const float* mean3, const float* std3);
+/* mmvqa_aug_train_fused on V views of each of B images (SupCon's TwoCropTransform), in ONE launch: row v * B + n of
+ * scratch_u8 [V*B][S][S][3] and out_f32 [V*B][3][S][S] is view v of image n, under record v * B + n of records_dev.
+ * src_u8 [B][S][S][3] is the Resize + CenterCrop output; it is only read.  scratch_u8 ends holding each view's last
+ * byte stage.  Every view is bit for bit what mmvqa_aug_train_fused gives for the same image and record.  Returns
+ * MMVQA_ERR_ARG, with nothing enqueued, for null pointers, B, V or S <= 0, S * S * 3 bytes beyond the device's LDS,
+ * and when the byte ranges of src_u8 and scratch_u8 overlap.  Records as for mmvqa_aug_train_fused: a view whose
+ * record breaks the rules is skipped by the kernel, its rows of out_f32 and scratch_u8 left as they were. */
+int mmvqa_aug_train_fused_views(mmvqa_stream_t s, const unsigned char* src_u8, unsigned char* scratch_u8, float* out_f32,
+                                const mmvqa_aug_record* records_dev, const int* tables_dev, int B, int V, int S,
+                                const float* mean3, const float* std3);
 /* 1 if mmvqa_aug_train_fused takes images of S x S on the current device (S * S * 3 bytes fit its LDS), else 0 */
 int mmvqa_aug_train_fused_fits(int S);
 /* A non-blocking stream of the current device's LEAST priority (HIP: 1 = low, 0 = normal, negative = high), created

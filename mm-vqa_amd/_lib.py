@@ -162,6 +162,7 @@ SIGNATURES = {
     "mmvqa_aug_to_tensor": (_i, [_P, _P, _P, _i, _i, _P, _P]),
     "mmvqa_sizeof_aug_record": (_sz, []),
     "mmvqa_aug_train_fused": (_i, [_P, _P, _P, _P, _P, _i, _i, _P, _P]),
+    "mmvqa_aug_train_fused_views": (_i, [_P, _P, _P, _P, _P, _P, _i, _i, _i, _P, _P]),
     "mmvqa_aug_train_fused_fits": (_i, [_i]),
     "mmvqa_low_priority_stream": (_i, [C.POINTER(_P), C.POINTER(_i)]),
     "mmvqa_stream_priority": (_i, [_P, C.POINTER(_i)]),

@@ -17,7 +17,8 @@ pinned against Pillow itself, tests/test_augment.py).
 
 For a training loop, run_packed() takes a ragged batch that is already on the device and only enqueues work on a
 stream: one pinned blob of tables / jobs / records goes up by one async copy, then Resize+CenterCrop (2 launches) and
-the rest of the train chain in ONE launch (mmvqa_aug_train_fused), no host sync.
+the rest of the train chain in ONE launch (mmvqa_aug_train_fused), no host sync.  run_packed(..., views=2) is SupCon's
+TwoCropTransform: both views of every image from one resize, in one launch (mmvqa_aug_train_fused_views).
 """
 from __future__ import annotations
 
@@ -276,20 +277,31 @@ class DeviceAugment:
         return _FUSED_FITS[key]
 
     # ---- non-blocking entry point (training loops): ragged device batch in, work enqueued on `stream` only
-    def run_packed(self, src_dev, offsets, shapes, params=None, stream=None, fused=True, out=None, generator=None):
+    def run_packed(self, src_dev, offsets, shapes, params=None, stream=None, fused=True, out=None, generator=None,
+                   views=1):
         """src_dev: uint8 device tensor holding B decoded RGB images back to back, image n = [h_n, w_n, 3] at byte
         offsets[n]; shapes: [B, 2] (h, w).  Enqueues Resize+CenterCrop and, for training, the rest of the chain on
         `stream` (default: the current stream) and returns fp32 [B, 3, S, S] (`out`, if given, is filled).  No host
         sync: everything the kernels read (coefficient tables, jobs, records) goes up as ONE pinned blob with one async
         copy.  fused=False runs the multi-launch stages of __call__ instead (the reference the tests compare with); they
         also run when S x S images do not fit the device's LDS (fused_fits(), decided before anything is packed).
-        last_uint8 is the last byte stage."""
+        last_uint8 is the last byte stage.
+
+        views=V (training only) runs the random part of the chain V times per image, as SupCon's TwoCropTransform
+        does: Resize+CenterCrop once per image, then RandomResizedCrop -> ... -> Normalize on each view, fused into
+        one launch (mmvqa_aug_train_fused_views, which only reads the resized image).  params then holds V * B sets in
+        the reference's draw order, params[n * V + v] = view v of image n, i.e. sample_params(V * B, ...): consecutive
+        sets are the V calls of TwoCropTransform on one image.  The output is view-major, row v * B + n = view v of
+        image n (process_tensors' layout): out [V * B, 3, S, S], last_uint8 [V * B, S, S, 3]."""
         if self.dev.type != "cuda":
             raise L.MMVQAError("DeviceAugment runs on the GPU only (no CPU fallback)")
         S, lib = self.size, L.lib()
         shapes = [(int(h), int(w)) for h, w in (shapes.tolist() if isinstance(shapes, torch.Tensor) else shapes)]
         offsets = [int(o) for o in (offsets.tolist() if isinstance(offsets, torch.Tensor) else offsets)]
-        B = len(shapes)
+        B, V = len(shapes), int(views)
+        if V < 1 or (V > 1 and not self.train):
+            raise ValueError(f"run_packed: views = {views}: need >= 1, and more than one only for training")
+        R = V * B                                           # output rows: view v of image n is row v * B + n
         if B == 0 or len(offsets) != B:
             raise ValueError("run_packed: need one offset per image and at least one image")
         if src_dev.dtype != torch.uint8 or src_dev.device.type != "cuda" or not src_dev.is_contiguous():
@@ -299,15 +311,16 @@ class DeviceAugment:
                 raise ValueError(f"run_packed: image ({h}, {w}) at offset {o} lies outside the {src_dev.numel()}-byte batch")
         if self.train:
             if params is None:
-                params = sample_params(B, S, self.scale, self.ratio, self.degrees, self.jitter, generator)
-            if len(params) != B:
-                raise ValueError("run_packed: one parameter set per image")
+                params = sample_params(R, S, self.scale, self.ratio, self.degrees, self.jitter, generator)
+            if len(params) != R:
+                raise ValueError("run_packed: one parameter set per image and view")
             for p in params:
                 i, j, h, w = p["box"]
                 if not (0 <= i and 0 <= j and 0 < h and 0 < w and i + h <= S and j + w <= S):
                     raise ValueError(f"run_packed: crop box {p['box']} outside the {S}x{S} image")
         stream = stream if stream is not None else torch.cuda.current_stream(self.dev)
         use_fused = self.train and fused and self.fused_fits()
+        rows = params if V == 1 or not self.train else [params[n * V + v] for v in range(V) for n in range(B)]
         with torch.cuda.stream(stream):
             pack = _Pack()
             tabs = {}
@@ -325,7 +338,7 @@ class DeviceAugment:
                 ch, cv = tab(w, rw), tab(h, rh)
                 st1.append((h, w, rw, rh, ox, oy, ch, cv) + _window_rows(cv[3], oy, S))
             st2 = []                                        # RandomResizedCrop box -> (S, S)
-            for p in (params if self.train else []):
+            for p in (rows if self.train else []):
                 i, j, h, w = p["box"]
                 ch, cv = tab(w, S), tab(h, S)
                 st2.append((j, i, w, h, ch, cv) + _window_rows(cv[3], 0, S))
@@ -341,21 +354,21 @@ class DeviceAugment:
             put("tables", tables.nbytes)
             put("jobs1", B * njob)
             if use_fused:
-                put("recs", B * C.sizeof(L.AugRecord))
+                put("recs", R * C.sizeof(L.AugRecord))
             elif self.train:
-                put("jobs2", B * njob)
-                put("fix", B * 6 * 4)
-                put("ops", 4 * B * 4)
-                put("facs", 4 * B * 4)
+                put("jobs2", R * njob)
+                put("fix", R * 6 * 4)
+                put("ops", 4 * R * 4)
+                put("facs", 4 * R * 4)
             blob = torch.empty(sum_n[0], dtype=torch.uint8, device=self.dev)
             base = blob.data_ptr()
             rows1 = max(m[-1] for m in st1)
             tmp1 = torch.empty(B, rows1, S, 3, dtype=torch.uint8, device=self.dev)
             a0 = torch.empty(B, S, S, 3, dtype=torch.uint8, device=self.dev)
             if out is None:
-                out = torch.empty(B, 3, S, S, dtype=torch.float32, device=self.dev)
-            elif out.shape != (B, 3, S, S) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != a0.device:
-                raise ValueError("run_packed: out must be a contiguous fp32 [B, 3, S, S] tensor on the device")
+                out = torch.empty(R, 3, S, S, dtype=torch.float32, device=self.dev)
+            elif out.shape != (R, 3, S, S) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != a0.device:
+                raise ValueError("run_packed: out must be a contiguous fp32 [views * B, 3, S, S] tensor on the device")
             tb = base + lay["tables"]
 
             def job(jb, src, sh, sw, box, rsz, off, ch, cv, ty0, tyn, tmp, dst):
@@ -380,8 +393,8 @@ class DeviceAugment:
             emit("jobs1", jobs1)
             keep = [blob, tmp1, a0]
             if use_fused:
-                recs = (L.AugRecord * B)()
-                for n, (p, (bx, by, bw, bh, ch, cv, ty0, tyn)) in enumerate(zip(params, st2)):
+                recs = (L.AugRecord * R)()
+                for n, (p, (bx, by, bw, bh, ch, cv, ty0, tyn)) in enumerate(zip(rows, st2)):
                     r = recs[n]
                     r.bx, r.by, r.bw, r.bh, r.ty0, r.tyn = bx, by, bw, bh, ty0, tyn
                     r.hb, r.hk, r.hks, r.vb, r.vk, r.vks = ch[0], ch[1], ch[2], cv[0], cv[1], cv[2]
@@ -389,41 +402,50 @@ class DeviceAugment:
                     r.op[:] = list(p["order"])
                     r.factor[:] = [_factor(p, o) for o in p["order"]]
                 emit("recs", recs)
+                if V > 1:                                   # the views' scratch: a0 stays the read-only source
+                    scratch = torch.empty(R, S, S, 3, dtype=torch.uint8, device=self.dev)
+                    keep.append(scratch)
             elif self.train:
                 rows2 = max(m[-1] for m in st2)
-                tmp2 = torch.empty(B, rows2, S, 3, dtype=torch.uint8, device=self.dev)
-                a1 = torch.empty(B, S, S, 3, dtype=torch.uint8, device=self.dev)
+                tmp2 = torch.empty(R, rows2, S, 3, dtype=torch.uint8, device=self.dev)
+                a1 = torch.empty(R, S, S, 3, dtype=torch.uint8, device=self.dev)
                 a2 = torch.empty_like(a1)
-                lsum = torch.empty(B, dtype=torch.int64, device=self.dev)
-                jobs2 = (L.ResampleJob * B)()
-                for n, (bx, by, bw, bh, ch, cv, ty0, tyn) in enumerate(st2):
-                    job(jobs2[n], a0[n].data_ptr(), S, S, (bx, by, bw, bh), (S, S), (0, 0), ch, cv, ty0, tyn,
+                lsum = torch.empty(R, dtype=torch.int64, device=self.dev)
+                jobs2 = (L.ResampleJob * R)()
+                for n, (bx, by, bw, bh, ch, cv, ty0, tyn) in enumerate(st2):    # row n reads image n % B of a0
+                    job(jobs2[n], a0[n % B].data_ptr(), S, S, (bx, by, bw, bh), (S, S), (0, 0), ch, cv, ty0, tyn,
                         tmp2[n].data_ptr(), a1[n].data_ptr())
                 emit("jobs2", jobs2)
-                emit("fix", np.array([rotate_fix(p["angle"], S, S) for p in params], np.int32))
-                emit("ops", np.array([[p["order"][r] for p in params] for r in range(4)], np.int32))
-                emit("facs", np.array([[_factor(p, p["order"][r]) for p in params] for r in range(4)], np.float32))
+                emit("fix", np.array([rotate_fix(p["angle"], S, S) for p in rows], np.int32))
+                emit("ops", np.array([[p["order"][r] for p in rows] for r in range(4)], np.int32))
+                emit("facs", np.array([[_factor(p, p["order"][r]) for p in rows] for r in range(4)], np.float32))
                 keep += [tmp2, a1, a2, lsum]
             blob.copy_(host, non_blocking=True)             # the one upload (the pinned block is held until it is done)
             sp = C.c_void_p(stream.cuda_stream)
             L.check(lib.mmvqa_aug_resample(sp, C.c_void_p(base + lay["jobs1"]), B, rows1, S, S))
             final = a0
-            if use_fused:
+            if use_fused and V == 1:
                 L.check(lib.mmvqa_aug_train_fused(sp, L.ptr(a0), L.ptr(out), C.c_void_p(base + lay["recs"]),
                                                   C.c_void_p(tb), B, S, self.mean, self.std))
+            elif use_fused:
+                L.check(lib.mmvqa_aug_train_fused_views(sp, L.ptr(a0), L.ptr(scratch), L.ptr(out),
+                                                        C.c_void_p(base + lay["recs"]), C.c_void_p(tb), B, V, S,
+                                                        self.mean, self.std))
+                final = scratch
             elif self.train:
-                L.check(lib.mmvqa_aug_resample(sp, C.c_void_p(base + lay["jobs2"]), B, rows2, S, S))
-                L.check(lib.mmvqa_aug_rotate(sp, L.ptr(a1), L.ptr(a2), C.c_void_p(base + lay["fix"]), B, S, S))
+                L.check(lib.mmvqa_aug_resample(sp, C.c_void_p(base + lay["jobs2"]), R, rows2, S, S))
+                L.check(lib.mmvqa_aug_rotate(sp, L.ptr(a1), L.ptr(a2), C.c_void_p(base + lay["fix"]), R, S, S))
                 for r in range(4):
-                    L.check(lib.mmvqa_aug_jitter_round(sp, L.ptr(a2), C.c_void_p(base + lay["ops"] + 4 * B * r),
-                                                       C.c_void_p(base + lay["facs"] + 4 * B * r), L.ptr(lsum), B, S * S))
+                    L.check(lib.mmvqa_aug_jitter_round(sp, L.ptr(a2), C.c_void_p(base + lay["ops"] + 4 * R * r),
+                                                       C.c_void_p(base + lay["facs"] + 4 * R * r), L.ptr(lsum), R, S * S))
                 final = a2
             if not use_fused:
-                L.check(lib.mmvqa_aug_to_tensor(sp, L.ptr(final), L.ptr(out), B, S * S, self.mean, self.std))
+                L.check(lib.mmvqa_aug_to_tensor(sp, L.ptr(final), L.ptr(out), R, S * S, self.mean, self.std))
         # Every buffer above was allocated on `stream` and is used on it only, so the caching allocator may hand its
         # block out again as soon as it is freed: later work on `stream` is ordered after these launches.
         self.last_fused = use_fused
-        self.last_uint8 = final                             # [B, S, S, 3] after the last byte-valued stage (tests)
+        self.last_uint8 = final                             # [V * B, S, S, 3] after the last byte-valued stage (tests)
+        self.last_resized = a0       # [B, S, S, 3] Resize + CenterCrop (tests; the one-view fused launch overwrites it)
         self._packed_keep = keep
         return out
 

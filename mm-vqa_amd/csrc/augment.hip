@@ -15,7 +15,9 @@
 //   to_tensor  ToTensor (x / 255) + Normalize ((x - mean) / std) into fp32 NCHW
 // All of it is HBM-bound byte work: one thread per output pixel (3 channels), rows contiguous across lanes.
 // This file is compiled with -ffp-contract=off: Pillow's results depend on separately rounded multiplies and adds.
+#include <limits.h>
 #include <math.h>
+#include <stdint.h>
 
 #include "common.h"
 
@@ -238,27 +240,34 @@ __global__ __launch_bounds__(256) void to_tensor_kernel(const u8* __restrict__ i
 }
 
 // --------------------------------------------------------------------------- the whole train chain in one launch
-// One workgroup per image, the working image in LDS ([S][S][3] bytes, 147 KiB at S = 224).  The image's own slot of
-// img is its scratch once read: the two passes that read LDS while producing the next LDS contents write their
-// pixels there first (thread tid owns pixels tid, tid + 1024, ...), then copy them back after a barrier.  Holding
-// the ~49 pixels per thread in registers instead took the kernel past 128 VGPRs (spills) at 1024 threads.
-//   RandomResizedCrop  horizontal pass img -> LDS tmp [tyn][S][3]; vertical pass LDS -> img -> LDS
+// One workgroup per image, the working image in LDS ([S][S][3] bytes, 147 KiB at S = 224).  Row blockIdx.x of img is
+// the workgroup's scratch: the two passes that read LDS while producing the next LDS contents write their pixels
+// there first (thread tid owns pixels tid, tid + 1024, ...), then copy them back after a barrier.  Holding the ~49
+// pixels per thread in registers instead took the kernel past 128 VGPRs (spills) at 1024 threads.
+//   RandomResizedCrop  horizontal pass source -> LDS tmp [tyn][S][3]; vertical pass LDS -> img -> LDS
 //   RandomRotation     gather LDS -> img -> LDS
 //   ColorJitter        four rounds in LDS; contrast takes the exact integer L sum of the workgroup
 //   ToTensor+Normalize LDS -> out (fp32 NCHW); the final bytes also go back to img (the last byte stage)
 // Same arithmetic as resample_h/v, rotate_nearest, lsum + jitter and to_tensor above, so the result is bit-identical.
+// VIEWS = false (mmvqa_aug_train_fused): the source is the row's own slot of img, read by the horizontal pass before
+//   anything is written there (in place; vsrc is unused).
+// VIEWS = true (mmvqa_aug_train_fused_views): row blockIdx.x = v * nsrc + n is view v of image n; the source is image
+//   n of vsrc, which is only read and does not overlap img (the host checks it), so both pointers are __restrict__.
 #define AUG_FUSED_THREADS 1024
 
+template <bool VIEWS>
 __global__ __launch_bounds__(AUG_FUSED_THREADS) void aug_train_fused_kernel(u8* __restrict__ img, float* __restrict__ out,
                                                                             const mmvqa_aug_record* __restrict__ recs,
                                                                             const int* __restrict__ tabs, int S, float m0,
                                                                             float m1, float m2, float s0, float s1,
-                                                                            float s2) {
+                                                                            float s2, const u8* __restrict__ vsrc,
+                                                                            int nsrc) {
   extern __shared__ u8 lds[];                   // [S][S][3]
   __shared__ unsigned red[AUG_FUSED_THREADS / 64];
   const int tid = threadIdx.x, npix = S * S;
   const mmvqa_aug_record r = recs[blockIdx.x];
-  u8* src = img + (size_t)blockIdx.x * npix * 3;
+  u8* slot = img + (size_t)blockIdx.x * npix * 3;
+  const u8* src = VIEWS ? vsrc + (size_t)(blockIdx.x % nsrc) * npix * 3 : slot;
   // a record whose box leaves the image would make the passes below index outside LDS: that image's outputs are left
   // unwritten (documented in mmvqa.h; the host side validates every box before it packs the records)
   if (r.bx < 0 || r.by < 0 || r.bw <= 0 || r.bh <= 0 || r.bx + r.bw > S || r.by + r.bh > S || r.ty0 < 0 || r.tyn <= 0 ||
@@ -282,7 +291,8 @@ __global__ __launch_bounds__(AUG_FUSED_THREADS) void aug_train_fused_kernel(u8* 
     }
   }
   __syncthreads();
-  // vertical pass: lds tmp -> img (its own bytes were read above: from here on it is this workgroup's scratch, L2-hot)
+  // vertical pass: lds tmp -> img (in place, its own bytes were read above): from here on the slot is this
+  // workgroup's scratch, L2-hot
   {
     const int* vb = tabs + r.vb;
     const int* vk = tabs + r.vk;
@@ -297,13 +307,13 @@ __global__ __launch_bounds__(AUG_FUSED_THREADS) void aug_train_fused_kernel(u8* 
         const u8* q = col + t * S * 3;
         a0 += (int)q[0] * c; a1 += (int)q[1] * c; a2 += (int)q[2] * c;
       }
-      src[p * 3] = clip8_22(a0); src[p * 3 + 1] = clip8_22(a1); src[p * 3 + 2] = clip8_22(a2);
+      slot[p * 3] = clip8_22(a0); slot[p * 3 + 1] = clip8_22(a1); slot[p * 3 + 2] = clip8_22(a2);
     }
   }
   __syncthreads();                              // every read of tmp is done
   // (each thread reads back only the bytes it wrote itself: program order, no fence needed)
   for (int p = tid; p < npix; p += AUG_FUSED_THREADS) {
-    lds[p * 3] = src[p * 3]; lds[p * 3 + 1] = src[p * 3 + 1]; lds[p * 3 + 2] = src[p * 3 + 2];
+    lds[p * 3] = slot[p * 3]; lds[p * 3 + 1] = slot[p * 3 + 1]; lds[p * 3 + 2] = slot[p * 3 + 2];
   }
   __syncthreads();
   // RandomRotation (affine_fixed, nearest, black fill): gather lds -> img, then back to lds
@@ -316,11 +326,11 @@ __global__ __launch_bounds__(AUG_FUSED_THREADS) void aug_train_fused_kernel(u8* 
       const u8* q = lds + (yin * S + xin) * 3;
       c0 = q[0]; c1 = q[1]; c2 = q[2];
     }
-    src[p * 3] = c0; src[p * 3 + 1] = c1; src[p * 3 + 2] = c2;
+    slot[p * 3] = c0; slot[p * 3 + 1] = c1; slot[p * 3 + 2] = c2;
   }
   __syncthreads();                              // every gather is done
   for (int p = tid; p < npix; p += AUG_FUSED_THREADS) {
-    lds[p * 3] = src[p * 3]; lds[p * 3 + 1] = src[p * 3 + 1]; lds[p * 3 + 2] = src[p * 3 + 2];
+    lds[p * 3] = slot[p * 3]; lds[p * 3 + 1] = slot[p * 3 + 1]; lds[p * 3 + 2] = slot[p * 3 + 2];
   }
   // ColorJitter in LDS: round rnd applies op[rnd] (the image's own permutation).  Each thread keeps to the pixels it
   // wrote just above, so only contrast's mean (a sum over the whole image) needs the workgroup.
@@ -369,7 +379,7 @@ __global__ __launch_bounds__(AUG_FUSED_THREADS) void aug_train_fused_kernel(u8* 
     o[p] = ((float)cr / 255.0f - m0) / s0;
     o[npix + p] = ((float)cg / 255.0f - m1) / s1;
     o[2 * npix + p] = ((float)cb / 255.0f - m2) / s2;
-    src[p * 3] = (u8)cr; src[p * 3 + 1] = (u8)cg; src[p * 3 + 2] = (u8)cb;
+    slot[p * 3] = (u8)cr; slot[p * 3 + 1] = (u8)cg; slot[p * 3 + 2] = (u8)cb;
   }
 }
 
@@ -436,7 +446,8 @@ static int fused_lds_cap(int* cap_out) {
     HIP_CHECK_RET(hipDeviceGetAttribute(&a, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
     HIP_CHECK_RET(hipDeviceGetAttribute(&b, hipDeviceAttributeSharedMemPerBlockOptin, dev));
     const int cap = (a > b ? a : b) - (int)(sizeof(unsigned) * (AUG_FUSED_THREADS / 64));   // less the static LDS
-    HIP_CHECK_RET(hipFuncSetAttribute((const void*)aug_train_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+    HIP_CHECK_RET(hipFuncSetAttribute((const void*)aug_train_fused_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
+    HIP_CHECK_RET(hipFuncSetAttribute((const void*)aug_train_fused_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, cap));
     lds_cap[dev] = cap;
   }
   *cap_out = lds_cap[dev];
@@ -461,8 +472,31 @@ int mmvqa_aug_train_fused(mmvqa_stream_t s, unsigned char* src_u8, float* out_f3
   const size_t lds = (size_t)S * S * 3;
   if (lds > (size_t)cap)
     return mmvqa_set_error(MMVQA_ERR_ARG, "aug_train_fused: S = %d needs %zu B of LDS, the device gives %d", S, lds, cap);
-  hipLaunchKernelGGL(aug_train_fused_kernel, dim3(B), dim3(AUG_FUSED_THREADS), lds, (hipStream_t)s, src_u8, out_f32,
-                     records_dev, tables_dev, S, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2]);
+  hipLaunchKernelGGL(aug_train_fused_kernel<false>, dim3(B), dim3(AUG_FUSED_THREADS), lds, (hipStream_t)s, src_u8, out_f32,
+                     records_dev, tables_dev, S, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2],
+                     (const u8*)nullptr, B);
+  KERNEL_CHECK_RET();
+  return MMVQA_OK;
+}
+
+int mmvqa_aug_train_fused_views(mmvqa_stream_t s, const unsigned char* src_u8, unsigned char* scratch_u8, float* out_f32,
+                                const mmvqa_aug_record* records_dev, const int* tables_dev, int B, int V, int S,
+                                const float* mean3, const float* std3) {
+  if (!src_u8 || !scratch_u8 || !out_f32 || !records_dev || !tables_dev || !mean3 || !std3 || B <= 0 || V <= 0 || S <= 0)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "aug_train_fused_views: bad arguments");
+  const size_t img = (size_t)S * S * 3;
+  if ((size_t)V * B > (size_t)INT_MAX)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "aug_train_fused_views: %d x %d views are too many for one launch", V, B);
+  const uintptr_t s0 = (uintptr_t)src_u8, s1 = s0 + img * B, d0 = (uintptr_t)scratch_u8, d1 = d0 + img * V * B;
+  if (s0 < d1 && d0 < s1)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "aug_train_fused_views: src_u8 and scratch_u8 overlap");
+  int cap = 0;
+  const int rc = fused_lds_cap(&cap);
+  if (rc != MMVQA_OK) return rc;
+  if (img > (size_t)cap)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "aug_train_fused_views: S = %d needs %zu B of LDS, the device gives %d", S, img, cap);
+  hipLaunchKernelGGL(aug_train_fused_kernel<true>, dim3(V * B), dim3(AUG_FUSED_THREADS), img, (hipStream_t)s, scratch_u8,
+                     out_f32, records_dev, tables_dev, S, mean3[0], mean3[1], mean3[2], std3[0], std3[1], std3[2], src_u8, B);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }

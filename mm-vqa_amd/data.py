@@ -8,6 +8,10 @@ Tables follow the reference's on-disk layouts:
                                                      traindf / valdf / testdf.csv, {Train,Val,Test}/images/<img_id>.jpg;
                                                      category and answer lower-cased; ans2idx over
                                                      concat(train, val, test) in first-seen order
+  ROCO SupCon pretrain/roco_supcon_train.py:83-85, models/SupConLoss/supcon_utils.py:218-256
+                                                     the ROCO train table with back-translations in columns 3-5
+                                                     (fr / de / es); three named rows removed; an item is both views'
+                                                     image, the caption and one translation, each MLM-masked
 (The reference also shuffles each table with DataFrame.sample(frac=pct); here the file order is kept and the epoch
 order is a seeded permutation, so ans2idx is the first-seen order of the files.)
 
@@ -100,6 +104,34 @@ def roco_table(root, split):
     return [(os.path.join(d, "images", r[1]), r[2].strip()) for r in rows if len(r) > 2 and r[1] in names]
 
 
+# rows roco_supcon_train.py:83-85 removes from the SupCon train table (two without an image, one without a caption)
+SUPCON_DROPPED = ("PMC4345544_yjbm_88_1_93_g04.jpg", "PMC4240561_MA-68-291-g002.jpg", "PMC4093298_jadp-03-059-g02.jpg")
+
+
+def roco_supcon_table(root):
+    """[(image path, caption, (t3, t4, t5))] of <root>/train/radiology/traindata.csv for SupCon: rows without an image
+    dropped (in order), then the three rows of SUPCON_DROPPED.  The translations are columns 3-5 by position, as
+    supcon_utils.py:228-236 reads them.  A kept row with fewer than 6 fields or an empty translation raises
+    ValueError naming the file and row (the reference would fail later, on the draw that picks the cell)."""
+    d = os.path.join(root, "train", "radiology")
+    names = set(os.listdir(os.path.join(d, "images")))
+    path = os.path.join(d, "traindata.csv")
+    _hdr, rows = _read_csv(path)
+    out = []
+    for k, r in enumerate(rows, start=1):
+        if len(r) < 2 or r[1] not in names or r[1] in SUPCON_DROPPED:
+            continue
+        if len(r) < 6:
+            raise ValueError(f"{path}: row {k} (after the header) has {len(r)} fields; SupCon needs 6 "
+                             "(id, name, caption and three translations)")
+        tr = tuple(c.strip() for c in r[3:6])
+        for c, t in enumerate(tr, start=3):
+            if not t:
+                raise ValueError(f"{path}: row {k} (after the header) has an empty translation in column {c}")
+        out.append((os.path.join(d, "images", r[1]), r[2].strip(), tr))
+    return out
+
+
 def vqa_tables(root):
     """-> (columns, {"train", "val", "test": [row]}, idx2ans).  A row is (image path, question, answer index, category,
     mode) -- the fields evaluate.write_test_files writes."""
@@ -178,6 +210,51 @@ def collate(items):
                 index=torch.tensor([it[5] for it in items], dtype=torch.int64))
 
 
+def collate_supcon(items):
+    """RocoSupConDataset items -> collate's dict with n images and the text already in process_tensors' layout
+    (supcon_utils.py:253-256): ids = (captions; translations), target = (caption targets; translation targets),
+    seg / mask = the captions' twice -- the translation half keeps the caption's mask even where its length differs,
+    as in the reference.  ids / seg / mask / target are [2n, T], index [n]."""
+    imgs = [it[0] for it in items]
+    pixels = torch.from_numpy(np.concatenate([np.ascontiguousarray(a).reshape(-1) for a in imgs]))
+    col = lambda i: torch.stack([it[i] for it in items])   # noqa: E731
+    seg, mask = col(3), col(4)
+    return dict(pixels=pixels, shapes=torch.tensor([a.shape[:2] for a in imgs], dtype=torch.int64),
+                ids=torch.cat([col(1), col(2)]), seg=torch.cat([seg, seg]), mask=torch.cat([mask, mask]),
+                target=torch.cat([col(5), col(6)]), index=torch.tensor([it[7] for it in items], dtype=torch.int64))
+
+
+class RocoSupConDataset(torch.utils.data.Dataset):
+    """item (epoch, index) -> (uint8 [H, W, 3], ids, aug_ids, seg, mask, tgt, aug_tgt, index) as supcon_utils.py:218-232
+    returns it (the image untransformed: both views are made on the device).  One rng, sample_rng(seed, epoch,
+    index), is drawn in the reference's order: the caption's MLM masking, then randint(3, 5) for the translation
+    column (get_translation), then the translation's masking.  The translation's seg / mask are not kept: the
+    reference uses the caption's for both halves (process_tensors)."""
+
+    collate = staticmethod(collate_supcon)     # HostLoader packs its batches with it
+
+    def __init__(self, rows, tokenizer, keywords, num_vis=5, max_position_embeddings=75, mlm_prob=0.15, seed=0):
+        self.rows, self.tok, self.kw = list(rows), tokenizer, frozenset(keywords)
+        self.num_vis, self.T, self.mlm_prob, self.seed = num_vis, max_position_embeddings, mlm_prob, seed
+
+    def __len__(self):
+        return len(self.rows)
+
+    def encode(self, epoch, idx):
+        """the item's text: (ids, aug_ids, seg, mask, tgt, aug_tgt)"""
+        _path, caption, trans = self.rows[idx]
+        rng = sample_rng(self.seed, epoch, idx)
+        ids, seg, mask, tgt = text.encode_text(caption, self.tok, self.kw, self.num_vis, self.T, self.mlm_prob, rng)
+        aug = trans[rng.randint(3, 5) - 3]
+        aug_ids, _seg, _mask, aug_tgt = text.encode_text(aug, self.tok, self.kw, self.num_vis, self.T, self.mlm_prob,
+                                                         rng)
+        return ids, aug_ids, seg, mask, tgt, aug_tgt
+
+    def __getitem__(self, key):
+        epoch, idx = key
+        return (decode(self.rows[idx][0]),) + self.encode(epoch, idx) + (idx,)
+
+
 def unpack(batch):
     """collate's pixels + shapes -> list of uint8 [h, w, 3] arrays (host)"""
     px, out, o = batch["pixels"].numpy(), [], 0
@@ -221,18 +298,22 @@ class EpochBatchSampler(torch.utils.data.Sampler):
 
 
 class HostLoader:
-    """iterates one epoch of host batches: (batch dict, augment params or None, {"epoch", "batch"})"""
+    """iterates one epoch of host batches: (batch dict, augment params or None, {"epoch", "batch"}).  With views=V the
+    params are V per image, sample_params(V * n, ...) from the batch's generator: params[i * V + v] is view v of
+    image i (TwoCropTransform's V calls in a row).  A dataset with a `collate` attribute packs its own batches."""
 
     def __init__(self, dataset, batch_size, shuffle=True, seed=0, rank=0, world=1, num_workers=None, aug=None,
-                 size=224, pin_memory=True):
+                 size=224, pin_memory=True, views=1):
+        if int(views) < 1:
+            raise ValueError("views must be >= 1")
         self.sampler = EpochBatchSampler(len(dataset), batch_size, shuffle, seed, rank, world)
-        self.seed, self.rank, self.aug, self.size = seed, rank, aug, size
+        self.seed, self.rank, self.aug, self.size, self.views = seed, rank, aug, size, int(views)
         self.num_workers = default_workers() if num_workers is None else int(num_workers)
         kw = {}
         if self.num_workers > 0:
             kw = dict(multiprocessing_context="forkserver", persistent_workers=True, prefetch_factor=2)
         self.loader = torch.utils.data.DataLoader(dataset, batch_sampler=self.sampler, num_workers=self.num_workers,
-                                                  collate_fn=collate,
+                                                  collate_fn=getattr(dataset, "collate", None) or collate,
                                                   pin_memory=bool(pin_memory) and torch.cuda.is_available(), **kw)
 
     def set_epoch(self, epoch):
@@ -247,7 +328,8 @@ class HostLoader:
             params = None
             if self.aug is not None:
                 n = batch["shapes"].shape[0]
-                params = sample_params(n, self.size, generator=batch_generator(self.seed, epoch, b, self.rank), **self.aug)
+                params = sample_params(self.views * n, self.size, generator=batch_generator(self.seed, epoch, b, self.rank),
+                                       **self.aug)
             yield batch, params, dict(epoch=epoch, batch=b)
 
 
@@ -270,6 +352,8 @@ class _Slot:
 
 class DeviceFeeder:
     """Iterator over device batches (img fp32 [B, 3, S, S], ids, seg, mask, target) of one epoch of a HostLoader.
+    With views=V (the HostLoader's, SupCon: 2) a batch of n images gives img [V * n, 3, S, S], view-major (row
+    v * n + i = view v of image i), and the text tensors as the host batch holds them.
 
     `depth` device slots rotate.  When batch n is handed out, batches up to n + depth - 1 are already enqueued on the
     feeder's stream (pinned H2D copies with non_blocking=True, then DeviceAugment.run_packed), so batch n + 1's copy
@@ -296,6 +380,7 @@ class DeviceFeeder:
         if depth < 1:
             raise ValueError("depth must be >= 1")
         self.host, self.dev, self.depth, self.fused = host, device, int(depth), fused
+        self.views = getattr(host, "views", 1)
         aug = host.aug or {}
         self.aug = DeviceAugment(size=host.size, train=train, mean=mean, std=std, device=device, **aug)
         self.stream, self.priority = low_priority_stream(device)
@@ -320,13 +405,13 @@ class DeviceFeeder:
             pass
         return self
 
-    def _buffers(self, slot, B, T):
+    def _buffers(self, slot, NI, B, T):
         t = slot.tensors
         S = self.aug.size
-        if t is None or t["img"].shape[0] < B or t["ids"].shape[1] != T:
+        if t is None or t["img"].shape[0] < NI or t["ids"].shape[0] < B or t["ids"].shape[1] != T:
             with torch.cuda.stream(self.stream):
                 t = slot.tensors = dict(
-                    img=torch.empty(B, 3, S, S, dtype=torch.float32, device=self.dev),
+                    img=torch.empty(NI, 3, S, S, dtype=torch.float32, device=self.dev),
                     **{k: torch.empty(B, T, dtype=torch.int64, device=self.dev) for k in ("ids", "seg", "mask")},
                     target=None)
         return t
@@ -345,15 +430,17 @@ class DeviceFeeder:
         if slot.free is not None:
             s.wait_event(slot.free)         # the consumer is done with what this slot held
         B, T = batch["ids"].shape
-        buf = self._buffers(slot, B, T)
+        NI = self.views * batch["shapes"].shape[0]          # image rows: views x images
+        buf = self._buffers(slot, NI, B, T)
         with torch.cuda.stream(s):
             tgt = batch["target"]
             if buf["target"] is None or buf["target"].shape[0] < B or buf["target"].shape[1:] != tgt.shape[1:]:
-                buf["target"] = torch.empty((max(B, buf["img"].shape[0]),) + tuple(tgt.shape[1:]), dtype=tgt.dtype,
+                buf["target"] = torch.empty((max(B, buf["ids"].shape[0]),) + tuple(tgt.shape[1:]), dtype=tgt.dtype,
                                             device=self.dev)
             pix = batch["pixels"].to(self.dev, non_blocking=True)
-            img = buf["img"][:B]
-            self.aug.run_packed(pix, offsets(batch["shapes"]), batch["shapes"], params, s, fused=self.fused, out=img)
+            img = buf["img"][:NI]
+            self.aug.run_packed(pix, offsets(batch["shapes"]), batch["shapes"], params, s, fused=self.fused, out=img,
+                                views=self.views)
             out = [img]
             for k in ("ids", "seg", "mask", "target"):
                 d = buf[k][:B]

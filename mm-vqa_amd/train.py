@@ -10,10 +10,11 @@ Kept from the reference: option names and defaults, Adam(lr) + ReduceLROnPlateau
 validation loss, zero_grad -> forward -> loss -> backward -> step order, loss / accuracy definitions,
 half-batch x 2 views for SupCon, best-val-loss checkpoint, the 5-epoch "recorder" dict
 {epoch, optimizer, scheduler, scaler, model}, --resume, the VQA early-stop counter and classifier[2] surgery.
-Data: with --data_dir (and --vocab_file, a local WordPiece vocab.txt) the mlm / vqa / eval loops read ROCO or
-VQA-Med 2019 from disk through mmvqa_amd.data (host decode + tokenisation in worker processes, the image transforms
-on the GPU in a DeviceFeeder); without it they run on synthetic batches of the same layout (mmvqa_amd.synth).
-SupCon stays synthetic.  Not kept (out of scope): wandb, BLEU.  One process per GPU under
+Data: with --data_dir (and --vocab_file, a local WordPiece vocab.txt) every loop reads ROCO or VQA-Med 2019 from
+disk through mmvqa_amd.data (host decode + tokenisation in worker processes, the image transforms on the GPU in a
+DeviceFeeder); without it they run on synthetic batches of the same layout (mmvqa_amd.synth).  SupCon reads the ROCO
+train table with its back-translations and makes both views of each image on the device in one launch
+(roco_supcon_train.py:83-85,137; supcon_utils.py:218-256).  Not kept (out of scope): wandb, BLEU.  One process per GPU under
 torch.distributed (RCCL).
 
     python -m mmvqa_amd.train mlm    --run_name r --mlm_prob 0.15 --epochs 2 --steps_per_epoch 20
@@ -21,6 +22,7 @@ torch.distributed (RCCL).
     python -m mmvqa_amd.train vqa    --run_name r --loss ASLSingleLabel --batch_size 64
     python -m mmvqa_amd.train eval   --model_dir save/MLM/r.pt --num_classes 1552 --batch_size 16
     python -m mmvqa_amd.train mlm    --data_dir roco-dataset/data --vocab_file vocab.txt --num_workers 4
+    python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --batch_size 32
 """
 from __future__ import annotations
 
@@ -72,16 +74,17 @@ def common_args(p):
     p.add_argument("--bucket_mb", type=float, default=64.0, help="all-reduce bucket size (data parallel)")
     p.add_argument("--overlap_adam", action="store_true", help="Adam per finished gradient range beside the backward pass (measured time-neutral; not with --clip)")
     p.add_argument("--data_dir", type=str, default=None,
-                   help="ROCO (mlm) or VQA-Med 2019 (vqa, eval) tree on disk; without it the batches are synthetic")
+                   help="ROCO (mlm, supcon) or VQA-Med 2019 (vqa, eval) tree on disk; without it the batches are synthetic")
     p.add_argument("--vocab_file", type=str, default=None, help="WordPiece vocab.txt (with --data_dir)")
     p.add_argument("--num_workers", type=int, default=None, help="decode / tokenise worker processes (default min(4, usable cores))")
     p.add_argument("--feeder_depth", type=int, default=2, help="device batches prepared ahead of the step")
 
 
-def feeder(args, ctx, dataset, train, aug=None):
+def feeder(args, ctx, dataset, train, aug=None, batch_size=None, views=1):
     """DeviceFeeder over one split (shuffled and augmented for training, file order and val transforms otherwise)"""
-    host = D.HostLoader(dataset, args.batch_size, shuffle=train, seed=args.seed, rank=ctx.rank, world=ctx.world,
-                        num_workers=args.num_workers, aug=aug if train else None, size=args.image_size)
+    host = D.HostLoader(dataset, batch_size or args.batch_size, shuffle=train, seed=args.seed, rank=ctx.rank,
+                        world=ctx.world, num_workers=args.num_workers, aug=aug if train else None, size=args.image_size,
+                        views=views)
     return D.DeviceFeeder(host, ctx.dev, train=train, depth=args.feeder_depth)
 
 
@@ -97,6 +100,17 @@ def roco_feeders(args, ctx):
     ds = lambda split: D.RocoDataset(D.roco_table(args.data_dir, split), tok, kw, args.num_vis,   # noqa: E731
                                      args.max_position_embeddings, args.mlm_prob, args.seed)
     return feeder(args, ctx, ds("train"), True, D.ROCO_AUG), feeder(args, ctx, ds("validation"), False)
+
+
+def roco_supcon_feeders(args, ctx, pairs):
+    """(train, validation) feeders of SupCon: `pairs` samples x 2 views per train batch (roco_supcon_train.py:134-139,
+    drop_last=False), the plain ROCO validation split at the full --batch_size"""
+    tok, kw = tokenizer(args), D.load_keywords(args.data_dir)
+    tr = D.RocoSupConDataset(D.roco_supcon_table(args.data_dir), tok, kw, args.num_vis, args.max_position_embeddings,
+                             args.mlm_prob, args.seed)
+    va = D.RocoDataset(D.roco_table(args.data_dir, "validation"), tok, kw, args.num_vis, args.max_position_embeddings,
+                       args.mlm_prob, args.seed)
+    return (feeder(args, ctx, tr, True, D.ROCO_AUG, batch_size=pairs, views=2), feeder(args, ctx, va, False))
 
 
 def epoch_batches(fd, epoch, synthetic):
@@ -325,25 +339,42 @@ def run_supcon(args):
     n = args.batch_size // 2                      # roco_supcon_train.py:137: the loader yields bs//2 pairs
     if n < 1:
         raise ValueError("--batch_size must be >= 2 (two views per sample)")
+    tr_fd = None
+    if args.data_dir:                             # fed batches come in process_tensors' layout (data.collate_supcon)
+        tr_fd, args.val_feeder = roco_supcon_feeders(args, ctx, n)
     start, kept = maybe_resume(args, model, opt, sched, "supcon")
     best = kept.get("best", float("inf"))
-    for epoch in range(start, args.epochs):
-        model.train()
-        tl = 0.0
+
+    def synthetic(epoch):
         for i in range(args.steps_per_epoch):
             sd = args.seed + 7919 * (epoch * 100003 + i) + ctx.rank
             a = synth.roco_batch(n, T, args.image_size, min(V, args.emb_vocab), seed=sd, device=ctx.dev, mlm_prob=args.mlm_prob)
             b = synth.roco_batch(n, T, args.image_size, min(V, args.emb_vocab), seed=sd + 1, device=ctx.dev, mlm_prob=args.mlm_prob)
-            batch = process_tensors((a[0], b[0]), a[1], b[1], a[2], a[3], a[4], b[4])
-            loss, _, _ = supcon_step(model, opt, red, ctx.world, batch)
-            tl += float(loss.detach())
+            yield process_tensors((a[0], b[0]), a[1], b[1], a[2], a[3], a[4], b[4])
+
+    for epoch in range(start, args.epochs):
+        model.train()
+        tl, nm, nc, steps = 0.0, 0.0, 0.0, 0
+        for batch in epoch_batches(tr_fd, epoch, synthetic(epoch)):
+            loss, _, stats = supcon_step(model, opt, red, ctx.world, batch)
+            tl, steps = tl + float(loss.detach()), steps + 1
+            if tr_fd is not None:                 # the MLM accuracy train_one_epoch returns (supcon_utils.py:296-318)
+                s = stats.tolist()
+                nm, nc = nm + s[1], nc + s[2]
         vl, va = validate_mlm(args, ctx, model, epoch)
         sched.step(vl)
         if (epoch + 1) % 5 == 0 and ctx.rank == 0:       # roco_supcon_train.py:177-184
             save_recorder(args, epoch, model, opt, sched, "supcon", {"best": min(best, vl)})
+        if tr_fd is not None:
+            tl = ctx.mean(tl / max(steps, 1))
         if ctx.rank == 0:
-            print(f"Epoch {epoch + 1}/{args.epochs} Learning rate: {opt.param_groups[0]['lr']:.7f}, "
-                  f"Train loss: {tl / args.steps_per_epoch:.4f}, Val loss: {vl:.4f}, Val acc: {va:.4f}", flush=True)
+            if tr_fd is not None:                         # roco_supcon_train.py:193
+                print(f"Epoch {epoch + 1}/{args.epochs} Learning rate: {opt.param_groups[0]['lr']:.7f}, "
+                      f"Train loss: {tl:.4f}, Train acc: {100.0 * nc / max(nm, 1):.4f} ,Val loss: {vl:.4f}, "
+                      f"Val acc: {va:.4f}", flush=True)
+            else:
+                print(f"Epoch {epoch + 1}/{args.epochs} Learning rate: {opt.param_groups[0]['lr']:.7f}, "
+                      f"Train loss: {tl / args.steps_per_epoch:.4f}, Val loss: {vl:.4f}, Val acc: {va:.4f}", flush=True)
             if vl < best:                                 # roco_supcon_train.py:199-202
                 save_model(args, model)
         best = min(best, vl)
