@@ -2,9 +2,12 @@
 """Headline benchmark: samples/s of one full ROCO-MLM training step (BASELINE.json configs[1]):
 resnet152 + transformer, num_vis 5, hidden 768, per-GPU batch 16, 224x224, T=32, fp32;
 forward + MLM loss + backward + (gradient all-reduce) + Adam, dropout active, train-mode BatchNorm,
-inputs resident in HBM.  Prints ONE JSON line (see the driver contract in the task statement).
+inputs resident in HBM.  Prints ONE JSON line on stdout.  A plain run sets up, tunes, warms up, times the steps,
+writes --dump-outputs and prints that line; --full adds what takes runs of its own: `roofline` (extra profiled steps)
+and `cpu_baseline` (the CPU oracle timed on the host; config 2 on one GPU).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --full [--no-roofline] [--no-cpu-baseline]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...
 """
 import argparse
@@ -201,8 +204,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the result of the timed steps also measure `roofline` and `cpu_baseline` (off by default: a "
+                         "plain run prints the headline figure only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out `cpu_baseline`")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave out `roofline`")
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4, 5])
     # knobs of the gradient exchange for the first real multi-GPU sweeps (defaults = what the driver's runs use)
     ap.add_argument("--bucket-mb", type=float, default=64.0, help="size of the all-reduce buckets cut from the flat gradient buffer")
@@ -359,7 +365,7 @@ def main():
     # agrees with the steady-state rocprofv3 kernel trace (profiles/round2_kernel_stats_steady_cfg2.csv).
     roof = None
     phases = None
-    if not a.no_roofline and CONFIG in (2, 3):
+    if a.full and not a.no_roofline and CONFIG in (2, 3):
         # where the step's wall time goes: one more step as the timed ones run (no per-launch events), torch events on the
         # caller's stream between the phases (every phase ends with that stream joined to the side stream)
         step(timed_parts=True)
@@ -369,7 +375,7 @@ def main():
                       backward_ms=ph("loss_fwd_b", "adam_a"), adam_ms=ph("adam_a", "adam_b"),
                       note="forward = CNN + taps + encoder + heads; loss = log-softmax / NLL / accuracy pass; backward incl. its "
                            "dlogits pass and the join with the weight-gradient stream")
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         model.profile(True)
         step(timed_parts=True)
         torch.cuda.synchronize()
@@ -452,7 +458,7 @@ def main():
                                      rehearsal_on_one_gpu=rehearse)))
     if roof is not None:
         out["roofline"] = roof
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and CONFIG == 2:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and CONFIG == 2:
         out["cpu_baseline"] = cpu_baseline(1234)
     if rank == 0:
         print(json.dumps(out), flush=True)

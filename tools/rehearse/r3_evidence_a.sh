@@ -2,7 +2,7 @@
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_STAGE:-${GRAFT_REPO_ROOT:?}}"
 O=gpurun_out/r3ev; mkdir -p $O
-timeout -k 10 500 python bench.py > $O/round3_bench_cfg2.json 2> $O/bench_cfg2.err || tail -5 $O/bench_cfg2.err
+timeout -k 10 500 python bench.py --full > $O/round3_bench_cfg2.json 2> $O/bench_cfg2.err || tail -5 $O/bench_cfg2.err
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof2 -o cfg2 --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-roofline > $O/prof2.log 2>&1
 tr=$(find $O/prof2 -name "*kernel_trace.csv" | head -1)
 python tools/trace_timeline.py $tr $O/round3_timeline_cfg2.json 2

@@ -8,7 +8,7 @@ timeout -k 10 400 rocprofv3 --pmc WRITE_SIZE -d $O/w3 --output-format csv -- pyt
 python tools/pmc_traffic.py $O/f3 $O/w3 $O/round3_igemm_traffic_cfg3.json > /dev/null && rm -rf $O/f3 $O/w3
 mkdir -p profiles_tmp && cp $O/round3_igemm_traffic_cfg3.json profiles/ 2>/dev/null
 for c in 3 4 5; do
-  timeout -k 10 400 python bench.py --config $c --no-cpu-baseline > $O/round3_bench_cfg$c.json 2> $O/bench_cfg$c.err || tail -5 $O/bench_cfg$c.err
+  timeout -k 10 400 python bench.py --full --config $c --no-cpu-baseline > $O/round3_bench_cfg$c.json 2> $O/bench_cfg$c.err || tail -5 $O/bench_cfg$c.err
 done
 timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $O/prof3 -o cfg3 --output-format csv -- python3 bench.py --config 3 --steps 3 --warmup 1 --no-cpu-baseline --no-roofline > $O/prof3.log 2>&1
 tr=$(find $O/prof3 -name "*kernel_trace.csv" | head -1)
