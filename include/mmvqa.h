@@ -145,8 +145,16 @@ typedef struct mmvqa_gemm_desc {
                            per tile (and split).  The launcher falls back to that form when a condition is not met. */
   unsigned int* sk_cnt; /* persist: sk_cnt_n arrival tickets, ZERO before the first launch; every launch leaves them zero */
   int sk_cnt_n;
-  int reserved0;
+  int reserved0;        /* operand precision (the field keeps its name so that the struct layout is unchanged):
+                           MMVQA_PREC_F32 (0) = fp32 operands, v_mfma_f32_32x32x2_f32;
+                           MMVQA_PREC_F16 (1) = both operands rounded to fp16 (nearest-even, bit-equal to
+                           torch's .half()) where the loader writes them to LDS, v_mfma_f32_32x32x16_f16, fp32
+                           accumulation and epilogue.  The f16 family has no SiLU / gate prologues (refused),
+                           no 8-wave variant (tile 5 runs as tile 3) and no persistent form (launched per tile). */
 } mmvqa_gemm_desc;
+
+#define MMVQA_PREC_F32 0
+#define MMVQA_PREC_F16 1
 
 /* Fused attention (models/transformer.py:19-30 and models/realformer.py:30-45). */
 typedef struct mmvqa_attn_desc {
@@ -352,6 +360,13 @@ int mmvqa_bn_act_add_fold(mmvqa_stream_t s, const float* z, const mmvqa_bn_fold*
 /* torch.optim.Adam defaults over a flat buffer; g is scaled by gscale first and zeroed when zero_grad != 0 */
 int mmvqa_adam(mmvqa_stream_t s, float* p, float* g, float* m, float* v, long n, double lr, double b1, double b2,
                double eps, int step, float gscale, int zero_grad);
+/* loss scaling (torch.amp.GradScaler semantics): found_inf[0] = 1 if any of g[0..n) is inf / nan (left as it is
+ * otherwise); with multiply != 0 also g *= inv_scale[0] in place.  Device pointers. */
+int mmvqa_amp_unscale(mmvqa_stream_t s, float* g, long n, const float* inv_scale, float* found_inf, int multiply);
+/* one-thread update of torch._amp_update_scale_: found_inf -> scale *= backoff, tracker = 0; else tracker + 1 and, at
+ * growth_interval, scale *= growth (unless that overflows fp32), tracker = 0 */
+int mmvqa_amp_update_scale(mmvqa_stream_t s, float* scale, int* growth_tracker, const float* found_inf,
+                           double growth_factor, double backoff_factor, int growth_interval);
 int mmvqa_axpy(mmvqa_stream_t s, float* y, const float* x, float a, long n);
 int mmvqa_colsum(mmvqa_stream_t s, const float* x, int ld, int rows, int cols, float* out);
 int mmvqa_dropout(mmvqa_stream_t s, float* x, long n, float p, uint32_t seed);
@@ -401,6 +416,12 @@ int mmvqa_engine_set_grad_callback(mmvqa_engine* e, mmvqa_grad_cb cb, void* user
  * Returns the number of tuned shapes so far (>= 0) or a negative error.  enable = 2 changes nothing and returns how many
  * of the tuned shapes run in the persistent form (mmvqa_gemm_desc.persist). */
 int mmvqa_engine_tune(mmvqa_engine* e, int enable);
+/* operand precision of every implicit GEMM of the following forward / backward calls: MMVQA_PREC_F32 (default) or
+ * MMVQA_PREC_F16 (mixed precision: both operands of each contraction rounded to fp16 nearest-even, fp32 accumulation;
+ * everything else -- storage, BatchNorm / LayerNorm, softmax, attention's QK^T and PV, epilogues, losses -- stays fp32).
+ * The fused QKV + attention launch is replaced by the unfused route in f16 mode.  ResNet encoders only: an
+ * EfficientNet engine refuses MMVQA_PREC_F16 (MMVQA_ERR_ARG). */
+int mmvqa_engine_set_precision(mmvqa_engine* e, int mode);
 /* per-kernel-class timing (HIP events on the launch stream) of the NEXT forward+backward:
  * enable, run, then read back {n_launches, total_ms, algorithmic_flops} per class.
  * enable = 1: as the step normally runs (weight-gradient GEMMs on the second stream beside the data-gradient chain, so

@@ -9,6 +9,7 @@ from .model import Model, desc_from_args
 from .functional import mlm_loss, asl_loss, supcon_loss, split_feat
 from .optim import FusedAdam
 from . import synth
+from . import amp
 
 __all__ = ["Model", "desc_from_args", "mlm_loss", "asl_loss", "supcon_loss", "split_feat", "FusedAdam", "synth",
-           "MMVQAError"]
+           "MMVQAError", "amp"]

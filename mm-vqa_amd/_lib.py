@@ -19,6 +19,7 @@ ACT_NONE, ACT_RELU, ACT_GELU, ACT_SERF, ACT_SILU, ACT_SIGMOID = 0, 1, 2, 3, 4, 5
 KIND_FWD, KIND_DGRAD, KIND_WGRAD = 0, 1, 2
 PRO_NONE, PRO_AFFINE_RELU, PRO_DZ, PRO_AFFINE, PRO_AFFINE_SILU, PRO_SILU_GATE = 0, 1, 2, 3, 4, 5
 EPI_PLAIN, EPI_TAP_FWD, EPI_TAP_BWD = 0, 1, 2
+PREC_F32, PREC_F16 = 0, 1   # mmvqa_gemm_desc.reserved0 / mmvqa_engine_set_precision
 STAT_SLOTS = 16
 
 
@@ -180,6 +181,9 @@ SIGNATURES = {
     "mmvqa_engine_backward": (_i, [_P, _P, _P, _i, _P]),
     "mmvqa_engine_set_grad_callback": (_i, [_P, _P, _P]),
     "mmvqa_engine_tune": (_i, [_P, _i]),
+    "mmvqa_amp_unscale": (_i, [_P, _P, _l, _P, _P, _i]),
+    "mmvqa_amp_update_scale": (_i, [_P, _P, _P, _P, _d, _d, _i]),
+    "mmvqa_engine_set_precision": (_i, [_P, _i]),
     "mmvqa_engine_profile": (_i, [_P, _i]),
     "mmvqa_engine_profile_read": (_i, [_P, _i, C.POINTER(_ll), C.POINTER(_d), C.POINTER(_d)]),
     "mmvqa_engine_profile_read_region": (_i, [_P, _i, _i, C.POINTER(_ll), C.POINTER(_d), C.POINTER(_d)]),

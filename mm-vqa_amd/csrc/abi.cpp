@@ -226,6 +226,16 @@ int mmvqa_bn_act_add(mmvqa_stream_t s, const float* z, const float* sc, const fl
                      const float* ids, const float* idb, int idn_act, int post_act, float* out, long rows, int C) {
   return k_bn_act_add(ST(s), z, sc, sh, pre_act, idn, ids, idb, idn_act, post_act, out, rows, C);
 }
+int mmvqa_amp_unscale(mmvqa_stream_t s, float* g, long n, const float* inv_scale, float* found_inf, int multiply) {
+  if (!g || !found_inf || (multiply && !inv_scale)) return mmvqa_set_error(MMVQA_ERR_ARG, "amp_unscale: null pointer");
+  return k_amp_unscale(ST(s), g, n, inv_scale, found_inf, multiply ? 1 : 0);
+}
+int mmvqa_amp_update_scale(mmvqa_stream_t s, float* scale, int* growth_tracker, const float* found_inf,
+                           double growth_factor, double backoff_factor, int growth_interval) {
+  if (!scale || !growth_tracker || !found_inf) return mmvqa_set_error(MMVQA_ERR_ARG, "amp_update_scale: null pointer");
+  if (growth_interval <= 0) return mmvqa_set_error(MMVQA_ERR_ARG, "amp_update_scale: growth_interval=%d", growth_interval);
+  return k_amp_update_scale(ST(s), scale, growth_tracker, found_inf, growth_factor, backoff_factor, growth_interval);
+}
 int mmvqa_adam(mmvqa_stream_t s, float* p, float* g, float* m, float* v, long n, double lr, double b1, double b2,
                double eps, int step, float gscale, int zero_grad) {
   return k_adam(ST(s), p, g, m, v, n, lr, b1, b2, eps, step, gscale, zero_grad);
@@ -307,6 +317,16 @@ int mmvqa_engine_set_grad_callback(mmvqa_engine* e, mmvqa_grad_cb cb, void* user
   if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "set_grad_callback: null engine");
   e->grad_cb = cb;
   e->grad_cb_user = user;
+  return MMVQA_OK;
+}
+int mmvqa_engine_set_precision(mmvqa_engine* e, int mode) {
+  if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "set_precision: null engine");
+  if (mode != MMVQA_PREC_F32 && mode != MMVQA_PREC_F16)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "set_precision: mode %d (0 = fp32, 1 = fp16 operands)", mode);
+  if (mode == MMVQA_PREC_F16 && e->d.cnn != 0)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "set_precision: the fp16 operand mode covers the ResNet encoders only (EfficientNet's "
+                                          "squeeze-excite, depthwise and thin tap products run outside the implicit GEMM)");
+  e->prec = mode;
   return MMVQA_OK;
 }
 int mmvqa_engine_tune(mmvqa_engine* e, int enable) {

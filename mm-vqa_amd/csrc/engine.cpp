@@ -724,7 +724,8 @@ static int tap_fwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
   const TapRef& t = e->taps[k];
   static const bool thin_off = getenv("MMVQA_NO_TAP_THIN") != nullptr;   // A/B switch
   // (C = 64 with BatchNorm+ReLU on load needs 256 VGPRs there and only ties the GEMM kernel: measured, round 2)
-  if (!thin_off && t.C <= 32 && k_tap_thin_ok(t.M, e->d.hidden, t.C, t.HW)) {
+  // (fp32 operands: not in the f16 mode, whose contract rounds every tap product's operands -- the implicit GEMM below)
+  if (!thin_off && e->prec == MMVQA_PREC_F32 && t.C <= 32 && k_tap_thin_ok(t.M, e->d.hidden, t.C, t.HW)) {
     // few channels, huge map (EfficientNet's stem tap): weights stay in registers, no tile machinery (tapthin.hip)
     TRY(prof_begin(e, st, PROF_MATRIX, 2.0 * (double)t.M * e->d.hidden * t.C, HB_TAP_THIN_FWD, 4.0 * (double)t.M * t.C));
     TRY(k_tap_thin_fwd(st, fmap, bn_in ? WS(bn_in->scale) : nullptr, bn_in ? WS(bn_in->shift) : nullptr,
@@ -762,7 +763,7 @@ static int tap_bwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
   g.C = WS(e->du); g.c_ld = Hd;
   set_sk(e, st, g);
   static const bool thin_off = getenv("MMVQA_NO_TAP_THIN") != nullptr;
-  if (!thin_off && t.C <= 32 && k_tap_thin_ok(t.M, Hd, t.C, t.HW))   // EfficientNet stem tap: recompute in registers (tapthin.hip)
+  if (!thin_off && e->prec == MMVQA_PREC_F32 && t.C <= 32 && k_tap_thin_ok(t.M, Hd, t.C, t.HW))   // EfficientNet stem tap: recompute in registers (tapthin.hip)
   {
     TRY(prof_begin(e, st, PROF_MATRIX, 2.0 * (double)t.M * Hd * t.C, HB_TAP_THIN_BWD, 4.0 * (double)t.M * (t.C + Hd)));
     TRY(k_tap_thin_bwd(st, fmap, bn_in ? WS(bn_in->scale) : nullptr, bn_in ? WS(bn_in->shift) : nullptr,
@@ -1441,7 +1442,8 @@ static int bert_forward(mmvqa_engine* e, hipStream_t st, const float* x_in, cons
     BertLayerRef& L = e->bert[i];
     TRY(ln_fwd(e, st, x, e->norm1, WS(L.xn1), WS(L.mean1), WS(L.rstd1), M, 1e-12f));
     static const bool fused_off = getenv("MMVQA_NO_FUSED_QKV") != nullptr;   // A/B switch
-    if (!fused_off && k_qkv_attn_fwd_ok(e->T, H, d.heads)) {
+    // (its projection is an fp32 MFMA: in f16 mode the projection goes through the implicit GEMM, the unfused route)
+    if (!fused_off && e->prec == MMVQA_PREC_F32 && k_qkv_attn_fwd_ok(e->T, H, d.heads)) {
       // projection + attention of every (sample, head) in one launch (qkvattn.hip): a profiler region of its own (the
       // north-star block = QKV products + attention, whichever launches carry them: bench.py adds the three regions)
       REG(REG_QKV_ATTN);
@@ -1717,6 +1719,12 @@ static int prepare_workspace(mmvqa_engine* e, hipStream_t st) {
   return MMVQA_OK;
 }
 
+// every implicit GEMM launched inside a forward / backward takes the engine's operand precision
+struct PrecScope {
+  explicit PrecScope(int prec) { mmvqa_set_igemm_precision(prec); }
+  ~PrecScope() { mmvqa_set_igemm_precision(MMVQA_PREC_F32); }
+};
+
 int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long long* ids, const long long* seg,
                    const long long* mask, float* logits, int logits_ld, float* feat, int training, uint32_t seed) {
   if (!e->planned || !e->bound) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_forward: plan/bind first");
@@ -1727,7 +1735,10 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
   e->img = img; e->ids = ids; e->seg = seg; e->mask = mask;
   e->logits = logits; e->logits_ld = logits_ld; e->feat = feat;
   e->training = training; e->seed = seed;
+  if (e->prec != MMVQA_PREC_F32 && d.cnn != 0)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward: f16 operand mode covers the ResNet encoders only");
   struct TunerScope { TunerScope(IgemmTuner* t) { mmvqa_set_tuner(t); } ~TunerScope() { mmvqa_set_tuner(nullptr); } } ts(&e->tuner);
+  PrecScope ps(e->prec);
   e->ev_next = 0;
   if (d.cnn == 1) TRY(effnet_forward(e, st)); else TRY(resnet_forward(e, st));
   const float pe = training ? d.p_emb_drop : 0.f;
@@ -1747,7 +1758,10 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
 int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, const float* dfeat) {
   if (!e->planned || !e->bound || !e->img) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_backward: run forward first");
   const mmvqa_model_desc& d = e->d;
+  if (e->prec != MMVQA_PREC_F32 && d.cnn != 0)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward: f16 operand mode covers the ResNet encoders only");
   struct TunerScope { TunerScope(IgemmTuner* t) { mmvqa_set_tuner(t); } ~TunerScope() { mmvqa_set_tuner(nullptr); } } ts(&e->tuner);
+  PrecScope ps(e->prec);
   e->ev_next = 0;
   const float* h = WS(e->enc_out_final);
   SideCtx sc_enc(e, st);

@@ -168,6 +168,8 @@ struct mmvqa_engine {
   void (*grad_cb)(void* user, long long lo, long long hi) = nullptr;
   void* grad_cb_user = nullptr;
   long long enc_lo = 0, emb_hi = 0;
+  // ---- operand precision of the implicit GEMMs of the next forward / backward (MMVQA_PREC_*, mmvqa_engine_set_precision)
+  int prec = MMVQA_PREC_F32;
   // ---- profiling
   int prof_on = 0;
   int prof_reg = REG_BACKBONE;

@@ -24,6 +24,15 @@
 // Prologues (BatchNorm apply + ReLU, BatchNorm backward) run at that LDS write; the epilogue fuses
 // bias / activation / dropout / residual / ReLU-mask / per-channel statistics so that BatchNorm never
 // needs its own pass over a feature map.
+//
+// f16-operand family (PREC = MMVQA_PREC_F16, mixed-precision training): the loaders, tap tables, fold setup and
+// prologue math are the fp32 ones; each operand value is rounded to fp16 (nearest-even, v_cvt_f16_f32: bit-equal
+// to torch's .half(), never the round-toward-zero cvt_pkrtz) where it is written to LDS, so the LDS images hold
+// halves: [row][k] with rows of BK+8 halves read as ds_read_b128 (8 halves = one lane's fragment), [k][row] with
+// rows of R (+32) halves read with ds_read_b64_tr_b16.  Lane (r, h) feeds k = 16s + 8h + j in element j of K-step
+// s for both operands; the MFMA is v_mfma_f32_32x32x16_f16 with fp32 accumulation, whose C/D layout is that of
+// the fp32 form, so the epilogues, split-K and the ticketed fix-up are shared.  The K loop is the plain one with
+// two register stages (loads of tile t+2 in flight while tile t is multiplied); no 8-wave or persistent form.
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -62,6 +71,20 @@ __device__ __forceinline__ int fdiv(int n, const FastDiv& f) {
 }
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
+
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+// LDS geometry of the operand tiles, in floats per buffer.  fp32: [row][k] rows of BK+4 floats, [k][row] rows of
+// R+4 floats.  f16: [row][k] rows of BK+8 halves (16-byte rows for ds_read_b128); [k][row] rows of R halves, +32
+// when R/2 is a multiple of 32 dwords, so that the four k-rows of one ds_read_b64_tr_b16 block fall on distinct
+// banks (row pitch = 16 or 48 dwords mod 64).
+__host__ __device__ constexpr int km_ld_h(int R) { return R + (((R / 2) % 64 == 16 || (R / 2) % 64 == 48) ? 0 : 32); }
+template <int PREC>
+__host__ __device__ constexpr int tile_rowk(int R, int BK) { return PREC == MMVQA_PREC_F16 ? R * (BK + 8) / 2 : R * (BK + 4); }
+template <int PREC>
+__host__ __device__ constexpr int tile_km(int R, int BK) { return PREC == MMVQA_PREC_F16 ? BK * km_ld_h(R) / 2 : BK * (R + 4); }
 
 // compile-time loops: the accumulator tiles must only ever be indexed with constants, otherwise the
 // compiler demotes them to scratch memory and re-stores them every K-tile
@@ -306,20 +329,22 @@ __device__ __forceinline__ void general_epilogue(const GemmParams& p, int m0, in
 // PERSIST: the persistent ("stream-K") form is its own instantiation -- the segment loop around the body invites the
 // compiler to hoist everything loop-invariant out of it and keep it in registers for the whole kernel (measured: 156 ->
 // 256 VGPRs with spills for the 64x64x32 forward tile); the one-workgroup-per-tile form must not pay for that.
-template <int BM, int BN, int BK, int KIND, bool NCHW, int KS, bool PERSIST = false>
+template <int BM, int BN, int BK, int KIND, bool NCHW, int KS, bool PERSIST = false, int PREC = MMVQA_PREC_F32>
 __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, const GemmAux x) {
   constexpr int NT = 256 * KS;
   constexpr int WM = BM / 2, WN = BN / 2, TM = WM / 32, TN = WN / 32;
+  constexpr bool F16 = (PREC == MMVQA_PREC_F16);   // f16-operand family: halves in LDS, 32x32x16 MFMA
+  static_assert(!F16 || (KS == 1 && !PERSIST), "the f16 family has no 8-wave or persistent form");
   constexpr bool PIPE = TM * TN <= 2;         // slot-pipelined K loop (one or two 32x32 tiles per wave); else the plain loop
-  constexpr int LDK = BK + 4;
+  constexpr int LDK = F16 ? BK + 8 : BK + 4;  // (f16: in halves, as LDA_KM / LDB_KM)
   constexpr int KQ = BK / 4;                 // float4 per row of a [row][k] tile
   constexpr int RSTEP = NT / KQ;             // rows covered by one pass of the NT threads
   constexpr int NA = BM / RSTEP, NB = BN / RSTEP;  // float4 chunks per thread per K-tile ([row][k] form)
   constexpr bool A_ROWK = (KIND != KIND_WGRAD);
   constexpr bool B_ROWK = (KIND == KIND_FWD);
-  constexpr int LDA_KM = BM + 4, LDB_KM = BN + 4;
-  constexpr int A_TILE = A_ROWK ? BM * LDK : BK * LDA_KM;
-  constexpr int B_TILE = B_ROWK ? BN * LDK : BK * LDB_KM;
+  constexpr int LDA_KM = F16 ? km_ld_h(BM) : BM + 4, LDB_KM = F16 ? km_ld_h(BN) : BN + 4;
+  constexpr int A_TILE = A_ROWK ? tile_rowk<PREC>(BM, BK) : tile_km<PREC>(BM, BK);   // floats per buffer
+  constexpr int B_TILE = B_ROWK ? tile_rowk<PREC>(BN, BK) : tile_km<PREC>(BN, BK);
   // [k][row] form: BK k-rows x (R/4) float4
   constexpr int A_X4 = BM / 4, A_KSTEP = NT / A_X4, NA_KM = BK / A_KSTEP;
   constexpr int B_X4 = BN / 4, B_KSTEP = NT / B_X4, NB_KM = BK / B_KSTEP;
@@ -587,6 +612,13 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
   // branch-free advance of (channel, tap) by one K-tile
   const int adv_tap = BK / p.g_Cs, adv_c = BK - adv_tap * p.g_Cs;
 
+  // four consecutive operand values -> LDS at element offset e of a tile (fp32: floats; f16 family: halves,
+  // rounded to nearest-even here and nowhere else)
+  auto lds_put = [&](float* tile, int e, f32x4 v) __attribute__((always_inline)) {
+    if constexpr (F16) *reinterpret_cast<f16x4*>(reinterpret_cast<_Float16*>(tile) + e) = __builtin_convertvector(v, f16x4);
+    else *reinterpret_cast<f32x4*>(&tile[e]) = v;
+  };
+
   // The whole K loop is instantiated per prologue mode so that its body is straight-line code
   // (loads -> MFMAs -> LDS writes in ONE basic block): the compiler can then slot the address
   // arithmetic and the prologue math between the 64-cycle MFMAs instead of running them serially.
@@ -749,9 +781,9 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
           for (int j = 0; j < 4; ++j) v[j] = (ok && (e0 + j < lim)) ? v[j] : 0.f;
         }
         if constexpr (A_ROWK) {
-          *reinterpret_cast<f32x4*>(&as[(a_r0 + RSTEP * r) * LDK + a_kq]) = v;
+          lds_put(as, (a_r0 + RSTEP * r) * LDK + a_kq, v);
         } else {
-          *reinterpret_cast<f32x4*>(&as[(akm_k0 + A_KSTEP * r) * LDA_KM + akm_x4 * 4]) = v;
+          lds_put(as, (akm_k0 + A_KSTEP * r) * LDA_KM + akm_x4 * 4, v);
         }
       } else {
         const int r = c - NAC;
@@ -770,9 +802,9 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = ok ? v[j] : 0.f;
         if constexpr (B_ROWK) {
-          *reinterpret_cast<f32x4*>(&bs[(b_r0 + RSTEP * r) * LDK + b_kq]) = v;
+          lds_put(bs, (b_r0 + RSTEP * r) * LDK + b_kq, v);
         } else {
-          *reinterpret_cast<f32x4*>(&bs[(bkm_k0 + B_KSTEP * r) * LDB_KM + bkm_x4 * 4]) = v;
+          lds_put(bs, (bkm_k0 + B_KSTEP * r) * LDB_KM + bkm_x4 * 4, v);
         }
       }
     };
@@ -970,9 +1002,9 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
           }
         }
         if constexpr (A_ROWK) {
-          *reinterpret_cast<f32x4*>(&as[(a_r0 + RSTEP * r) * LDK + a_kq]) = v;
+          lds_put(as, (a_r0 + RSTEP * r) * LDK + a_kq, v);
         } else {
-          *reinterpret_cast<f32x4*>(&as[(akm_k0 + A_KSTEP * r) * LDA_KM + akm_x4 * 4]) = v;
+          lds_put(as, (akm_k0 + A_KSTEP * r) * LDA_KM + akm_x4 * 4, v);
         }
       } else {
         const int r = c - NAC;
@@ -988,9 +1020,9 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
           }
         }
         if constexpr (B_ROWK) {
-          *reinterpret_cast<f32x4*>(&bs[(b_r0 + RSTEP * r) * LDK + b_kq]) = v;
+          lds_put(bs, (b_r0 + RSTEP * r) * LDK + b_kq, v);
         } else {
-          *reinterpret_cast<f32x4*>(&bs[(bkm_k0 + B_KSTEP * r) * LDB_KM + bkm_x4 * 4]) = v;
+          lds_put(bs, (bkm_k0 + B_KSTEP * r) * LDB_KM + bkm_x4 * 4, v);
         }
       }
     };
@@ -1044,7 +1076,7 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
       if constexpr (PIPE) LT(S1, kt_begin + 1);
 #pragma unroll
       for (int c = 0; c < NC; ++c) SC(S0, 0, kt_begin, c);
-      if constexpr (FAST != 0 && PIPE) f_halo(S0);   // S0 receives tile kt_begin + 2 next
+      if constexpr (FAST != 0 && PIPE && !F16) f_halo(S0);   // S0 receives tile kt_begin + 2 next
     }
     // No load may be pending across the loop entry: the wait-count pass merges the entry and the back-edge
     // states, and a load still in flight here turns into a vmcnt(0) at the loop head of EVERY iteration.
@@ -1052,7 +1084,57 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
     __syncthreads();
     TRACE_MARK(2);
 
-    if constexpr (PIPE) {
+    if constexpr (F16) {
+      // f16 family: per K-tile BK/16 K-steps of TM x TN 32x32x16 MFMAs.  Small wave tiles (PIPE): two register stages
+      // in strict load order (S0: tiles 0, 2, 4, ..., S1: 1, 3, ...), the loads of tile t+2 are issued before tile t is
+      // multiplied and the stage loaded one iteration earlier (tile t+1) is written to the other LDS buffer after it.
+      // Large wave tiles: one stage (tile t+1), as the fp32 plain loop -- a second one would not fit in registers.
+      // A fragment: [row][k] image -> one ds_read_b128 at (row, 16s + 8h); [k][row] image -> two ds_read_b64_tr_b16,
+      // lane 4q+p of each 16-lane group addressing k-row 16s + 8h + 4rd + q, columns 16*((lane>>4)&1) + 4p .. +3, and
+      // receiving column lane&31 of those four k-rows (all 64 lanes active: the reads sit in uniform code).
+      auto frag = [&](const float* tile, int rowk, int ldkm, int r0, int st) __attribute__((always_inline)) {
+        const _Float16* t = reinterpret_cast<const _Float16*>(tile);
+        if (rowk) return *reinterpret_cast<const f16x8*>(t + (r0 + li) * LDK + st * 16 + lh * 8);
+        const int g = lane >> 4, q = (lane >> 2) & 3, pp = lane & 3;
+        const _Float16* b = t + (st * 16 + (g >> 1) * 8 + q) * ldkm + r0 + (g & 1) * 16 + 4 * pp;
+        typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+        const f16x4 lo = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(b)));
+        const f16x4 hi = __builtin_bit_cast(f16x4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(b + 4 * ldkm)));
+        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+      };
+      auto body16 = [&](int t, Stage& Sload, Stage& Sstore) __attribute__((always_inline)) {
+        const int buf = t & 1;
+        LT(Sload, kt_begin + t + (PIPE ? 2 : 1));   // past the end everything is masked
+        const float* as = As + buf * A_TILE;
+        const float* bs = Bs + buf * B_TILE;
+#pragma unroll
+        for (int st = 0; st < BK / 16; ++st) {
+          f16x8 fa[TM], fb[TN];
+#pragma unroll
+          for (int i = 0; i < TM; ++i) fa[i] = frag(as, A_ROWK, LDA_KM, wm0 + i * 32, st);
+#pragma unroll
+          for (int i = 0; i < TN; ++i) fb[i] = frag(bs, B_ROWK, LDB_KM, wn0 + i * 32, st);
+#pragma unroll
+          for (int a = 0; a < TM; ++a)
+#pragma unroll
+            for (int b = 0; b < TN; ++b)
+              acc[a][b] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[a], fb[b], acc[a][b], 0, 0, 0);
+        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) SC(Sstore, buf ^ 1, kt_begin + t + 1, c);
+        __syncthreads();
+      };
+      if constexpr (PIPE) {
+        int t = 0;
+        for (; t + 1 < nkt; t += 2) {
+          body16(t, S0, S1);
+          body16(t + 1, S1, S0);
+        }
+        if (t < nkt) body16(t, S0, S1);
+      } else {
+        for (int t = 0; t < nkt; ++t) body16(t, S0, S0);
+      }
+    } else if constexpr (PIPE) {
       // Software pipeline of the small tiles, one fenced slot per MFMA.  A wave's MFMAs form a dependent
       // chain (one 32x32 accumulator), so the next one issues 64 cycles after its predecessor and ~15 VALU
       // instructions fit in that shadow for free; anything clustered beyond that idles the matrix pipe.
@@ -1213,8 +1295,9 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
     using I0 = std::integral_constant<int, PRO_NONE>;
     using I1 = std::integral_constant<int, PRO_AFFINE_RELU>;
     using I2 = std::integral_constant<int, PRO_DZ>;
-    using I4 = std::integral_constant<int, PRO_AFFINE_SILU>;
-    using I5 = std::integral_constant<int, PRO_SILU_GATE>;
+    // (the f16 family has no SiLU / gate prologues -- the host refuses them -- so they instantiate nothing new there)
+    using I4 = std::integral_constant<int, F16 ? PRO_NONE : PRO_AFFINE_SILU>;
+    using I5 = std::integral_constant<int, F16 ? PRO_NONE : PRO_SILU_GATE>;
     using G = std::integral_constant<int, 0>;    // general loaders
     using F1 = std::integral_constant<int, 1>;   // uniform-tap loaders
     using F2 = std::integral_constant<int, 2>;   // uniform-tap loaders + halo mask
@@ -1549,12 +1632,12 @@ static FastDiv make_fastdiv(int d) {
   return f;
 }
 
-template <int BM, int BN, int BK, int KIND, bool NCHW, int KS = 1>
+template <int BM, int BN, int BK, int KIND, bool NCHW, int KS = 1, int PREC = MMVQA_PREC_F32>
 static int launch_cfg(GemmParams p, hipStream_t stream) {
   constexpr bool A_ROWK = (KIND != KIND_WGRAD);
   constexpr bool B_ROWK = (KIND == KIND_FWD);
-  constexpr int A_TILE = A_ROWK ? BM * (BK + 4) : BK * (BM + 4);
-  constexpr int B_TILE = B_ROWK ? BN * (BK + 4) : BK * (BN + 4);
+  constexpr int A_TILE = A_ROWK ? tile_rowk<PREC>(BM, BK) : tile_km<PREC>(BM, BK);
+  constexpr int B_TILE = B_ROWK ? tile_rowk<PREC>(BN, BK) : tile_km<PREC>(BN, BK);
   constexpr size_t tile_floats = (size_t)(2 * A_TILE + 2 * B_TILE + MAX_TAPS);
   constexpr size_t epi_floats = (size_t)BM * (BN + 4) + 8 * BN;   // staged output tile + tap accumulators
   constexpr size_t smem_max = (tile_floats + FOLD_MAX_FLOATS > epi_floats ? tile_floats + FOLD_MAX_FLOATS : epi_floats) * sizeof(float);
@@ -1563,7 +1646,7 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (!(attr_dev_mask >> (dev & 31) & 1)) {
-    HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<BM, BN, BK, KIND, NCHW, KS>,
+    HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<BM, BN, BK, KIND, NCHW, KS, false, PREC>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max));
     attr_dev_mask |= 1 << (dev & 31);
   }
@@ -1639,7 +1722,7 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
       x.tick = 1; x.part = nullptr; x.sk_slots = p.splitk; x.sk_part = p.sk_ws; x.sk_cnt = p.sk_cnt;
     }
   }
-  if (p.persist > 0 && !NCHW && BM == 64 && BN == 64 && p.epi_mode == EPI_PLAIN && !x.part && p.splitk == 1) {
+  if (p.persist > 0 && PREC == MMVQA_PREC_F32 && !NCHW && BM == 64 && BN == 64 && p.epi_mode == EPI_PLAIN && !x.part && p.splitk == 1) {
     const long long tiles = (long long)grid.x * grid.y, nkt = (p.K + BK - 1) / BK, T = tiles * nkt;
     long long G = p.persist < T ? p.persist : T;
     bool ok = G >= 8;
@@ -1665,9 +1748,10 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
     if (x.sk_G && !x.xcd) x.xcd = 1;
   }
   if (getenv("MMVQA_IGEMM_LOG"))   // one line per launch: which loader family a shape gets (diagnostics)
-    fprintf(stderr, "igemm kind %d fast %d tile %dx%dx%d ks %d M %d N %d K %d Cs %d taps %d stride %d apro %d bpro %d splitk %d persist %d fold %d tick %d\n", KIND, x.fast,
-            BM, BN, BK, KS, p.M, p.N, p.K, p.g_Cs, p.g_KH * p.g_KW, p.g_stride, p.a_pro, p.b_pro, p.splitk, x.sk_G, x.ldsc, x.tick);
-  if constexpr (BM == 64 && BN == 64 && !NCHW) {
+    fprintf(stderr, "igemm kind %d fast %d tile %dx%dx%d ks %d M %d N %d K %d Cs %d taps %d stride %d apro %d bpro %d splitk %d persist %d fold %d tick %d prec %s\n", KIND, x.fast,
+            BM, BN, BK, KS, p.M, p.N, p.K, p.g_Cs, p.g_KH * p.g_KW, p.g_stride, p.a_pro, p.b_pro, p.splitk, x.sk_G, x.ldsc, x.tick,
+            PREC == MMVQA_PREC_F16 ? "f16" : "f32");
+  if constexpr (BM == 64 && BN == 64 && !NCHW && PREC == MMVQA_PREC_F32) {
     if (x.sk_G) {
       static int attr_dev_mask_p = 0;
       if (!(attr_dev_mask_p >> (dev & 31) & 1)) {
@@ -1680,7 +1764,7 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
       return MMVQA_OK;
     }
   }
-  hipLaunchKernelGGL((igemm_kernel<BM, BN, BK, KIND, NCHW, KS>), grid, dim3(256 * KS), smem, stream, p, x);
+  hipLaunchKernelGGL((igemm_kernel<BM, BN, BK, KIND, NCHW, KS, false, PREC>), grid, dim3(256 * KS), smem, stream, p, x);
   KERNEL_CHECK_RET();
   if (x.part) {
     hipLaunchKernelGGL(splitk_finish_kernel, dim3((p.N + 63) / 64, (p.M + 63) / 64), dim3(256), 0, stream, p, x.part,
@@ -1706,10 +1790,12 @@ static bool sk_eligible(const GemmParams& p, int kind) {
 // side restores the BatchNorm buffers and zeroes the gradients afterwards).
 static thread_local IgemmTuner* g_tuner = nullptr;
 void mmvqa_set_tuner(IgemmTuner* t) { g_tuner = t; }
+static thread_local int g_prec = MMVQA_PREC_F32;
+void mmvqa_set_igemm_precision(int prec) { g_prec = prec; }
 
 static std::string tune_key(const GemmParams& p, int kind, int nchw) {
-  char buf[160];
-  snprintf(buf, sizeof(buf), "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", kind, nchw, p.M, p.N, p.K,
+  char buf[176];
+  snprintf(buf, sizeof(buf), "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", p.reserved0, kind, nchw, p.M, p.N, p.K,
            p.g_KH * p.g_KW, p.g_stride, p.g_Cs, p.a_pro, p.b_pro, p.epi_mode, p.act | (p.dact << 4),
            (p.stat1 ? 1 : 0) | (p.stat2 ? 2 : 0) | (p.Mk ? 4 : 0) | (p.R ? 8 : 0) | (p.Cpre ? 16 : 0) |
                (p.colsum ? 32 : 0) | (p.bias ? 64 : 0) | (p.sk_ws ? 128 : 0) | (p.a_fold.stat ? 256 : 0) | (p.sk_cnt ? 512 : 0),
@@ -1726,6 +1812,10 @@ static int launch_one(GemmParams p, int kind, int nchw, int tile, hipStream_t st
 static int validate_desc(const GemmParams& p, int kind, int nchw) {
 #define BAD(...) return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: " __VA_ARGS__)
   if (kind < KIND_FWD || kind > KIND_WGRAD) BAD("unknown kind %d", kind);
+  if (p.reserved0 != MMVQA_PREC_F32 && p.reserved0 != MMVQA_PREC_F16) BAD("unknown operand precision %d (reserved0)", p.reserved0);
+  if (p.reserved0 == MMVQA_PREC_F16 && (p.a_pro == PRO_AFFINE_SILU || p.a_pro == PRO_SILU_GATE || p.b_pro == PRO_AFFINE_SILU ||
+                                        p.b_pro == PRO_SILU_GATE || p.gate))
+    BAD("the f16 operand family has no SiLU / gate prologues (a_pro %d, b_pro %d)", p.a_pro, p.b_pro);
   if (!p.A || !p.B) BAD("operand pointer is null (A=%p B=%p)", (const void*)p.A, (const void*)p.B);
   if (!p.C && p.epi_mode != EPI_TAP_FWD) BAD("output pointer is null");
   const int KH = p.g_KH > 0 ? p.g_KH : 1, KW = p.g_KH > 0 ? p.g_KW : 1;
@@ -1771,6 +1861,7 @@ static int validate_desc(const GemmParams& p, int kind, int nchw) {
 
 int mmvqa_launch_igemm(GemmParams p, int kind, int nchw, int tile, hipStream_t stream) {
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return MMVQA_OK;
+  if (p.reserved0 == MMVQA_PREC_F32) p.reserved0 = g_prec;
   if (int r = validate_desc(p, kind, nchw)) return r;
   if (tile != 0 || nchw || !g_tuner) return launch_one(p, kind, nchw, tile, stream);
   const std::string key = tune_key(p, kind, nchw);
@@ -1864,6 +1955,11 @@ static int launch_one(GemmParams p, int kind, int nchw, int tile, hipStream_t st
     if (tile == 3 && kind != KIND_WGRAD && (long)cdiv(p.M, 64) * cdiv(p.N, 64) < 400 && p.K >= 512) tile = 5;
   }
   if (nchw) tile = (kind == KIND_FWD) ? 2 : 3;
+  const bool f16 = p.reserved0 == MMVQA_PREC_F16;
+  if (f16) {   // the f16 family has no 8-wave variant and no persistent form
+    if (tile == 5) tile = 3;
+    p.persist = 0;
+  }
   const int bm = (tile == 1 || tile == 2) ? 128 : 64;
   const int bn = (tile == 1 || tile == 4) ? 128 : 64;
   const int bk = ((tile == 3 || tile == 5) && !nchw) ? 64 : 32;
@@ -1905,12 +2001,22 @@ static int launch_one(GemmParams p, int kind, int nchw, int tile, hipStream_t st
   p.splitk = cdiv(nkt, p.ktiles_per_split);
   if (p.splitk > 1 && !p.c_atomic && !(kind != KIND_WGRAD && !nchw && sk_eligible(p, kind)))
     return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: split-K needs an accumulating epilogue");
-#define GO(BM_, BN_, BK_)                                                                   \
-  do {                                                                                      \
-    if (kind == KIND_FWD) return launch_cfg<BM_, BN_, BK_, KIND_FWD, false>(p, stream);     \
-    if (kind == KIND_DGRAD) return launch_cfg<BM_, BN_, BK_, KIND_DGRAD, false>(p, stream); \
-    return launch_cfg<BM_, BN_, BK_, KIND_WGRAD, false>(p, stream);                         \
+#define GO(BM_, BN_, BK_)                                                                                          \
+  do {                                                                                                             \
+    if (f16) {                                                                                                     \
+      if (kind == KIND_FWD) return launch_cfg<BM_, BN_, BK_, KIND_FWD, false, 1, MMVQA_PREC_F16>(p, stream);     \
+      if (kind == KIND_DGRAD) return launch_cfg<BM_, BN_, BK_, KIND_DGRAD, false, 1, MMVQA_PREC_F16>(p, stream); \
+      return launch_cfg<BM_, BN_, BK_, KIND_WGRAD, false, 1, MMVQA_PREC_F16>(p, stream);                         \
+    }                                                                                                              \
+    if (kind == KIND_FWD) return launch_cfg<BM_, BN_, BK_, KIND_FWD, false>(p, stream);                            \
+    if (kind == KIND_DGRAD) return launch_cfg<BM_, BN_, BK_, KIND_DGRAD, false>(p, stream);                        \
+    return launch_cfg<BM_, BN_, BK_, KIND_WGRAD, false>(p, stream);                                                \
   } while (0)
+  if (nchw && f16) {
+    if (kind == KIND_FWD) return launch_cfg<128, 64, 32, KIND_FWD, true, 1, MMVQA_PREC_F16>(p, stream);
+    if (kind == KIND_WGRAD) return launch_cfg<64, 64, 32, KIND_WGRAD, true, 1, MMVQA_PREC_F16>(p, stream);
+    return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: no NCHW dgrad");
+  }
   if (nchw) {
     if (kind == KIND_FWD) return launch_cfg<128, 64, 32, KIND_FWD, true>(p, stream);
     if (kind == KIND_WGRAD) return launch_cfg<64, 64, 32, KIND_WGRAD, true>(p, stream);

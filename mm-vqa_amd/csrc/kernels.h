@@ -13,6 +13,9 @@ struct IgemmTuner {
   std::unordered_map<std::string, IgemmChoice> table;
 };
 void mmvqa_set_tuner(IgemmTuner* t);
+// operand precision the engine gives every implicit-GEMM launch of the calling thread (MMVQA_PREC_*): a launch whose
+// descriptor says MMVQA_PREC_F32 takes this one (set around a forward / backward, like the tuner)
+void mmvqa_set_igemm_precision(int prec);
 int mmvqa_launch_igemm(GemmParams p, int kind, int nchw, int tile, hipStream_t stream);
 int mmvqa_launch_attention(const AttnParams& p, int head_dim, int bwd, hipStream_t st);
 // qkvattn.hip: fused QKV projection + self-attention of a BertLayer (forward), T <= 32, head dimension 64
@@ -70,6 +73,10 @@ int k_supcon(hipStream_t st, const float* f, float* loss, float* df, float* ws, 
 int k_adam(hipStream_t st, float* p, float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps,
            int step, float gscale, int zero_grad);
 int k_axpy(hipStream_t st, float* y, const float* x, float a, long n);
+// amp.hip: loss scaling (non-finite check + optional unscale of a gradient buffer; scale / growth-tracker update)
+int k_amp_unscale(hipStream_t st, float* g, long n, const float* inv_scale, float* found_inf, int mul);
+int k_amp_update_scale(hipStream_t st, float* scale, int* growth_tracker, const float* found_inf, double growth_factor,
+                       double backoff_factor, int growth_interval);
 int k_colsum(hipStream_t st, const float* x, int ld, int rows, int cols, float* out);
 int k_dropout(hipStream_t st, float* x, long n, float p, uint32_t seed);
 int k_pixmask(hipStream_t st, int* out, int N, int OH, int OW, int SH, int SW, int KH, int KW, int stride, int pad);

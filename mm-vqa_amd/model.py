@@ -99,14 +99,31 @@ class _HeadSeq(_Node):
 
 class _ModelFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, anchor, img, ids, seg, mask):
+    def forward(ctx, model, anchor, img, ids, seg, mask, prec):
         ctx.model = model
-        return model._engine_forward(img, ids, seg, mask)
+        ctx.prec = prec
+        return model._engine_forward(img, ids, seg, mask, prec)
 
     @staticmethod
     def backward(ctx, *grads):
-        ctx.model._engine_backward(*grads)
-        return (None,) * 6
+        ctx.model._engine_backward(*grads, prec=ctx.prec)
+        return (None,) * 7
+
+
+def autocast_precision(model_desc) -> int:
+    """Operand precision of a forward run now: PREC_F16 inside torch.autocast("cuda", dtype=torch.float16) (what the
+    reference's torch.cuda.amp.autocast() means), PREC_F32 outside autocast.  Any other autocast dtype, and an
+    EfficientNet encoder under fp16 autocast, raise NotImplementedError instead of running silently in fp32."""
+    if not torch.is_autocast_enabled("cuda"):
+        return L.PREC_F32
+    dt = torch.get_autocast_dtype("cuda")
+    if dt != torch.float16:
+        raise NotImplementedError(f"mixed precision supports torch.autocast('cuda', dtype=torch.float16) only, not {dt}")
+    if model_desc.cnn != 0:
+        raise NotImplementedError("mixed precision (fp16 autocast) supports the ResNet encoders only, not "
+                                  "tf_efficientnetv2_m: its squeeze-excite, depthwise and thin tap products run "
+                                  "outside the implicit GEMM")
+    return L.PREC_F16
 
 
 class Model(nn.Module):
@@ -309,7 +326,7 @@ class Model(nn.Module):
         """dropout stream for training-mode forwards (counter-based RNG in the kernels)"""
         self._seed_ctr = int(seed) & 0x7FFFFFFF
 
-    def _engine_forward(self, img, ids, seg, mask):
+    def _engine_forward(self, img, ids, seg, mask, prec=0):
         if not img.is_cuda:
             raise L.MMVQAError("mm-vqa_amd runs on the GPU only: move the model and inputs to 'cuda' "
                                "(there is no CPU fallback by design)")
@@ -327,6 +344,7 @@ class Model(nn.Module):
             buf[:, V:].zero_()
         feat = torch.empty(B, d.feat_dim, dtype=torch.float32, device=img.device) if d.supcon else None
         self._seed_ctr = (self._seed_ctr * 1103515245 + 12345) & 0x7FFFFFFF
+        L.check(L.lib().mmvqa_engine_set_precision(self._handle, int(prec)))
         L.check(L.lib().mmvqa_engine_forward(self._handle, L.stream_ptr(), L.ptr(img), L.ptr(ids), L.ptr(seg),
                                              L.ptr(mask), L.ptr(buf), ld, L.ptr(feat), 1 if self.training else 0,
                                              self._seed_ctr))
@@ -335,7 +353,7 @@ class Model(nn.Module):
         logits = logits.view(B, T, V) if d.head_kind == 0 else logits
         return (logits, feat) if d.supcon else logits
 
-    def _engine_backward(self, dlogits, dfeat=None):
+    def _engine_backward(self, dlogits, dfeat=None, prec=0):
         img, ids, seg, mask, rows, V, ld = self._fwd_state
         first = next(p for n, p in self._params_by_name.items() if not n.startswith(_NEVER_USED))
         if first.grad is None:           # optimizer.zero_grad(set_to_none=True) semantics
@@ -348,6 +366,7 @@ class Model(nn.Module):
         gld = g.stride(0)
         if dfeat is not None:
             dfeat = dfeat.contiguous()
+        L.check(L.lib().mmvqa_engine_set_precision(self._handle, int(prec)))   # the mode of this backward's forward
         L.check(L.lib().mmvqa_engine_backward(self._handle, L.stream_ptr(), L.ptr(g), gld, L.ptr(dfeat)))
         if getattr(self, "_cb_error", None) is not None:
             err, self._cb_error = self._cb_error, None
@@ -355,7 +374,18 @@ class Model(nn.Module):
         self.attach_grads()
 
     def forward(self, img, input_ids, segment_ids, input_mask):
-        out = _ModelFn.apply(self, self._anchor, img, input_ids, segment_ids, input_mask)
+        """Inside torch.autocast("cuda", dtype=torch.float16) the forward and its backward run in the mixed-precision
+        mode: both operands of every contraction of the implicit GEMM (every ResNet convolution with the stem,
+        the downsample branches and the five tap 1x1 convolutions; every nn.Linear of the encoder and the heads;
+        forward, data gradient and weight gradient) are rounded to fp16 nearest-even (bit-equal to .half()) and
+        accumulated in fp32.  Everything else stays fp32: activations, gradients and parameters in storage,
+        BatchNorm statistics, epilogues, LayerNorm, softmax, attention's QK^T and PV products, embeddings, losses
+        and the returned logits.  This rounds strictly less than torch's autocast, which also rounds each
+        conv / linear output to fp16 and runs BatchNorm and elementwise ops on fp16 tensors: results are close
+        to, not bit-equal to, the reference under autocast.  Other autocast dtypes (bf16) and EfficientNet
+        under fp16 autocast raise NotImplementedError.  Outside autocast everything is fp32 as before."""
+        prec = autocast_precision(self._desc)
+        out = _ModelFn.apply(self, self._anchor, img, input_ids, segment_ids, input_mask, prec)
         if self.dataset == "VQA-Med":
             return out, 0, 0   # models/mmbert.py:167
         return out
@@ -405,11 +435,12 @@ class Model(nn.Module):
         cb = getattr(self, "_cb", None)
         if cb is not None:   # the throw-away pass must not trigger gradient all-reduces
             L.check(lib.mmvqa_engine_set_grad_callback(self._handle, None, None))
+        prec = autocast_precision(self._desc)   # under fp16 autocast the f16-operand shapes are tuned
         try:
-            out = self._engine_forward(img, input_ids, segment_ids, input_mask)
+            out = self._engine_forward(img, input_ids, segment_ids, input_mask, prec)
             logits = out[0] if isinstance(out, tuple) else out
             feat = out[1] if isinstance(out, tuple) else None
-            self._engine_backward(torch.zeros_like(logits), None if feat is None else torch.zeros_like(feat))
+            self._engine_backward(torch.zeros_like(logits), None if feat is None else torch.zeros_like(feat), prec=prec)
             torch.cuda.synchronize()
         finally:
             n = lib.mmvqa_engine_tune(self._handle, 0)

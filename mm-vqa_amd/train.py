@@ -36,6 +36,7 @@ from torch.optim import lr_scheduler
 
 from . import FusedAdam, Model, asl_loss, checkpoint, evaluate, mlm_loss, split_feat, supcon_loss, synth
 from . import data as D
+from .amp import GradScaler
 from .ddp import GradReducer, comm_info, global_supcon_views, sync_replicas
 
 
@@ -72,6 +73,13 @@ def common_args(p):
     p.add_argument("--resnet_width", type=int, default=64)
     p.add_argument("--emb_vocab", type=int, default=30522)
     p.add_argument("--bucket_mb", type=float, default=64.0, help="all-reduce bucket size (data parallel)")
+    p.add_argument("--mixed_precision", action="store_true", default=False,
+                   help="fp16 autocast + loss scaling (mmvqa_amd.amp.GradScaler): every conv / linear contraction of the "
+                        "ResNet encoders, the transformer and the heads rounds both operands to fp16 (fp32 accumulation, "
+                        "everything else fp32).  vqa reproduces the reference's loop (utils.py:651-657): scaler.scale(loss) is "
+                        "computed and discarded, the backward is unscaled, --clip acts on those gradients and scaler.step "
+                        "then divides them by the scale.  supcon: accepted, runs fp32 (the reference's SupCon loop has no "
+                        "autocast).  Not with --overlap_adam")
     p.add_argument("--overlap_adam", action="store_true", help="Adam per finished gradient range beside the backward pass (measured time-neutral; not with --clip)")
     p.add_argument("--data_dir", type=str, default=None,
                    help="ROCO (mlm, supcon) or VQA-Med 2019 (vqa, eval) tree on disk; without it the batches are synthetic")
@@ -228,15 +236,25 @@ def maybe_resume(args, model, opt, sched, mode):
 
 
 # ----------------------------------------------------------------------------------------- one training step each
-def mlm_step(model, opt, red, world, batch):
+def mlm_step(model, opt, red, world, batch, scaler=None):
     """pretrain/roco_utils.py:214-247,257-265: zero_grad -> forward -> log_softmax + NLLLoss -> backward ->
-    (gradient all-reduce) -> Adam.  Returns (loss, pred[B,T], stats = {loss, #target>0, #correct})."""
+    (gradient all-reduce) -> Adam.  Returns (loss, pred[B,T], stats = {loss, #target>0, #correct}).
+    With a scaler (--mixed_precision, roco_utils.py:224-245): autocast forward + loss, scaled backward, scaler.step
+    after the all-reduce (every rank checks the same gradients), scaler.update."""
     img, ids, seg, mask, tgt = batch
     opt.zero_grad()
-    loss, pred, stats = mlm_loss(model(img, ids, seg, mask), tgt)
-    loss.backward()
+    if scaler is None:
+        loss, pred, stats = mlm_loss(model(img, ids, seg, mask), tgt)
+        loss.backward()
+        red.allreduce()
+        opt.step(grad_scale=1.0 / world, zero_grad=True)
+        return loss, pred, stats
+    with torch.autocast("cuda", dtype=torch.float16):
+        loss, pred, stats = mlm_loss(model(img, ids, seg, mask), tgt)
+    scaler.scale(loss).backward()
     red.allreduce()
-    opt.step(grad_scale=1.0 / world, zero_grad=True)
+    scaler.step(opt, grad_scale=1.0 / world, zero_grad=True)
+    scaler.update()
     return loss, pred, stats
 
 
@@ -264,20 +282,30 @@ def supcon_step(model, opt, red, world, batch):
     return loss, pred, stats
 
 
-def vqa_step(model, opt, red, world, batch, crit, clip=False):
+def vqa_step(model, opt, red, world, batch, crit, clip=False, scaler=None):
     """vqamed2019/utils.py:633-673: logits, _, _ = model(...); loss = criterion(logits, target); backward;
-    optional clip_grad_norm_(1.0) (:663-664); Adam; pred = softmax(1).argmax(1)"""
+    optional clip_grad_norm_(1.0) (:663-664); Adam; pred = softmax(1).argmax(1).
+    With a scaler (--mixed_precision) the reference's sequence of utils.py:641-657: autocast
+    forward + loss; scaler.scale(loss) is computed and DISCARDED; the backward is unscaled; the clip acts on those
+    gradients; scaler.step then unscales them by 1/scale all the same (and skips on a non-finite gradient)."""
     img, ids, seg, mask, tgt = batch
     opt.zero_grad()
-    logits, _, _ = model(img, ids, seg, mask)       # utils.py:646
-    loss = crit(logits, tgt)
+    with torch.autocast("cuda", dtype=torch.float16, enabled=scaler is not None):
+        logits, _, _ = model(img, ids, seg, mask)       # utils.py:646
+        loss = crit(logits, tgt)
+    if scaler is not None:
+        scaler.scale(loss)                          # utils.py:651: the scaled loss is not used
     loss.backward()
     red.allreduce()
     scale = 1.0 / world
     if clip:                                        # global 2-norm over the (averaged) flat gradient buffer
         gn = float(model.flat_grads.norm()) * scale
         scale *= min(1.0, 1.0 / (gn + 1e-6))
-    opt.step(grad_scale=scale, zero_grad=True)
+    if scaler is None:
+        opt.step(grad_scale=scale, zero_grad=True)
+    else:
+        scaler.step(opt, grad_scale=scale, zero_grad=True)
+        scaler.update()
     return loss, logits.detach().softmax(1).argmax(1)
 
 
@@ -286,6 +314,7 @@ def run_mlm(args):
     ctx = Ctx(args)
     args.dataset, args.task = "roco", "MLM"
     model, opt, sched, red = build(args, ctx)
+    scaler = GradScaler() if args.mixed_precision else None
     T, B, V = args.max_position_embeddings, args.batch_size, args.vocab_size
     tr_fd, args.val_feeder = roco_feeders(args, ctx) if args.data_dir else (None, None)
     start, kept = maybe_resume(args, model, opt, sched, "mlm")
@@ -297,10 +326,10 @@ def run_mlm(args):
                                       seed=args.seed + 7919 * (epoch * 100003 + i) + ctx.rank,
                                       device=ctx.dev, mlm_prob=args.mlm_prob) for i in range(args.steps_per_epoch))
         for img, ids, seg, mask, tgt in epoch_batches(tr_fd, epoch, synthetic):
-            _, _, stats = mlm_step(model, opt, red, ctx.world, (img, ids, seg, mask, tgt))
+            _, _, stats = mlm_step(model, opt, red, ctx.world, (img, ids, seg, mask, tgt), scaler=scaler)
             s = stats.tolist()               # per-step host sync, as roco_utils.py:267
             tl, nm, nc, steps = tl + s[0], nm + s[1], nc + s[2], steps + 1
-        vl, va = validate_mlm(args, ctx, model, epoch)
+        vl, va = validate_mlm(args, ctx, model, epoch, amp=args.mixed_precision)
         sched.step(vl)
         if (epoch + 1) % 5 == 0 and ctx.rank == 0:
             save_recorder(args, epoch, model, opt, sched, "mlm", {"best": min(best, vl)})
@@ -315,14 +344,16 @@ def run_mlm(args):
 
 
 @torch.no_grad()
-def validate_mlm(args, ctx, model, epoch):
+def validate_mlm(args, ctx, model, epoch, amp=False):
+    """amp: the forwards under fp16 autocast (mlm --mixed_precision, roco_utils.py:310-311); SupCon validates in fp32"""
     model.eval()
     vl, nm, nc, steps = 0.0, 0.0, 0.0, 0
     synthetic = (synth.roco_batch(args.batch_size, args.max_position_embeddings, args.image_size,
                                   min(args.vocab_size, args.emb_vocab), seed=10 ** 6 + i + ctx.rank,
                                   device=ctx.dev, mlm_prob=args.mlm_prob) for i in range(args.val_steps))
     for img, ids, seg, mask, tgt in epoch_batches(getattr(args, "val_feeder", None), epoch, synthetic):
-        out = model(img, ids, seg, mask)
+        with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
+            out = model(img, ids, seg, mask)
         logits = out[0] if isinstance(out, tuple) else out
         _, _, stats = mlm_loss(logits, tgt)
         s = stats.tolist()
@@ -394,6 +425,7 @@ def run_vqa(args):
         va_fd = feeder(args, ctx, D.VqaDataset(tabs["val"], tok, args.max_position_embeddings), False)
     C = args.num_classes
     model, opt, sched, red = build(args, ctx, n_classes=C)
+    scaler = GradScaler() if args.mixed_precision else None
     T, B = args.max_position_embeddings, args.batch_size
     crit = (lambda lg, t: asl_loss(lg, t)) if args.loss == "ASLSingleLabel" else (lambda lg, t: mlm_loss(lg, t)[0])
     # (vqamed2019/train.py itself has no recorder / --resume; kept here like the two pre-training loops)
@@ -407,7 +439,7 @@ def run_vqa(args):
                                      seed=args.seed + 7919 * (epoch * 100003 + i) + ctx.rank, device=ctx.dev)
                      for i in range(args.steps_per_epoch))
         for img, ids, seg, mask, tgt in epoch_batches(tr_fd, epoch, synthetic):
-            loss, _ = vqa_step(model, opt, red, ctx.world, (img, ids, seg, mask, tgt), crit, clip=args.clip)
+            loss, _ = vqa_step(model, opt, red, ctx.world, (img, ids, seg, mask, tgt), crit, clip=args.clip, scaler=scaler)
             tl, steps = tl + float(loss.detach()), steps + 1
         model.eval()
         vl, correct, total, vsteps = 0.0, 0, 0, 0
@@ -415,8 +447,9 @@ def run_vqa(args):
             synthetic = (synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=10 ** 6 + i, device=ctx.dev)
                          for i in range(args.val_steps))
             for img, ids, seg, mask, tgt in epoch_batches(va_fd, epoch, synthetic):
-                logits, _, _ = model(img, ids, seg, mask)
-                vl += float(crit(logits, tgt))
+                with torch.autocast("cuda", dtype=torch.float16, enabled=args.mixed_precision):   # utils.py:708-715
+                    logits, _, _ = model(img, ids, seg, mask)
+                    vl += float(crit(logits, tgt))
                 correct += int((logits.softmax(1).argmax(1) == tgt).sum())   # utils.py:673
                 total += tgt.shape[0]
                 vsteps += 1
@@ -487,7 +520,8 @@ def run_eval(args):
     else:
         batches = loader()
     cats = [r[3] for r in rows]
-    test_loss, predictions, acc, bleu = evaluate.test(batches, model, crit, cats, idx2ans, category=args.category)
+    with torch.autocast("cuda", dtype=torch.float16, enabled=args.mixed_precision):   # utils.py:786-792
+        test_loss, predictions, acc, bleu = evaluate.test(batches, model, crit, cats, idx2ans, category=args.category)
     model_name = (args.model_dir or args.run_name).split("/")[-1]               # eval.py:68
     if ctx.rank == 0:
         paths = evaluate.write_test_files(rows, cols, predictions, idx2ans, args.save_dir, model_name)   # eval.py:171-178
@@ -524,6 +558,11 @@ def main(argv=None):
         p.add_argument("--category", type=str, default=None, help="eval: one question category only (eval.py:29)")
         p.add_argument("--test_samples", type=int, default=64, help="eval: size of the synthetic test split")
     args = p.parse_args(argv)
+    if args.mixed_precision and args.overlap_adam:
+        p.error("--overlap_adam cannot be combined with --mixed_precision: the whole gradient must be checked for "
+                "inf / nan before the first parameter update")
+    if args.mixed_precision and mode == "supcon":
+        print("--mixed_precision: the SupCon loop runs in fp32, as the reference's (supcon_utils.py:263-323 has no autocast)")
     out = {"mlm": run_mlm, "supcon": run_supcon, "vqa": run_vqa, "eval": run_eval}[mode](args)
     if dist.is_initialized():
         dist.destroy_process_group()
