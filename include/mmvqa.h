@@ -405,6 +405,23 @@ int mmvqa_engine_forward(mmvqa_engine* e, mmvqa_stream_t s, const float* img, co
 /* accumulates into grads; dlogits same layout as logits; dfeat nullable */
 int mmvqa_engine_backward(mmvqa_engine* e, mmvqa_stream_t s, const float* dlogits, int dlogits_ld,
                           const float* dfeat);
+/* Attribution: after an EVAL-mode mmvqa_engine_forward (training = 0, fp32 operands), writes dA = the gradient of
+ * sum(dlogits * logits) with respect to the deepest backbone feature map A (ResNet: output of layer4, tapped by conv2;
+ * EfficientNet: output of the last block = o[4], tapped by conv7), NHWC fp32 [B][H][W][C], into the caller's buffer.
+ * Data gradients only (heads -> encoder -> one visual-token row -> one tap) on the given stream alone: parameters, the
+ * gradient buffer, BatchNorm buffers are not written, no gradient callback is called.  MMVQA_ERR_STATE before any forward
+ * or after a training-mode forward, MMVQA_ERR_ARG in the f16 operand mode. */
+int mmvqa_engine_backward_feature(mmvqa_engine* e, mmvqa_stream_t s, const float* dlogits, int dlogits_ld, float* dA);
+/* where A lives (inside the bound workspace: valid from a forward until the next one) and its dimensions */
+int mmvqa_engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, int* C);
+/* Grad-CAM (vqamed2019/grad_cam2.py:139-176, batched per sample) from A and dA [B][H][W][C] (H * W <= 256, C % 4 == 0,
+ * C <= 4096): w[c] = mean_hw dA, cam = relu(mean_c w[c] A) / max -> cam [B][H][W], valid[b] = 0 (and zeros) when the
+ * maximum is not positive; up [B][IH][IW] = bilinear resize (half-pixel centres, edge clamp) or NULL; overlay
+ * [B][IH][IW][3] uint8 = clip(alpha * jet[(uint8)(255 up)] + image_u8, 0, 255) or NULL (then image_u8 / jet may be
+ * NULL); jet: 256 x 3 uint8 colour table on the device. */
+int mmvqa_gradcam(mmvqa_stream_t s, const float* A, const float* dA, int B, int H, int W, int C, float* cam, int* valid,
+                  float* up, int IH, int IW, const unsigned char* image_u8, const unsigned char* jet, float alpha,
+                  unsigned char* overlay);
 /* data-parallel overlap: cb(user, lo, hi) is called on the HOST thread inside mmvqa_engine_backward as soon as
  * the kernels completing grads[lo, hi) (float offsets) are enqueued and the given stream is ordered behind them, so
  * the caller can start the all-reduce of that range on its communication stream while backward continues.

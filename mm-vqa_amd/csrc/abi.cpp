@@ -8,6 +8,8 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW);
 int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long long* ids, const long long* seg,
                    const long long* mask, float* logits, int logits_ld, float* feat, int training, uint32_t seed);
 int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, const float* dfeat);
+int engine_backward_feature(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, float* dA);
+int engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, int* C);
 int engine_create(const mmvqa_model_desc* desc, mmvqa_engine** out);
 int engine_profile_collect(mmvqa_engine* e);
 
@@ -312,6 +314,14 @@ int mmvqa_engine_backward(mmvqa_engine* e, mmvqa_stream_t s, const float* dlogit
                           const float* dfeat) {
   if (!e || !dlogits) return mmvqa_set_error(MMVQA_ERR_ARG, "backward: null pointer");
   return engine_backward(e, ST(s), dlogits, dlogits_ld, dfeat);
+}
+int mmvqa_engine_backward_feature(mmvqa_engine* e, mmvqa_stream_t s, const float* dlogits, int dlogits_ld, float* dA) {
+  if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "backward_feature: null engine");
+  return engine_backward_feature(e, ST(s), dlogits, dlogits_ld, dA);
+}
+int mmvqa_engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, int* C) {
+  if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "feature_map: null engine");
+  return engine_feature_map(e, A, H, W, C);
 }
 int mmvqa_engine_set_grad_callback(mmvqa_engine* e, mmvqa_grad_cb cb, void* user) {
   if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "set_grad_callback: null engine");

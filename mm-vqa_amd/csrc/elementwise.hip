@@ -335,6 +335,7 @@ __global__ void layernorm_bwd_kernel(const float* __restrict__ dy, const float* 
     }
   }
   __syncthreads();
+  if (!dgamma) return;   // gradient with respect to x only (mmvqa_engine_backward_feature)
   for (int i = threadIdx.x; i < H; i += blockDim.x) {
     atomicAdd(&dgamma[i], lds[i]);
     atomicAdd(&dbeta[i], lds[H + i]);

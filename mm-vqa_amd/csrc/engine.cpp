@@ -597,8 +597,10 @@ static int ln_fwd(mmvqa_engine* e, hipStream_t st, const float* x, const LNRef& 
   return MMVQA_OK;
 }
 static int ln_bwd(mmvqa_engine* e, hipStream_t st, const float* dy, const float* x, const LNRef& ln,
-                  const float* mean, const float* rstd, const float* dres, float* dx, long rows) {
-  RUNB(HB_LAYERNORM_BWD, (dres ? 16.0 : 12.0) * rows * e->d.hidden, k_layernorm_bwd(st, dy, x, PRM(ln.g), mean, rstd, dres, dx, GRD(ln.g), GRD(ln.b), (int)rows,
+                  const float* mean, const float* rstd, const float* dres, float* dx, long rows, bool data_only = false) {
+  // data_only (mmvqa_engine_backward_feature): the gradient with respect to x alone, dgamma / dbeta are not accumulated
+  RUNB(HB_LAYERNORM_BWD, (dres ? 16.0 : 12.0) * rows * e->d.hidden, k_layernorm_bwd(st, dy, x, PRM(ln.g), mean, rstd, dres, dx,
+                                     data_only ? nullptr : GRD(ln.g), data_only ? nullptr : GRD(ln.b), (int)rows,
                                      e->d.hidden));
   return MMVQA_OK;
 }
@@ -748,8 +750,9 @@ static int tap_fwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
 }
 
 // backward of one tap: du (recompute), dW_tap, and the gradient wrt the feature map (T_k or masked G)
+// (data_only: the recompute and the data gradient, no weight gradient -- mmvqa_engine_backward_feature)
 static int tap_bwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, const BNRef* bn_in, float* dfmap,
-                   const EpiOpt& o) {
+                   const EpiOpt& o, bool data_only = false) {
   REG(REG_TAP);
   const TapRef& t = e->taps[k];
   const int Hd = e->d.hidden;
@@ -771,6 +774,7 @@ static int tap_bwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
     TRY(prof_end(e, st));
   } else
     RUN(PROF_IGEMM, 2.0 * (double)g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_FWD, 0, 0, st));
+  if (!data_only) {
   // dW_tap[Hd][C] += du^T fmap
   GemmParams w = gp_linear_geom();
   w.M = Hd; w.N = t.C; w.K = (int)t.M;
@@ -779,6 +783,7 @@ static int tap_bwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
   if (bn_in) { w.b_pro = PRO_AFFINE_RELU; w.b_c0 = WS(bn_in->scale); w.b_c1 = WS(bn_in->shift); }
   w.C = GRD(t.w); w.c_ld = t.C; w.c_atomic = 1;
   RUN(PROF_IGEMM, 2.0 * (double)w.M * w.N * w.K, mmvqa_launch_igemm(w, KIND_WGRAD, 0, 0, st));
+  }
   // dfmap[M][C] = du W_tap
   GemmParams dg = gp_linear_geom();
   dg.M = (int)t.M; dg.N = t.C; dg.K = Hd;
@@ -812,8 +817,8 @@ struct SideCtx {
   mmvqa_engine* e;
   hipStream_t st, sd;
   bool on;
-  SideCtx(mmvqa_engine* e_, hipStream_t st_) : e(e_), st(st_) {
-    on = e->use_side && !e->tuner.tuning;   // (the per-launch profiler records its events on the launching stream)
+  SideCtx(mmvqa_engine* e_, hipStream_t st_, bool allow = true) : e(e_), st(st_) {
+    on = allow && e->use_side && !e->tuner.tuning;   // (the per-launch profiler records its events on the launching stream)
     if (on && !e->side) {
       // the side stream carries work with slack (weight gradients, taps, downsample branches): lowest priority, so
       // that the dependency chain on the caller's stream is dispatched first whenever both have kernels ready
@@ -902,10 +907,12 @@ struct SideReads {
   SideCtx& sc;
   bool on;
   std::vector<std::pair<const void*, hipEvent_t>> rd;
-  explicit SideReads(SideCtx& s) : sc(s) {
+  bool data_only;   // data gradients only (mmvqa_engine_backward_feature): no weight / bias / LayerNorm-parameter gradient
+  explicit SideReads(SideCtx& s, bool data_only_ = false) : sc(s), data_only(data_only_) {
     static const bool off = getenv("MMVQA_ENC_SIDE_OFF") != nullptr;
-    on = sc.on && !off;
+    on = sc.on && !off && !data_only;
   }
+  float* bias_grad(float* g) const { return data_only ? nullptr : g; }
   void read(const void* p) {
     hipEvent_t ev = sc.mark();
     for (auto& kv : rd) if (kv.first == p) { kv.second = ev; return; }
@@ -919,6 +926,7 @@ struct SideReads {
 // dW += dy^T x (+ bias gradient) beside the chain: starts behind everything queued on the caller's stream so far
 static int lin_wgrad_side(mmvqa_engine* e, SideReads& sr, hipStream_t st, const float* dy, int dy_ld, const float* x, int x_ld, long M,
                           const LinRef& L, bool bias_from_colsum) {
+  if (sr.data_only) return MMVQA_OK;
   if (!sr.on) return lin_wgrad(e, st, dy, dy_ld, x, x_ld, M, L, bias_from_colsum);
   sr.sc.fork();
   TRY(lin_wgrad(e, sr.sc.sd, dy, dy_ld, x, x_ld, M, L, bias_from_colsum));
@@ -1492,13 +1500,13 @@ static int bert_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, Sid
     }
     TRY(lin_wgrad_side(e, sr, st, dzd, H, WS(L.h1), 4 * H, M, L.fc2, true));
     sr.write(WS(e->t_big));
-    TRY(lin_dgrad(e, st, dzd, H, M, L.fc2, WS(e->t_big), 4 * H, ACT_GELU, WS(L.pre1), 4 * H, GRD(L.fc1.b), nullptr, 0));
+    TRY(lin_dgrad(e, st, dzd, H, M, L.fc2, WS(e->t_big), 4 * H, ACT_GELU, WS(L.pre1), 4 * H, sr.bias_grad(GRD(L.fc1.b)), nullptr, 0));
     TRY(lin_wgrad_side(e, sr, st, WS(e->t_big), 4 * H, WS(L.xn2), H, M, L.fc1, false));
     sr.write(WS(e->t_c));
     TRY(lin_dgrad(e, st, WS(e->t_big), 4 * H, M, L.fc1, WS(e->t_c), H, 0, nullptr, 0, nullptr, nullptr, 0));
     // dy = LN'(dxn2) + dz
     sr.write(WS(e->t_d));
-    TRY(ln_bwd(e, st, WS(e->t_c), WS(L.y), e->norm1, WS(L.mean2), WS(L.rstd2), dz, WS(e->t_d), M));
+    TRY(ln_bwd(e, st, WS(e->t_c), WS(L.y), e->norm1, WS(L.mean2), WS(L.rstd2), dz, WS(e->t_d), M, sr.data_only));
     float* dy = WS(e->t_d);
     // attention branch: y = x + drop(proj(attn(norm1(x))))
     const float* dyd = dy;
@@ -1528,7 +1536,7 @@ static int bert_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, Sid
       sr.write(WS(e->t_c));
       TRY(lin_dgrad(e, st, dqkv, 3 * H, M, L.qkv, WS(e->t_c), H, 0, nullptr, 0, nullptr, nullptr, 0)); }  // dxn1
     sr.write(dz);
-    TRY(ln_bwd(e, st, WS(e->t_c), x, e->norm1, WS(L.mean1), WS(L.rstd1), dy, dz, M));
+    TRY(ln_bwd(e, st, WS(e->t_c), x, e->norm1, WS(L.mean1), WS(L.rstd1), dy, dz, M, sr.data_only));
   }
   return MMVQA_OK;
 }
@@ -1578,7 +1586,7 @@ static int rf_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, SideR
     const float* x = i == 0 ? x_in : WS(e->rf[i - 1].x2);
     // x2 = ln2(s2), s2 = x1 + drop(ff2(serf(ff0(x1))))
     sr.write(WS(e->t_d));
-    TRY(ln_bwd(e, st, dx2, WS(L.s2), L.ln2, WS(L.mean2), WS(L.rstd2), nullptr, WS(e->t_d), M));
+    TRY(ln_bwd(e, st, dx2, WS(L.s2), L.ln2, WS(L.mean2), WS(L.rstd2), nullptr, WS(e->t_d), M, sr.data_only));
     float* ds2 = WS(e->t_d);
     const float* dff = ds2;
     if (p > 0.f) {
@@ -1588,13 +1596,13 @@ static int rf_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, SideR
     }
     TRY(lin_wgrad_side(e, sr, st, dff, H, WS(L.hact), 4 * H, M, L.ff2, true));
     sr.write(WS(e->t_big));
-    TRY(lin_dgrad(e, st, dff, H, M, L.ff2, WS(e->t_big), 4 * H, ACT_SERF, WS(L.pre), 4 * H, GRD(L.ff0.b), nullptr, 0));
+    TRY(lin_dgrad(e, st, dff, H, M, L.ff2, WS(e->t_big), 4 * H, ACT_SERF, WS(L.pre), 4 * H, sr.bias_grad(GRD(L.ff0.b)), nullptr, 0));
     TRY(lin_wgrad_side(e, sr, st, WS(e->t_big), 4 * H, WS(L.x1), H, M, L.ff0, false));
     sr.write(WS(e->t_c));
     TRY(lin_dgrad(e, st, WS(e->t_big), 4 * H, M, L.ff0, WS(e->t_c), H, 0, nullptr, 0, nullptr, ds2, H));  // dx1 total
     // x1 = ln1(s1), s1 = x + drop(proj(res))
     sr.write(WS(e->t_d));
-    TRY(ln_bwd(e, st, WS(e->t_c), WS(L.s1), L.ln1, WS(L.mean1), WS(L.rstd1), nullptr, WS(e->t_d), M));
+    TRY(ln_bwd(e, st, WS(e->t_c), WS(L.s1), L.ln1, WS(L.mean1), WS(L.rstd1), nullptr, WS(e->t_d), M, sr.data_only));
     float* ds1 = WS(e->t_d);
     const float* dr = ds1;
     if (p > 0.f) {
@@ -1666,7 +1674,7 @@ static int heads_backward(mmvqa_engine* e, hipStream_t st, const float* h, const
   const long M = (long)e->B * e->T;
   const long HM = d.head_kind == 1 ? e->B : M;
   const float* hin = d.head_kind == 1 ? WS(e->hd_pool) : h;
-  {  // classifier[2]: logits = c1 W^T + b  (beside the data gradient of the same layer: both read dlogits, nobody writes it)
+  if (!sr.data_only) {  // classifier[2]: logits = c1 W^T + b  (beside the data gradient of the same layer: both read dlogits, nobody writes it)
     hipStream_t st_main = st;
     if (sr.on) sr.sc.fork();
     hipStream_t st = sr.on ? sr.sc.sd : st_main;
@@ -1679,9 +1687,9 @@ static int heads_backward(mmvqa_engine* e, hipStream_t st, const float* h, const
     RUN(PROF_OTHER, 0, k_colsum(st, dlogits, dl_ld, (int)HM, d.n_classes, GRD(e->cls2.b)));
   }
   TRY(lin_dgrad(e, st, dlogits, dl_ld, HM, e->cls2, WS(e->t_b), H, 0, nullptr, 0, nullptr, nullptr, 0));  // dc1
-  TRY(ln_bwd(e, st, WS(e->t_b), WS(e->hd_c0), e->cls_ln, WS(e->hd_mean), WS(e->hd_rstd), nullptr, WS(e->t_c), HM));
+  TRY(ln_bwd(e, st, WS(e->t_b), WS(e->hd_c0), e->cls_ln, WS(e->hd_mean), WS(e->hd_rstd), nullptr, WS(e->t_c), HM, sr.data_only));
   TRY(lin_wgrad_side(e, sr, st, WS(e->t_c), H, WS(e->hd_u), H, HM, e->cls0, true));
-  TRY(lin_dgrad(e, st, WS(e->t_c), H, HM, e->cls0, WS(e->t_b), H, ACT_SERF, WS(e->hd_upre), H, GRD(e->fc1.b), nullptr, 0));
+  TRY(lin_dgrad(e, st, WS(e->t_c), H, HM, e->cls0, WS(e->t_b), H, ACT_SERF, WS(e->hd_upre), H, sr.bias_grad(GRD(e->fc1.b)), nullptr, 0));
   TRY(lin_wgrad_side(e, sr, st, WS(e->t_b), H, hin, H, HM, e->fc1, false));
   float* dh = WS(e->t_a);
   if (d.head_kind == 1) {
@@ -1782,6 +1790,59 @@ int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int d
   e->prof_reg = REG_BACKBONE;
   if (e->grad_cb) e->grad_cb(e->grad_cb_user, 0, e->emb_hi);            // embedding tables + LayerNorm
   return d.cnn == 1 ? effnet_backward(e, st) : resnet_backward(e, st);
+}
+
+// The deepest backbone feature map A (the one map that feeds nothing but its own tap) and the index of that tap =
+// the visual-token row it fills: ResNet layer4 -> conv2 -> row 0, EfficientNet last block (o[4]) -> conv7 -> row 4.
+static int feature_tap(const mmvqa_engine* e, size_t* off, int* H, int* W, int* C) {
+  if (e->d.cnn == 1) { const EffBlock& b = e->eff.back(); *off = b.out; *H = b.OH; *W = b.OW; *C = b.cout; return 4; }
+  const BlockRef& b = e->blocks.back(); *off = b.out; *H = b.OH; *W = b.OW; *C = b.c3.Cout; return 0;
+}
+
+int engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, int* C) {
+  if (!e->planned || !e->bound) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_feature_map: plan/bind and run a forward first");
+  size_t off = 0; int h = 0, w = 0, c = 0;
+  (void)feature_tap(e, &off, &h, &w, &c);
+  if (A) *A = WS(off);
+  if (H) *H = h;
+  if (W) *W = w;
+  if (C) *C = c;
+  return MMVQA_OK;
+}
+
+// Gradient of sum(dlogits * logits) with respect to the deepest feature map, after an eval-mode forward: the data
+// gradients of heads -> encoder -> one visual-token row -> one tap, on the caller's stream alone.  The eval forward
+// already leaves everything this reads (attention probabilities, LayerNorm statistics, pre-activations: nothing in the
+// forward is conditional on `training` except dropout probabilities and BatchNorm statistics).  Parameters, gradient
+// buffer and BatchNorm buffers are not written.
+int engine_backward_feature(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, float* dA) {
+  if (!e->planned || !e->bound || !e->img)
+    return mmvqa_set_error(MMVQA_ERR_STATE, "engine_backward_feature: run an eval-mode forward first");
+  if (e->training)
+    return mmvqa_set_error(MMVQA_ERR_STATE, "engine_backward_feature: the last forward ran in training mode (dropout and batch "
+                                            "statistics couple the samples); run an eval-mode forward first");
+  if (e->prec != MMVQA_PREC_F32)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward_feature: attribution runs with fp32 operands, not in the f16 operand mode");
+  const mmvqa_model_desc& d = e->d;
+  if (!dlogits || !dA) return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward_feature: null pointer");
+  if (dl_ld < d.n_classes || (dl_ld & 3))
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward_feature: dlogits_ld=%d must be >= n_classes and %%4==0", dl_ld);
+  struct TunerScope { TunerScope(IgemmTuner* t) { mmvqa_set_tuner(t); } ~TunerScope() { mmvqa_set_tuner(nullptr); } } ts(&e->tuner);
+  PrecScope ps(MMVQA_PREC_F32);
+  e->ev_next = 0;
+  SideCtx sc(e, st, false);
+  SideReads sr(sc, true);
+  TRY(heads_backward(e, st, WS(e->enc_out_final), dlogits, dl_ld, nullptr, sr));
+  if (d.encoder == 0) TRY(bert_backward(e, st, WS(e->emb_out), sr));
+  else TRY(rf_backward(e, st, WS(e->emb_out), sr));
+  size_t off = 0; int h = 0, w = 0, C = 0;
+  const int k = feature_tap(e, &off, &h, &w, &C);
+  // the visual tokens overwrite rows 0..4 after the embedding LayerNorm: dvis[k][b] is row k of sample b, copied
+  HIP_CHECK_RET(hipMemcpy2DAsync(WS(e->dvis) + (size_t)k * e->B * d.hidden, (size_t)d.hidden * sizeof(float),
+                                 WS(e->t_a) + (size_t)k * d.hidden, (size_t)e->T * d.hidden * sizeof(float),
+                                 (size_t)d.hidden * sizeof(float), (size_t)e->B, hipMemcpyDeviceToDevice, st));
+  e->prof_reg = REG_BACKBONE;
+  return tap_bwd(e, st, k, WS(off), nullptr, dA, EpiOpt(), true);
 }
 
 int engine_create(const mmvqa_model_desc* desc, mmvqa_engine** out) {

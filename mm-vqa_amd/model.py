@@ -373,6 +373,43 @@ class Model(nn.Module):
             raise err
         self.attach_grads()
 
+    def feature_gradient(self, img, input_ids, segment_ids, input_mask, target=None):
+        """Attribution pass (vqamed2019/grad_cam2.py:139-145, batched): an eval-mode forward, then the gradient of
+        logits[b, target[b]] with respect to the deepest backbone feature map A of sample b (ResNet: layer4's output,
+        EfficientNet: the last block's, o[4]).  Returns (logits [B, classes], A, dA, target) with A, dA NHWC
+        [B, H, W, C] fp32.  target=None: the predicted class.  Data gradients only: parameters, .grad, BatchNorm buffers
+        and self.training are as before; nothing here waits for the device.  fp32 only (NotImplementedError inside
+        torch.autocast), VQA head only."""
+        if torch.is_autocast_enabled("cuda"):
+            raise NotImplementedError("attribution (feature_gradient / grad_cam) is fp32 in this version: call it outside "
+                                      "torch.autocast")
+        d = self._desc
+        if d.head_kind != 1:
+            raise NotImplementedError("feature_gradient needs the VQA head (dataset='VQA-Med'): one row of logits per sample")
+        lib = L.lib()
+        was_training = self.training
+        self.train(False)
+        try:
+            with torch.no_grad():
+                logits = self._engine_forward(img, input_ids, segment_ids, input_mask, L.PREC_F32)
+        finally:
+            self.train(was_training)
+        B, V = logits.shape
+        ld = self._fwd_state[6]
+        if target is None:
+            target = logits.argmax(1)
+        target = torch.as_tensor(target, device=logits.device).long().reshape(B)
+        g = torch.zeros(B, ld, dtype=torch.float32, device=logits.device)
+        g.scatter_(1, target.view(B, 1), 1.0)
+        ap, fh, fw, fc = C.c_void_p(), C.c_int(), C.c_int(), C.c_int()
+        L.check(lib.mmvqa_engine_feature_map(self._handle, C.byref(ap), C.byref(fh), C.byref(fw), C.byref(fc)))
+        H, W, Cc = fh.value, fw.value, fc.value
+        off = ap.value - self._ws.data_ptr()
+        A = self._ws[off:off + 4 * B * H * W * Cc].view(torch.float32).view(B, H, W, Cc).clone()   # (the next forward overwrites the workspace)
+        dA = torch.empty(B, H, W, Cc, dtype=torch.float32, device=logits.device)
+        L.check(lib.mmvqa_engine_backward_feature(self._handle, L.stream_ptr(), L.ptr(g), ld, L.ptr(dA)))
+        return logits, A, dA, target
+
     def forward(self, img, input_ids, segment_ids, input_mask):
         """Inside torch.autocast("cuda", dtype=torch.float16) the forward and its backward run in the mixed-precision
         mode: both operands of every contraction of the implicit GEMM (every ResNet convolution with the stem,

@@ -5,6 +5,7 @@ which never ship to the GPU box (SURVEY.md 8(b) "Callers the build must supply")
   supcon   pretrain/roco_supcon_train.py:137,168-202 + models/SupConLoss/supcon_utils.py:253-379
   vqa      vqamed2019/train.py:125-296 + vqamed2019/utils.py:625-767
   eval     vqamed2019/eval.py:99-180 + vqamed2019/utils.py:769-843 (test-set run: metrics, <model>_preds.csv, <model>_res.txt)
+  gradcam  vqamed2019/grad_cam2.py:99-188 over the test split (one overlay PNG per row + gradcam_index.csv)
 
 Kept from the reference: option names and defaults, Adam(lr) + ReduceLROnPlateau(patience, factor) on the
 validation loss, zero_grad -> forward -> loss -> backward -> step order, loss / accuracy definitions,
@@ -487,6 +488,24 @@ def run_eval(args):
     -> test() over the test split (batch_size, shuffle False) -> print acc / bleu -> <model_name>_preds.csv and
     <model_name>_res.txt in save_dir.  The test split is synthetic (mmvqa_amd.synth.vqa_test_table + vqa_batch: the
     dataset and its tokenizer are not in the image); everything after the loader is the reference's sequence."""
+    ctx, model, cols, rows, idx2ans, batches = eval_setup(args)
+    crit = (lambda lg, t: asl_loss(lg, t)) if args.loss == "ASLSingleLabel" else (lambda lg, t: mlm_loss(lg, t)[0])
+    cats = [r[3] for r in rows]
+    with torch.autocast("cuda", dtype=torch.float16, enabled=args.mixed_precision):   # utils.py:786-792
+        test_loss, predictions, acc, bleu = evaluate.test(batches, model, crit, cats, idx2ans, category=args.category)
+    model_name = (args.model_dir or args.run_name).split("/")[-1]               # eval.py:68
+    if ctx.rank == 0:
+        paths = evaluate.write_test_files(rows, cols, predictions, idx2ans, args.save_dir, model_name)   # eval.py:171-178
+        print("test_loss", float(test_loss))
+        print("acc", acc)
+        print("bleu", bleu)
+        print("wrote", *paths)
+    return test_loss, acc, bleu
+
+
+def eval_setup(args):
+    """What the test-set run and `gradcam` share: the model with its checkpoint (eval.py:99-112) and the test split in
+    file order -> (ctx, model, columns, rows, idx2ans, batches)"""
     ctx = Ctx(args)
     args.dataset, args.task = "VQA-Med", "MLM"
     if args.data_dir:                                   # the real test split (vqamed2019/utils.py:51-79)
@@ -502,7 +521,6 @@ def run_eval(args):
         print("Loading model at ", args.model_dir)
         model.load_state_dict(checkpoint.read_state_dict(args.model_dir))        # eval.py:112
     model.to(ctx.dev)
-    crit = (lambda lg, t: asl_loss(lg, t)) if args.loss == "ASLSingleLabel" else (lambda lg, t: mlm_loss(lg, t)[0])
     B, T = args.batch_size, args.max_position_embeddings
     if not args.data_dir:
         cols, rows, idx2ans = synth.vqa_test_table(args.test_samples, C, seed=args.seed)
@@ -519,22 +537,54 @@ def run_eval(args):
         batches = ((img, ids, seg, mask, tgt.clone()) for img, ids, seg, mask, tgt in epoch_batches(test_fd, 0, None))
     else:
         batches = loader()
-    cats = [r[3] for r in rows]
-    with torch.autocast("cuda", dtype=torch.float16, enabled=args.mixed_precision):   # utils.py:786-792
-        test_loss, predictions, acc, bleu = evaluate.test(batches, model, crit, cats, idx2ans, category=args.category)
-    model_name = (args.model_dir or args.run_name).split("/")[-1]               # eval.py:68
+    return ctx, model, cols, rows, idx2ans, batches
+
+
+# ----------------------------------------------------------------------------------------- Grad-CAM over the test split
+def run_gradcam(args):
+    """vqamed2019/grad_cam2.py:99-188 over the whole test split instead of one named image: the model and checkpoint of
+    `eval`, one attribution pass per batch (mmvqa_amd.gradcam.grad_cam), <save_dir>/<category>_<image name>.png per
+    row (grad_cam2.py:188's naming) and gradcam_index.csv (image, category, question index, target, predicted, valid)."""
+    import csv
+    from PIL import Image
+    from . import gradcam as G
+    if args.mixed_precision:
+        raise SystemExit("gradcam: attribution runs in fp32 (no --mixed_precision)")
+    ctx, model, _cols, rows, _idx2ans, batches = eval_setup(args)
+    model.eval()
+    limit = len(rows) if args.limit is None else min(args.limit, len(rows))
+    os.makedirs(args.save_dir, exist_ok=True)
+    index, done = [], 0
+    for img, ids, seg, mask, tgt in batches:
+        if done >= limit:
+            break
+        res = G.grad_cam(model, img, ids, seg, mask, target=tgt if args.target == "answer" else None,
+                         image_u8=G.image_u8_from_normalised(img))
+        over, pred = res.overlay.cpu().numpy(), res.logits.argmax(1).cpu().tolist()
+        target, valid = res.target.cpu().tolist(), res.valid.cpu().tolist()
+        for b in range(img.shape[0]):
+            if done >= limit:
+                break
+            path, _q, _a, cat, _m = rows[done]
+            name = os.path.splitext(os.path.basename(str(path)))[0]
+            out = os.path.join(args.save_dir, f"{cat}_{name}.png")
+            if ctx.rank == 0:
+                Image.fromarray(over[b], "RGB").save(out)
+            index.append([os.path.basename(out), cat, done, target[b], pred[b], valid[b]])
+            done += 1
+    p_idx = os.path.join(args.save_dir, "gradcam_index.csv")
     if ctx.rank == 0:
-        paths = evaluate.write_test_files(rows, cols, predictions, idx2ans, args.save_dir, model_name)   # eval.py:171-178
-        print("test_loss", float(test_loss))
-        print("acc", acc)
-        print("bleu", bleu)
-        print("wrote", *paths)
-    return test_loss, acc, bleu
+        with open(p_idx, "w", newline="") as f:
+            w = csv.writer(f, lineterminator="\n")
+            w.writerow(["image", "category", "question_index", "target", "predicted", "valid"])
+            w.writerows(index)
+        print("wrote", done, "overlays and", p_idx)
+    return index
 
 
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
-    mode = argv.pop(0) if argv and argv[0] in ("mlm", "supcon", "vqa", "eval") else "mlm"
+    mode = argv.pop(0) if argv and argv[0] in ("mlm", "supcon", "vqa", "eval", "gradcam") else "mlm"
     p = argparse.ArgumentParser(description=f"mmvqa_amd training ({mode})")
     common_args(p)
     if mode in ("mlm", "supcon"):
@@ -557,13 +607,17 @@ def main(argv=None):
         p.add_argument("--resume_dir", type=str, default=None, help="fine-tuned Model state_dict to continue from")
         p.add_argument("--category", type=str, default=None, help="eval: one question category only (eval.py:29)")
         p.add_argument("--test_samples", type=int, default=64, help="eval: size of the synthetic test split")
+        if mode == "gradcam":
+            p.add_argument("--target", type=str, default="answer", choices=["answer", "predicted"],
+                           help="the class each map explains: the row's answer (grad_cam2.py:141) or the model's prediction")
+            p.add_argument("--limit", type=int, default=None, help="stop after N rows of the split")
     args = p.parse_args(argv)
     if args.mixed_precision and args.overlap_adam:
         p.error("--overlap_adam cannot be combined with --mixed_precision: the whole gradient must be checked for "
                 "inf / nan before the first parameter update")
     if args.mixed_precision and mode == "supcon":
         print("--mixed_precision: the SupCon loop runs in fp32, as the reference's (supcon_utils.py:263-323 has no autocast)")
-    out = {"mlm": run_mlm, "supcon": run_supcon, "vqa": run_vqa, "eval": run_eval}[mode](args)
+    out = {"mlm": run_mlm, "supcon": run_supcon, "vqa": run_vqa, "eval": run_eval, "gradcam": run_gradcam}[mode](args)
     if dist.is_initialized():
         dist.destroy_process_group()
     return out
