@@ -288,6 +288,22 @@ int mmvqa_l2norm_bwd(mmvqa_stream_t s, const float* dy, const float* y, const fl
  * data-parallel job, SURVEY 8(e) collective 2). */
 int mmvqa_supcon_loss(mmvqa_stream_t s, const float* f, float* loss, float* df, float* ws, int N, int D, float temp,
                       float base_temp, float gscale);
+/* SupConLoss.forward(features, mask=mask) (loss.py:21-98, contrast_mode 'all', two views): mask is [N][N] fp32, any
+ * weights, may be asymmetric; it is tiled 2x2 over the 2N rows with the diagonal of the tiling zeroed, and weights the
+ * positives of every anchor: loss = -(T/T_base) mean_a sum_b mt[a][b] (z[a][b] - lse[a]) / M[a], M[a] = sum_b mt[a][b].
+ * A row with M[a] == 0 gives NaN, as the reference's division does.  f, df, N, D, gscale as mmvqa_supcon_loss;
+ * ws = 6*N floats (2*N more than the unmasked call: the mask row sums M, which the gradient pass needs for both
+ * mt[a][b] / M[a] and mt[b][a] / M[b]).  Null f / mask / loss / ws, D > 256 or N < 1: MMVQA_ERR_ARG. */
+int mmvqa_supcon_loss_masked(mmvqa_stream_t s, const float* f, const float* mask, float* loss, float* df, float* ws,
+                             int N, int D, float temp, float base_temp, float gscale);
+/* Jaccard mask of a batch (SimilarityCalculator.jaccard, supcon_utils.py:110-138) from a word-id CSR on the device:
+ * text (row, col), col in 0..3 (caption, three translations), owns the sorted unique ids
+ * ids[offsets[4*row+col] .. offsets[4*row+col+1]); offsets has 4*table_rows + 1 entries.  mask[i][j] (n x n fp32) = 1
+ * for i == j, else |A_i & B_j| / |A_i | B_j| (0 when both are empty) with A_i = text (rowsA[i], colsA[i]),
+ * B_j = text (rowsB[j], colsB[j]); the quotient is the double quotient rounded to fp32.  Sets of any length.  A row
+ * or column outside the table gives NaN in the entries it touches.  All pointers are device pointers. */
+int mmvqa_jaccard_mask(mmvqa_stream_t s, const int* offsets, const int* ids, const int* rowsA, const int* colsA,
+                       const int* rowsB, const int* colsB, float* mask, int n, int table_rows);
 /* ---- EfficientNetV2 (timm tf_efficientnetv2_m as models/image_encoding.py:15,26,100-115 instantiates it) pieces,
  * NHWC fp32; sc/sh = BatchNorm scale/shift of the producing conv (applied on load), stat = [16][C][2] doubles.
  * depthwise 3x3 (MBConv conv_dw): z2 = dw(silu(z1*s1+b1)), statistics of z2; TF "SAME" padding via pad (begin) */

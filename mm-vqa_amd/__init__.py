@@ -6,10 +6,10 @@ points here).  All arithmetic is in libmmvqa_hip.so (mm-vqa_amd/csrc, C ABI in i
 from . import _lib
 from ._lib import MMVQAError
 from .model import Model, desc_from_args
-from .functional import mlm_loss, asl_loss, supcon_loss, split_feat
+from .functional import mlm_loss, asl_loss, supcon_loss, split_feat, jaccard_mask
 from .optim import FusedAdam
 from . import synth
 from . import amp
 
-__all__ = ["Model", "desc_from_args", "mlm_loss", "asl_loss", "supcon_loss", "split_feat", "FusedAdam", "synth",
+__all__ = ["Model", "desc_from_args", "mlm_loss", "asl_loss", "supcon_loss", "split_feat", "jaccard_mask", "FusedAdam", "synth",
            "MMVQAError", "amp"]

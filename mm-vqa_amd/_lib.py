@@ -132,6 +132,8 @@ SIGNATURES = {
     "mmvqa_l2norm_fwd": (_i, [_P, _P, _P, _P, _i, _i]),
     "mmvqa_l2norm_bwd": (_i, [_P, _P, _P, _P, _P, _i, _i]),
     "mmvqa_supcon_loss": (_i, [_P, _P, _P, _P, _P, _i, _i, _f, _f, _f]),
+    "mmvqa_supcon_loss_masked": (_i, [_P, _P, _P, _P, _P, _P, _i, _i, _f, _f, _f]),
+    "mmvqa_jaccard_mask": (_i, [_P] * 8 + [_i, _i]),
     "mmvqa_dwconv_fwd": (_i, [_P, _P, _P, _P, _P, _P, _P] + [_i] * 8),
     "mmvqa_dwconv_bwd_data": (_i, [_P] * 14 + [_i] * 8),
     "mmvqa_dwconv_bwd_weight": (_i, [_P] * 10 + [_i] * 8),

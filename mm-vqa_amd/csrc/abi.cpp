@@ -152,6 +152,14 @@ int mmvqa_supcon_loss(mmvqa_stream_t s, const float* f, float* loss, float* df, 
                       float base_temp, float gscale) {
   return k_supcon(ST(s), f, loss, df, ws, N, D, temp, base_temp, gscale);
 }
+int mmvqa_supcon_loss_masked(mmvqa_stream_t s, const float* f, const float* mask, float* loss, float* df, float* ws,
+                             int N, int D, float temp, float base_temp, float gscale) {
+  return k_supcon_masked(ST(s), f, mask, loss, df, ws, N, D, temp, base_temp, gscale);
+}
+int mmvqa_jaccard_mask(mmvqa_stream_t s, const int* offsets, const int* ids, const int* rowsA, const int* colsA,
+                       const int* rowsB, const int* colsB, float* mask, int n, int table_rows) {
+  return k_jaccard_mask(ST(s), offsets, ids, rowsA, colsA, rowsB, colsB, mask, n, table_rows);
+}
 int mmvqa_dwconv_fwd(mmvqa_stream_t s, const float* z1, const float* s1, const float* b1, const float* w, float* z2,
                      double* stat, int N, int H, int W, int C, int OH, int OW, int stride, int pad) {
   return k_dwconv_fwd(ST(s), z1, s1, b1, w, z2, stat, N, H, W, C, OH, OW, stride, pad);

@@ -132,6 +132,69 @@ def roco_supcon_table(root):
     return out
 
 
+class WordSets:
+    """Word sets of every text of a SupCon table as one CSR of integer ids, for the Jaccard mask
+    (SimilarityCalculator.jaccard_similarity, supcon_utils.py:120-138).  Text t = row * 4 + column (0 = caption,
+    1..3 = the translations of CSV columns 3..5) owns ids[offsets[t]:offsets[t + 1]]: the sorted, unique ids of
+    set(text.lower().split()).  Words map to ids through one table-wide dictionary in first-seen order -- exact, no
+    hashing, so two different words never share an id.  offsets [4 * rows + 1] and ids are int32 tensors; built once
+    per dataset on the host, moved once with .to(device)."""
+
+    TEXTS = 4
+
+    def __init__(self, offsets, ids, rows, vocab=None):
+        self.offsets, self.ids, self.rows, self.vocab = offsets, ids, int(rows), vocab
+
+    @classmethod
+    def from_texts(cls, texts):
+        """texts: per row, (caption, t3, t4, t5)"""
+        vocab, offs, chunks = {}, [0], []
+        for row in texts:
+            if len(row) != cls.TEXTS:
+                raise ValueError(f"WordSets: a row holds {cls.TEXTS} texts (caption and three translations), got {len(row)}")
+            for t in row:
+                w = np.array(sorted({vocab.setdefault(x, len(vocab)) for x in t.lower().split()}), dtype=np.int64)
+                chunks.append(w)
+                offs.append(offs[-1] + len(w))
+        if offs[-1] >= 2 ** 31 or len(vocab) >= 2 ** 31:
+            raise ValueError(f"WordSets: {offs[-1]} ids / {len(vocab)} words do not fit int32 offsets")
+        ids = np.concatenate(chunks) if chunks else np.zeros(0, dtype=np.int64)
+        if ids.size == 0:
+            ids = np.zeros(1, dtype=np.int64)       # never read (every set is empty); keeps the pointer non-null
+        return cls(torch.from_numpy(np.asarray(offs, dtype=np.int32)), torch.from_numpy(ids.astype(np.int32)),
+                   len(texts), vocab)
+
+    @classmethod
+    def from_table(cls, rows):
+        """rows of roco_supcon_table: (image path, caption, (t3, t4, t5))"""
+        return cls.from_texts([(r[1],) + tuple(r[2]) for r in rows])
+
+    def to(self, device):
+        return WordSets(self.offsets.to(device), self.ids.to(device), self.rows, self.vocab)
+
+    def word_ids(self, row, col):
+        """the id set of one text as a numpy array (host copy of the CSR only)"""
+        t = int(row) * self.TEXTS + int(col)
+        o = self.offsets.numpy()
+        return self.ids.numpy()[o[t]:o[t + 1]]
+
+    def jaccard_host(self, rows_a, cols_a, rows_b, cols_b):
+        """the mask mmvqa_jaccard_mask computes, in numpy from the host CSR (tests, and the DDP rehearsal on CPU)"""
+        n = len(rows_a)
+        out = np.zeros((n, n), dtype=np.float32)
+        for i in range(n):
+            a = self.word_ids(rows_a[i], cols_a[i])
+            for j in range(n):
+                if i == j:
+                    out[i, j] = 1.0
+                    continue
+                b = self.word_ids(rows_b[j], cols_b[j])
+                inter = np.intersect1d(a, b, assume_unique=True).size
+                uni = a.size + b.size - inter
+                out[i, j] = np.float32(float(inter) / uni) if uni else 0.0
+        return out
+
+
 def vqa_tables(root):
     """-> (columns, {"train", "val", "test": [row]}, idx2ans).  A row is (image path, question, answer index, category,
     mode) -- the fields evaluate.write_test_files writes."""
@@ -224,35 +287,57 @@ def collate_supcon(items):
                 target=torch.cat([col(5), col(6)]), index=torch.tensor([it[7] for it in items], dtype=torch.int64))
 
 
+def collate_supcon_cols(items):
+    """collate_supcon for items that end with the translation column drawn (RocoSupConDataset(report_aug_col=True)):
+    the same dict plus aug_col [n] int32 (1..3: which translation each sample drew) and row [n] int32 (= index; the
+    pair (row, aug_col) names the translation text in the table's WordSets)"""
+    out = collate_supcon([it[:8] for it in items])
+    out["aug_col"] = torch.tensor([it[8] for it in items], dtype=torch.int32)
+    out["row"] = out["index"].to(torch.int32)
+    return out
+
+
 class RocoSupConDataset(torch.utils.data.Dataset):
     """item (epoch, index) -> (uint8 [H, W, 3], ids, aug_ids, seg, mask, tgt, aug_tgt, index) as supcon_utils.py:218-232
     returns it (the image untransformed: both views are made on the device).  One rng, sample_rng(seed, epoch,
     index), is drawn in the reference's order: the caption's MLM masking, then randint(3, 5) for the translation
     column (get_translation), then the translation's masking.  The translation's seg / mask are not kept: the
-    reference uses the caption's for both halves (process_tensors)."""
+    reference uses the caption's for both halves (process_tensors).
+    report_aug_col=True (the Jaccard mask needs to know which translation was drawn): the item gains a ninth element,
+    the drawn column as 1..3 (= CSV column - 2, the WordSets column), and batches are packed by collate_supcon_cols."""
 
     collate = staticmethod(collate_supcon)     # HostLoader packs its batches with it
 
-    def __init__(self, rows, tokenizer, keywords, num_vis=5, max_position_embeddings=75, mlm_prob=0.15, seed=0):
+    def __init__(self, rows, tokenizer, keywords, num_vis=5, max_position_embeddings=75, mlm_prob=0.15, seed=0,
+                 report_aug_col=False):
         self.rows, self.tok, self.kw = list(rows), tokenizer, frozenset(keywords)
         self.num_vis, self.T, self.mlm_prob, self.seed = num_vis, max_position_embeddings, mlm_prob, seed
+        self.report_aug_col = bool(report_aug_col)
+        if self.report_aug_col:
+            self.collate = collate_supcon_cols
 
     def __len__(self):
         return len(self.rows)
 
-    def encode(self, epoch, idx):
-        """the item's text: (ids, aug_ids, seg, mask, tgt, aug_tgt)"""
+    def encode_col(self, epoch, idx):
+        """(the item's text, the translation column drawn as 1..3)"""
         _path, caption, trans = self.rows[idx]
         rng = sample_rng(self.seed, epoch, idx)
         ids, seg, mask, tgt = text.encode_text(caption, self.tok, self.kw, self.num_vis, self.T, self.mlm_prob, rng)
-        aug = trans[rng.randint(3, 5) - 3]
-        aug_ids, _seg, _mask, aug_tgt = text.encode_text(aug, self.tok, self.kw, self.num_vis, self.T, self.mlm_prob,
-                                                         rng)
-        return ids, aug_ids, seg, mask, tgt, aug_tgt
+        col = rng.randint(3, 5) - 3
+        aug_ids, _seg, _mask, aug_tgt = text.encode_text(trans[col], self.tok, self.kw, self.num_vis, self.T,
+                                                         self.mlm_prob, rng)
+        return (ids, aug_ids, seg, mask, tgt, aug_tgt), col + 1
+
+    def encode(self, epoch, idx):
+        """the item's text: (ids, aug_ids, seg, mask, tgt, aug_tgt)"""
+        return self.encode_col(epoch, idx)[0]
 
     def __getitem__(self, key):
         epoch, idx = key
-        return (decode(self.rows[idx][0]),) + self.encode(epoch, idx) + (idx,)
+        enc, col = self.encode_col(epoch, idx)
+        item = (decode(self.rows[idx][0]),) + enc + (idx,)
+        return item + (col,) if self.report_aug_col else item
 
 
 def unpack(batch):
@@ -370,10 +455,16 @@ class DeviceFeeder:
     loop that syncs every step it sits between one step's sync and the next step's first launch.
 
     log: one entry per batch handed out -- epoch, batch, dataset rows and the augment params used (tests rebuild the
-    batch from it)."""
+    batch from it).
+
+    pairs=True (SupCon with the Jaccard mask; the host batches must carry `row` and `aug_col`, i.e. come from a
+    RocoSupConDataset(report_aug_col=True)): the batch is a 6-tuple whose last element is (rows, cols), two int32 device
+    tensors [n] naming the translation text (table row, WordSets column 1..3) of each sample.  They live in the slot and
+    are copied on the feeder's stream with the rest of it: same ready event, same reuse rule.  The log entry gains
+    `aug_col`.  With pairs=False (default) the batch stays the 5-tuple."""
 
     def __init__(self, host: HostLoader, device, train=True, depth=2, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5),
-                 fused=True):
+                 fused=True, pairs=False):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("DeviceFeeder runs on the GPU only (no CPU fallback)")
@@ -381,6 +472,7 @@ class DeviceFeeder:
             raise ValueError("depth must be >= 1")
         self.host, self.dev, self.depth, self.fused = host, device, int(depth), fused
         self.views = getattr(host, "views", 1)
+        self.pairs = bool(pairs)
         aug = host.aug or {}
         self.aug = DeviceAugment(size=host.size, train=train, mean=mean, std=std, device=device, **aug)
         self.stream, self.priority = low_priority_stream(device)
@@ -446,9 +538,22 @@ class DeviceFeeder:
                 d = buf[k][:B]
                 d.copy_(batch[k], non_blocking=True)
                 out.append(d)
+            if self.pairs:
+                if "aug_col" not in batch or "row" not in batch:
+                    raise ValueError("DeviceFeeder(pairs=True): the host batches carry no `row` / `aug_col` "
+                                     "(RocoSupConDataset(report_aug_col=True) reports them)")
+                n = batch["row"].shape[0]
+                if buf.get("pair") is None or buf["pair"].shape[1] < n:
+                    buf["pair"] = torch.empty(2, max(n, NI // self.views), dtype=torch.int32, device=self.dev)
+                rows, cols = buf["pair"][0, :n], buf["pair"][1, :n]
+                rows.copy_(batch["row"], non_blocking=True)
+                cols.copy_(batch["aug_col"], non_blocking=True)
+                out.append((rows, cols))
             slot.ready = torch.cuda.Event()
             slot.ready.record(s)
         entry = dict(meta, index=batch["index"].tolist(), params=params, shapes=batch["shapes"].tolist())
+        if self.pairs:
+            entry["aug_col"] = batch["aug_col"].tolist()
         self._queue.append((slot, tuple(out), entry))
         return True
 

@@ -6,7 +6,8 @@ fp32 buffer, so the exchange is a few large RCCL all-reduces over xGMI instead o
 buckets are cut from the END of the buffer first (heads/encoder gradients are complete before the
 backbone's), each issued asynchronously so RCCL's stream runs beside the remaining compute; the
 1/world_size scale is folded into the fused Adam (no extra pass).  SupCon features use an all-gather
-whose backward returns each rank its own slice.
+whose backward returns each rank its own slice; the Jaccard positive mask of that global view set is built on every
+rank from the all-gathered (row, column) index pairs (global_supcon_pairs).
 """
 from __future__ import annotations
 
@@ -248,3 +249,17 @@ def global_supcon_views(feat, n):
     w = world()
     parts = f.view(w, 2, n, -1)
     return torch.cat([parts[:, 0].reshape(w * n, 1, -1), parts[:, 1].reshape(w * n, 1, -1)], 1).contiguous()
+
+
+def global_supcon_pairs(rows, cols):
+    """(rows, cols) int32 [n] of this rank -- the (table row, translation column) of each sample -> the same for the
+    global batch, [world*n] each, rank-major: the sample order global_supcon_views gives the features.  One all-gather
+    of 2n integers on the current stream (no host synchronisation); every rank then builds the identical
+    [world*n, world*n] Jaccard mask from its own resident copy of the table's word sets, so no text travels."""
+    if world() == 1:
+        return rows, cols
+    mine = torch.stack([rows, cols]).contiguous()                  # [2, n]
+    out = [torch.empty_like(mine) for _ in range(world())]
+    dist.all_gather(out, mine)
+    g = torch.stack(out)                                           # [world, 2, n]
+    return g[:, 0].reshape(-1).contiguous(), g[:, 1].reshape(-1).contiguous()

@@ -24,6 +24,7 @@ torch.distributed (RCCL).
     python -m mmvqa_amd.train eval   --model_dir save/MLM/r.pt --num_classes 1552 --batch_size 16
     python -m mmvqa_amd.train mlm    --data_dir roco-dataset/data --vocab_file vocab.txt --num_workers 4
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --batch_size 32
+    python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --supcon_mask jaccard
 """
 from __future__ import annotations
 
@@ -35,10 +36,10 @@ import torch
 import torch.distributed as dist
 from torch.optim import lr_scheduler
 
-from . import FusedAdam, Model, asl_loss, checkpoint, evaluate, mlm_loss, split_feat, supcon_loss, synth
+from . import FusedAdam, Model, asl_loss, checkpoint, evaluate, jaccard_mask, mlm_loss, split_feat, supcon_loss, synth
 from . import data as D
 from .amp import GradScaler
-from .ddp import GradReducer, comm_info, global_supcon_views, sync_replicas
+from .ddp import GradReducer, comm_info, global_supcon_pairs, global_supcon_views, sync_replicas
 
 
 def common_args(p):
@@ -89,12 +90,12 @@ def common_args(p):
     p.add_argument("--feeder_depth", type=int, default=2, help="device batches prepared ahead of the step")
 
 
-def feeder(args, ctx, dataset, train, aug=None, batch_size=None, views=1):
+def feeder(args, ctx, dataset, train, aug=None, batch_size=None, views=1, pairs=False):
     """DeviceFeeder over one split (shuffled and augmented for training, file order and val transforms otherwise)"""
     host = D.HostLoader(dataset, batch_size or args.batch_size, shuffle=train, seed=args.seed, rank=ctx.rank,
                         world=ctx.world, num_workers=args.num_workers, aug=aug if train else None, size=args.image_size,
                         views=views)
-    return D.DeviceFeeder(host, ctx.dev, train=train, depth=args.feeder_depth)
+    return D.DeviceFeeder(host, ctx.dev, train=train, depth=args.feeder_depth, pairs=pairs)
 
 
 def tokenizer(args):
@@ -113,13 +114,18 @@ def roco_feeders(args, ctx):
 
 def roco_supcon_feeders(args, ctx, pairs):
     """(train, validation) feeders of SupCon: `pairs` samples x 2 views per train batch (roco_supcon_train.py:134-139,
-    drop_last=False), the plain ROCO validation split at the full --batch_size"""
+    drop_last=False), the plain ROCO validation split at the full --batch_size.  With --supcon_mask jaccard the train
+    batches carry each sample's (row, translation column) and the third value is the table's word sets on the device
+    (else None)."""
     tok, kw = tokenizer(args), D.load_keywords(args.data_dir)
-    tr = D.RocoSupConDataset(D.roco_supcon_table(args.data_dir), tok, kw, args.num_vis, args.max_position_embeddings,
-                             args.mlm_prob, args.seed)
+    table = D.roco_supcon_table(args.data_dir)
+    jac = getattr(args, "supcon_mask", "none") == "jaccard"
+    words = D.WordSets.from_table(table).to(ctx.dev) if jac else None
+    tr = D.RocoSupConDataset(table, tok, kw, args.num_vis, args.max_position_embeddings, args.mlm_prob, args.seed,
+                             report_aug_col=jac)
     va = D.RocoDataset(D.roco_table(args.data_dir, "validation"), tok, kw, args.num_vis, args.max_position_embeddings,
                        args.mlm_prob, args.seed)
-    return (feeder(args, ctx, tr, True, D.ROCO_AUG, batch_size=pairs, views=2), feeder(args, ctx, va, False))
+    return feeder(args, ctx, tr, True, D.ROCO_AUG, batch_size=pairs, views=2, pairs=jac), feeder(args, ctx, va, False), words
 
 
 def epoch_batches(fd, epoch, synthetic):
@@ -267,16 +273,26 @@ def process_tensors(img, caption_token, aug_tokens, segment_ids, attention_mask,
             cat(attention_mask, attention_mask), cat(target, aug_targets))
 
 
-def supcon_step(model, opt, red, world, batch):
+def supcon_step(model, opt, red, world, batch, words=None):
     """models/SupConLoss/supcon_utils.py:270-294: MLM loss over both views + SupCon(split_feat(feat)) (called without
-    a mask => SimCLR, :287); under DDP the views of all ranks are gathered first.  Returns (loss, pred, stats)."""
-    img, ids, seg, mask, tgt = batch
+    a mask => SimCLR, :287); under DDP the views of all ranks are gathered first.  Returns (loss, pred, stats).
+    With `words` (--supcon_mask jaccard: the table's WordSets on the device) the batch is the feeder's 6-tuple and the
+    loss is the call the reference leaves in a comment, supcon_loss(feat, mask=mask) with buildMask's Jaccard matrix
+    (:276-287): caption of sample i against the translation sample j drew.  Under DDP the (row, column) pairs of all
+    ranks are gathered and every rank builds the global mask, in the sample order of the gathered features; gather and
+    mask launch go on the step's stream."""
+    img, ids, seg, mask, tgt = batch[:5]
     opt.zero_grad()
     logits, feat = model(img, ids, seg, mask)
     loss_mlm, pred, stats = mlm_loss(logits, tgt)
     bsz = img.shape[0] // 2                        # supcon_utils.py:284 (2 = n_views)
     feat = global_supcon_views(feat, bsz)          # = split_feat(feat, bsz) on one rank; global negatives under DDP
-    loss = loss_mlm + supcon_loss(feat)            # 2N*world rows: the tiled kernel has no size cap
+    if words is None:
+        loss = loss_mlm + supcon_loss(feat)        # 2N*world rows: the tiled kernel has no size cap
+    else:
+        rows, cols = global_supcon_pairs(*batch[5])
+        pos = jaccard_mask(words, rows, torch.zeros_like(cols), rows, cols)
+        loss = loss_mlm + supcon_loss(feat, mask=pos)
     loss.backward()
     red.allreduce()
     opt.step(grad_scale=1.0 / world, zero_grad=True)
@@ -371,9 +387,9 @@ def run_supcon(args):
     n = args.batch_size // 2                      # roco_supcon_train.py:137: the loader yields bs//2 pairs
     if n < 1:
         raise ValueError("--batch_size must be >= 2 (two views per sample)")
-    tr_fd = None
+    tr_fd = words = None
     if args.data_dir:                             # fed batches come in process_tensors' layout (data.collate_supcon)
-        tr_fd, args.val_feeder = roco_supcon_feeders(args, ctx, n)
+        tr_fd, args.val_feeder, words = roco_supcon_feeders(args, ctx, n)
     start, kept = maybe_resume(args, model, opt, sched, "supcon")
     best = kept.get("best", float("inf"))
 
@@ -388,7 +404,7 @@ def run_supcon(args):
         model.train()
         tl, nm, nc, steps = 0.0, 0.0, 0.0, 0
         for batch in epoch_batches(tr_fd, epoch, synthetic(epoch)):
-            loss, _, stats = supcon_step(model, opt, red, ctx.world, batch)
+            loss, _, stats = supcon_step(model, opt, red, ctx.world, batch, words=words)
             tl, steps = tl + float(loss.detach()), steps + 1
             if tr_fd is not None:                 # the MLM accuracy train_one_epoch returns (supcon_utils.py:296-318)
                 s = stats.tolist()
@@ -582,7 +598,8 @@ def run_gradcam(args):
     return index
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """-> (mode, args); contradictory options end in argparse's error exit before anything touches the GPU"""
     argv = list(sys.argv[1:] if argv is None else argv)
     mode = argv.pop(0) if argv and argv[0] in ("mlm", "supcon", "vqa", "eval", "gradcam") else "mlm"
     p = argparse.ArgumentParser(description=f"mmvqa_amd training ({mode})")
@@ -593,7 +610,11 @@ def main(argv=None):
         p.add_argument("--max_position_embeddings", type=int, default=75)
         if mode == "supcon":
             p.add_argument("--con_task", type=str, default="supcon", choices=["simclr", "supcon"])
-            p.add_argument("--similarity", type=str, default="sentence_transformers")
+            p.add_argument("--similarity", type=str, default="sentence_transformers")      # accepted, not read
+            p.add_argument("--supcon_mask", type=str, default="none", choices=["none", "jaccard"],
+                           help="positives of the SupCon loss: none = the other view only (SimCLR, what the reference's "
+                                "loop runs); jaccard = caption / back-translation word overlap weights every pair "
+                                "(SimilarityCalculator.jaccard), built on the GPU per batch.  Needs --data_dir")
     else:
         p.add_argument("--lr", type=float, default=1e-4)
         p.add_argument("--max_position_embeddings", type=int, default=28)
@@ -615,6 +636,16 @@ def main(argv=None):
     if args.mixed_precision and args.overlap_adam:
         p.error("--overlap_adam cannot be combined with --mixed_precision: the whole gradient must be checked for "
                 "inf / nan before the first parameter update")
+    if mode == "supcon" and args.supcon_mask != "none":
+        if args.con_task == "simclr":
+            p.error(f"--con_task simclr contradicts --supcon_mask {args.supcon_mask}: SimCLR has no positive mask")
+        if not args.data_dir:
+            p.error(f"--supcon_mask {args.supcon_mask} needs --data_dir: synthetic batches have no captions to compare")
+    return mode, args
+
+
+def main(argv=None):
+    mode, args = parse_args(argv)
     if args.mixed_precision and mode == "supcon":
         print("--mixed_precision: the SupCon loop runs in fp32, as the reference's (supcon_utils.py:263-323 has no autocast)")
     out = {"mlm": run_mlm, "supcon": run_supcon, "vqa": run_vqa, "eval": run_eval, "gradcam": run_gradcam}[mode](args)

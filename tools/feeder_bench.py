@@ -13,6 +13,13 @@ workers over the wall time of the fed blocks.
 
     python tools/feeder_bench.py --out profiles/feeder_cfg2.json
     python tools/feeder_bench.py --config 4 --out profiles/feeder_cfg4.json
+
+--config 4 --supcon_mask jaccard: the fed config-4 step with the Jaccard positive mask (train.py --supcon_mask jaccard:
+the feeder hands out the (row, column) pairs, mmvqa_jaccard_mask builds the mask, mmvqa_supcon_loss_masked replaces the
+unmasked loss) against the same fed step without it, alternating blocks in one process; plus the GPU time of the mask
+launch and of the masked loss (forward + gradient) next to the unmasked loss, alone on an idle device.
+
+    python tools/feeder_bench.py --config 4 --supcon_mask jaccard --out profiles/supcon_mask_cfg4.json
 """
 import argparse
 import json
@@ -63,6 +70,111 @@ def cpu_seconds(pid):
         return 0.0
 
 
+def mask_bench(a, dev, tmp, model, opt, red, tok, fd, T_):
+    """fed config-4 step with / without the Jaccard mask, and the two new launches alone"""
+    import mmvqa_amd
+    from mmvqa_amd import _lib as L
+    from mmvqa_amd import data as D
+    from mmvqa_amd.train import supcon_step
+    table = D.roco_supcon_table(tmp)
+    t0 = time.perf_counter()
+    host_words = D.WordSets.from_table(table)
+    words_ms = 1e3 * (time.perf_counter() - t0)
+    words = host_words.to(dev)
+    ds = D.RocoSupConDataset(table, tok, D.load_keywords(tmp), 5, T_, 0.15, seed=1, report_aug_col=True)
+    host = D.HostLoader(ds, B, shuffle=True, seed=1, num_workers=a.workers, aug=D.ROCO_AUG, size=HW, views=2)
+    fdm = D.DeviceFeeder(host, dev, depth=2, pairs=True)
+
+    def batches(feeder):
+        epoch = 0
+        while True:
+            feeder.set_epoch(epoch)
+            for b in feeder:
+                if b[0].shape[0] == 2 * B:
+                    yield b
+            epoch += 1
+
+    gens = {"unmasked": (batches(fd), None), "masked": (batches(fdm), words)}
+
+    def run(n, kind):
+        g, w = gens[kind]
+        for _ in range(n):
+            _, _, stats = supcon_step(model, opt, red, 1, next(g), words=w)
+            stats.tolist()                       # the per-step host sync of train.py
+    for kind in gens:
+        run(a.warmup, kind)
+    torch.cuda.synchronize()
+    res = {k: [] for k in gens}
+    for _ in range(a.blocks):
+        for kind in gens:
+            t0 = time.perf_counter()
+            run(a.steps, kind)
+            torch.cuda.synchronize()
+            res[kind].append(1e3 * (time.perf_counter() - t0) / a.steps)
+            print(f"{kind:9s} {res[kind][-1]:.2f} ms/step", flush=True)
+
+    # the launches alone: the stream is held behind a ~20 ms matmul block so that the host side of the calls is done
+    # before the GPU reaches e0 (the method of augment_gpu_ms_per_batch)
+    s = torch.cuda.Stream()
+    m = torch.randn(4096, 4096, device=dev)
+    mo = torch.empty_like(m)
+    lib, Dm = L.lib(), 128
+    alone = {}
+    for n in (16, 128):                          # one GPU's 16 pairs; the gathered set of 8 GPUs
+        g = torch.Generator().manual_seed(n)
+        f = torch.nn.functional.normalize(torch.randn(2 * n, Dm, generator=g), dim=1).to(dev)
+        rows = torch.randint(0, len(table), (n,), generator=g).to(torch.int32).to(dev)
+        cols = torch.randint(1, 4, (n,), generator=g).to(torch.int32).to(dev)
+        zero = torch.zeros_like(cols)
+        mask = torch.empty(n, n, device=dev)
+        loss, df, ws = torch.empty(1, device=dev), torch.empty_like(f), torch.empty(6 * n, device=dev)
+        sp = s.cuda_stream
+        calls = {
+            "jaccard_mask": lambda: lib.mmvqa_jaccard_mask(sp, L.ptr(words.offsets), L.ptr(words.ids), L.ptr(rows), L.ptr(zero),
+                                                           L.ptr(rows), L.ptr(cols), L.ptr(mask), n, words.rows),
+            "masked_loss_fwd_bwd": lambda: lib.mmvqa_supcon_loss_masked(sp, L.ptr(f), L.ptr(mask), L.ptr(loss), L.ptr(df),
+                                                                        L.ptr(ws), n, Dm, 0.07, 0.07, 1.0),
+            "unmasked_loss_fwd_bwd": lambda: lib.mmvqa_supcon_loss(sp, L.ptr(f), L.ptr(loss), L.ptr(df), L.ptr(ws), n, Dm,
+                                                                   0.07, 0.07, 1.0),
+        }
+        for key, call in calls.items():
+            ts = []
+            for r in range(a.aug_reps + 3):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                with torch.cuda.stream(s):
+                    for _ in range(12):
+                        torch.mm(m, m, out=mo)
+                e0.record(s)
+                L.check(call())
+                e1.record(s)
+                e1.synchronize()
+                if r >= 3:
+                    ts.append(e0.elapsed_time(e1))
+            alone[f"{key}_n{n}"] = round(statistics.median(ts), 4)
+    un, ma = statistics.median(res["unmasked"]), statistics.median(res["masked"])
+    spread = max(res["unmasked"]) - min(res["unmasked"])
+    out = dict(
+        workload="config 4 (tf_efficientnetv2_m + realformer + SupCon head, ROCO MLM + SupCon), 16 pairs = 32 views, 224^2, "
+                 f"T 32, one GPU, fed by a DeviceFeeder (depth 2, views 2) over {a.images} generated JPEGs; unmasked = "
+                 "supcon_step as train.py runs it without --supcon_mask (the launches of the default path); masked = "
+                 "--supcon_mask jaccard: feeder with pairs, mmvqa_jaccard_mask, mmvqa_supcon_loss_masked",
+        unmasked_ms_per_step=round(un, 3), masked_ms_per_step=round(ma, 3), ratio=round(ma / un, 4),
+        unmasked_block_spread_ms=round(spread, 3), masked_minus_unmasked_ms=round(ma - un, 3),
+        within_unmasked_spread=bool(ma - un <= spread),
+        blocks={k: [round(x, 3) for x in v] for k, v in res.items()}, steps_per_block=a.steps, workers=host.num_workers,
+        word_sets=dict(table_rows=host_words.rows, ids=int(host_words.ids.numel()), words=len(host_words.vocab),
+                       host_build_ms=round(words_ms, 3)),
+        gpu_ms_alone=dict(alone, D=Dm,
+                          method="cuda events around the launches of one C-ABI call, the stream held behind a ~20 ms matmul "
+                                 f"block so that the host side is done first; otherwise idle device, median of {a.aug_reps}; "
+                                 "the loss calls are forward + gradient + reduce (2N rows, D 128)"))
+    print(json.dumps(out))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", type=int, default=2, choices=[2, 4])
@@ -73,7 +185,11 @@ def main():
     ap.add_argument("--workers", type=int, default=None)
     ap.add_argument("--aug_reps", type=int, default=20)
     ap.add_argument("--out", type=str, default=None)
+    ap.add_argument("--supcon_mask", type=str, default="none", choices=["none", "jaccard"],
+                    help="jaccard (with --config 4): time the fed step with the Jaccard mask against the one without")
     a = ap.parse_args()
+    if a.supcon_mask != "none" and a.config != 4:
+        ap.error("--supcon_mask needs --config 4 (the SupCon step)")
 
     import mmvqa_amd
     from mmvqa_amd import data as D
@@ -121,6 +237,8 @@ def main():
         ds = D.RocoDataset(D.roco_table(tmp, "train"), tok, D.load_keywords(tmp), 5, T, 0.15, seed=1)
     host = D.HostLoader(ds, B, shuffle=True, seed=1, num_workers=a.workers, aug=D.ROCO_AUG, size=HW, views=views)
     fd = D.DeviceFeeder(host, dev, depth=2)
+    if a.supcon_mask == "jaccard":
+        return mask_bench(a, dev, tmp, model, opt, red, tok, fd, T)
 
     def fed_batches():
         epoch = 0
