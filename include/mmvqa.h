@@ -132,25 +132,25 @@ typedef struct mmvqa_gemm_desc {
                          taps that fall inside the image (mmvqa_pixmask); enables the uniform-tap weight-gradient loaders */
   float* sk_ws;       /* optional, KIND_FWD / KIND_DGRAD: scratch of sk_ws_floats floats.  With it a launch that has few
                          output tiles and a long contraction may split K over workgroups (splitk, or the launcher's /
-                         tuner's choice when splitk <= 0): partial tiles go to the scratch and a second launch sums them
-                         and applies the whole epilogue.  Needs splitk * M * N <= sk_ws_floats; one stream at a time. */
+                         tuner's choice when splitk <= 0): every workgroup of a tile writes its partial tile to the
+                         scratch.  With sk_cnt the split is ticketed: the workgroup of a tile that arrives last sums the
+                         partial tiles and applies the whole epilogue in the same kernel; without sk_cnt (or when the
+                         tickets or the scratch are too small for the ticketed layout) a second launch does that.  Needs
+                         splitk * M * N <= sk_ws_floats; one stream at a time. */
   long long sk_ws_floats;
   mmvqa_bn_fold a_fold; /* optional: the coefficients of the A prologue (a_pro AFFINE_RELU: scale/shift; DZ: P/Q/R) come
                            from raw sums instead of a_c0 / a_c1 / a_c2 (which may then be NULL) */
   int stat_slots;       /* replicas the statistics epilogue (stat1 / stat2) spreads its sums over; 0 = MMVQA_STAT_SLOTS */
-  int persist;          /* > 0: persistent ("stream-K") launch of that many workgroups, each walking an equal share of the
-                           launch's K-tile iterations; tiles cut over several workgroups are completed by the workgroup
-                           that arrives last.  Plain-epilogue products only; an accumulating product (c_atomic) needs
-                           nothing else, any other needs sk_ws (partial tiles) and sk_cnt (tickets).  0 = one workgroup
-                           per tile (and split).  The launcher falls back to that form when a condition is not met. */
-  unsigned int* sk_cnt; /* persist: sk_cnt_n arrival tickets, ZERO before the first launch; every launch leaves them zero */
+  int reserved1;        /* must be 0 (a non-zero value is refused; the field keeps the struct layout unchanged) */
+  unsigned int* sk_cnt; /* optional, with sk_ws: sk_cnt_n arrival tickets (one per 64x64 output tile at least) of the
+                           ticketed split-K, ZERO before the first launch; every launch leaves them zero */
   int sk_cnt_n;
   int reserved0;        /* operand precision (the field keeps its name so that the struct layout is unchanged):
                            MMVQA_PREC_F32 (0) = fp32 operands, v_mfma_f32_32x32x2_f32;
                            MMVQA_PREC_F16 (1) = both operands rounded to fp16 (nearest-even, bit-equal to
                            torch's .half()) where the loader writes them to LDS, v_mfma_f32_32x32x16_f16, fp32
                            accumulation and epilogue.  The f16 family has no SiLU / gate prologues (refused),
-                           no 8-wave variant (tile 5 runs as tile 3) and no persistent form (launched per tile). */
+                           and no 8-wave variant (tile 5 runs as tile 3). */
 } mmvqa_gemm_desc;
 
 #define MMVQA_PREC_F32 0
@@ -408,7 +408,7 @@ long long mmvqa_engine_nbt_count(const mmvqa_engine* e);
 /* plan for a batch geometry; returns workspace bytes needed (0 on error) */
 size_t mmvqa_engine_plan(mmvqa_engine* e, int B, int T, int img_h, int img_w);
 /* Borrowed buffers of the following forward / backward calls.  Part of the WORKSPACE holds state that must survive
- * between calls (tap-validity tables of the 3x3 weight gradients, the zeroed arrival tickets of persistent GEMM
+ * between calls (tap-validity tables of the 3x3 weight gradients, the zeroed arrival tickets of the split-K GEMM
  * launches): the first forward after a bind puts it in place on that call's stream; the caller must not write to the
  * workspace while it is bound (re-bind after any such write). */
 int mmvqa_engine_bind(mmvqa_engine* e, float* params, float* grads, float* bufs, long long* nbt, void* workspace,
@@ -446,8 +446,8 @@ int mmvqa_engine_set_grad_callback(mmvqa_engine* e, mmvqa_grad_cb cb, void* user
 /* per-shape kernel configuration: while enabled, every implicit-GEMM shape met for the first time in
  * forward/backward is timed over its candidate (tile, split-K) set and the fastest is kept for later
  * calls.  A pass run with tuning enabled is a throw-away pass (outputs/statistics are garbage).
- * Returns the number of tuned shapes so far (>= 0) or a negative error.  enable = 2 changes nothing and returns how many
- * of the tuned shapes run in the persistent form (mmvqa_gemm_desc.persist). */
+ * Returns the number of tuned shapes so far (>= 0) or a negative error.  enable is 0 or 1: any other value is
+ * refused with MMVQA_ERR_ARG and changes nothing. */
 int mmvqa_engine_tune(mmvqa_engine* e, int enable);
 /* operand precision of every implicit GEMM of the following forward / backward calls: MMVQA_PREC_F32 (default) or
  * MMVQA_PREC_F16 (mixed precision: both operands of each contraction rounded to fp16 nearest-even, fp32 accumulation;

@@ -54,7 +54,7 @@ class GemmDesc(C.Structure):
         ("stat2", c_ptr), ("Z2", c_ptr), ("z2_ld", C.c_int), ("mean2", c_ptr), ("invstd2", c_ptr),
         ("colsum", c_ptr), ("gate", c_ptr), ("gate_hw", C.c_int), ("mk_mode", C.c_int), ("pixmask", c_ptr),
         ("sk_ws", c_ptr), ("sk_ws_floats", C.c_longlong),
-        ("a_fold", BnFold), ("stat_slots", C.c_int), ("persist", C.c_int), ("sk_cnt", c_ptr), ("sk_cnt_n", C.c_int),
+        ("a_fold", BnFold), ("stat_slots", C.c_int), ("reserved1", C.c_int), ("sk_cnt", c_ptr), ("sk_cnt_n", C.c_int),
         ("reserved0", C.c_int),
     ]
 

@@ -349,11 +349,7 @@ int mmvqa_engine_set_precision(mmvqa_engine* e, int mode) {
 }
 int mmvqa_engine_tune(mmvqa_engine* e, int enable) {
   if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "tune: null engine");
-  if (enable == 2) {   // query: how many shapes run in the persistent form
-    int n = 0;
-    for (const auto& kv : e->tuner.table) n += kv.second.persist > 0;
-    return n;
-  }
+  if (enable != 0 && enable != 1) return mmvqa_set_error(MMVQA_ERR_ARG, "tune: enable=%d is neither 0 nor 1", enable);
   e->tuner.tuning = enable != 0;
   return (int)e->tuner.table.size();
 }

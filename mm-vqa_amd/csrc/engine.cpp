@@ -392,7 +392,7 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
   }
   e->vis = a.f((size_t)5 * B * H);
   for (int i = 0; i < 3; ++i) e->sk_ws[i] = a.f(SK_WS_FLOATS);   // split-K partial tiles (caller's / side / tap stream)
-  for (int i = 0; i < 3; ++i) e->sk_cnt[i] = a.f(SK_CNT_N);      // arrival tickets of ticketed / persistent launches
+  for (int i = 0; i < 3; ++i) e->sk_cnt[i] = a.f(SK_CNT_N);      // arrival tickets of ticketed split-K launches
   e->dvis = a.f((size_t)5 * B * H);
   e->du = a.f(max_tapM * H);
   for (int i = 0; i < 3; ++i) e->gbuf[i] = a.f(max_io);
@@ -1714,7 +1714,7 @@ static int heads_backward(mmvqa_engine* e, hipStream_t st, const float* h, const
 
 // --------------------------------------------------------------------------- whole model
 // State that lives in the caller's workspace ACROSS calls (mmvqa.h, mmvqa_engine_bind): the tap-validity tables of the
-// 3x3 weight gradients and the (zero) arrival tickets of the persistent launches.  Put in place on the caller's stream
+// 3x3 weight gradients and the (zero) arrival tickets of the ticketed split-K launches.  Put in place on the caller's stream
 // by the first forward after a bind, i.e. before the side stream exists for that workspace.
 static int prepare_workspace(mmvqa_engine* e, hipStream_t st) {
   if (e->ws_ready) return MMVQA_OK;

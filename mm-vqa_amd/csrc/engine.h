@@ -97,7 +97,7 @@ enum { HB_NONE = 0, HB_BN_ADD_RELU, HB_MAXPOOL_FWD, HB_MAXPOOL_BWD, HB_LAYERNORM
        HB_TAP_THIN_FWD, HB_TAP_THIN_BWD, HB_N };
 
 constexpr size_t SK_WS_FLOATS = (size_t)8 << 20;   // 32 MB: 8 splits of a 224-tile (64x64) product
-constexpr int SK_CNT_N = 16384;                    // tiles a persistent launch may have (one arrival ticket each)
+constexpr int SK_CNT_N = 16384;                    // tiles a ticketed split-K launch may have (one arrival ticket each)
 
 struct mmvqa_engine {
   mmvqa_model_desc d;
@@ -161,8 +161,8 @@ struct mmvqa_engine {
   // stream can launch a weight gradient (the workspace is the caller's: see mmvqa_engine_bind in mmvqa.h)
   struct PixGeom { int N, OH, OW, H, W, KH, stride, pad; size_t off; };
   std::map<std::string, PixGeom> pixmask_off;
-  bool ws_ready = false;                        // persistent workspace state (tables, tickets) is in place
-  size_t sk_cnt[3] = {0, 0, 0};                 // arrival tickets of ticketed / persistent launches (one set per stream)
+  bool ws_ready = false;                        // workspace state that persists across calls (tables, tickets) is in place
+  size_t sk_cnt[3] = {0, 0, 0};                 // arrival tickets of ticketed split-K launches (one set per stream)
   // ---- gradient-ready notifications (data-parallel overlap): called on the host right after the kernels that
   // complete grads[lo, hi) have been enqueued and the main stream has been ordered behind them
   void (*grad_cb)(void* user, long long lo, long long hi) = nullptr;

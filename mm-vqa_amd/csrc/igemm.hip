@@ -32,7 +32,7 @@
 // rows of R (+32) halves read with ds_read_b64_tr_b16.  Lane (r, h) feeds k = 16s + 8h + j in element j of K-step
 // s for both operands; the MFMA is v_mfma_f32_32x32x16_f16 with fp32 accumulation, whose C/D layout is that of
 // the fp32 form, so the epilogues, split-K and the ticketed fix-up are shared.  The K loop is the plain one with
-// two register stages (loads of tile t+2 in flight while tile t is multiplied); no 8-wave or persistent form.
+// two register stages (loads of tile t+2 in flight while tile t is multiplied); no 8-wave form.
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -49,18 +49,16 @@ struct GemmAux {
   float* part;   // split-K over workgroups with a finishing launch: partial tiles [split][M][N] go here, no epilogue
   int ldsc;      // the A-prologue coefficients are folded from raw BatchNorm sums into an LDS table in the setup phase
                  // (mmvqa_bn_fold) and the K loop reads them there
-  // persistent ("stream-K") form: the grid is sk_G workgroups, each walks a contiguous run of the launch's K-tile
-  // iterations (tiles x K-tiles per tile, tile-major), so that every workgroup does the same amount of matrix work
-  // whatever the tile count.  A tile whose K range is cut over several workgroups is completed by whichever of them
-  // arrives LAST (a ticket per tile; nobody waits): the others publish their partial tile to sk_part.
-  int sk_G;            // 0: one workgroup per (tile, split) as the grid says
+  // ticketed split-K (split over the grid's z WITHOUT a finishing launch): the sk_slots (= splits) workgroups of a tile
+  // publish their partial tiles to sk_part and draw a ticket each; the tile is completed by whichever of them arrives
+  // LAST (nobody waits): it sums the partial tiles and runs the epilogue.
+  int pad0;            // unused: keeps the kernel-argument offsets of the fields behind it (with sk_part 8 bytes lower the
+                       // compiler groups the argument loads differently and every kernel's register assignment shifts)
   int sk_gx, sk_gy;    // tile grid
-  int sk_slots;        // partial tiles a tile can receive (most contributors of one tile)
+  int sk_slots;        // partial tiles a tile receives (= splits)
   float* sk_part;      // [tile][sk_slots][BM*BN]
   unsigned* sk_cnt;    // [tile] arrival tickets, zero before and after every launch
-  int tick;            // split-K over the grid's z WITHOUT a finishing launch: the sk_slots (= splits) workgroups of a tile
-                       // publish their partial tiles to sk_part and draw tickets exactly as above; the last one sums and
-                       // runs the epilogue
+  int tick;            // 1: this launch is a ticketed split | 0: one workgroup per tile, or a split with a finishing launch (part)
   int xcd;       // workgroup ids are dealt round-robin to the 8 XCDs: renumber so that an XCD gets a CONTIGUOUS run of
                  // tiles (1: the N-tiles of an M-panel, 2: the M-tiles of an N-panel share that XCD's L2 instead of
                  // pulling the panel into up to 8 of them)
@@ -99,7 +97,7 @@ __device__ __forceinline__ void static_for(F&& f) {
 
 #define MAX_TAPS 32
 #define SC1_AUX 16       // cache-policy bits of the raw buffer builtins on gfx950: 1 = sc0, 2 = nt, 16 = sc1 (write-through / L1 bypass)
-#define SK_PART_MAX 8    // most contributors of one tile in the persistent form (host-checked)
+#define SK_PART_MAX 8    // most splits of one tile in the ticketed split-K (host-checked)
 #define TRY_RET(x) do { int r_ = (x); if (r_ != MMVQA_OK) return r_; } while (0)
 
 // Phase timestamps of every workgroup (tools/igemm_trace.py builds the library with -DIGEMM_TRACE):
@@ -326,15 +324,12 @@ __device__ __forceinline__ void general_epilogue(const GemmParams& p, int m0, in
 // KS = intra-workgroup split of every K-tile over KS groups of 4 waves (KS*256 threads): for problems
 // with fewer workgroups than CUs it doubles the waves per SIMD (latency hiding) at the price of one
 // LDS reduction at the end.
-// PERSIST: the persistent ("stream-K") form is its own instantiation -- the segment loop around the body invites the
-// compiler to hoist everything loop-invariant out of it and keep it in registers for the whole kernel (measured: 156 ->
-// 256 VGPRs with spills for the 64x64x32 forward tile); the one-workgroup-per-tile form must not pay for that.
-template <int BM, int BN, int BK, int KIND, bool NCHW, int KS, bool PERSIST = false, int PREC = MMVQA_PREC_F32>
+template <int BM, int BN, int BK, int KIND, bool NCHW, int KS, int PREC = MMVQA_PREC_F32>
 __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, const GemmAux x) {
   constexpr int NT = 256 * KS;
   constexpr int WM = BM / 2, WN = BN / 2, TM = WM / 32, TN = WN / 32;
   constexpr bool F16 = (PREC == MMVQA_PREC_F16);   // f16-operand family: halves in LDS, 32x32x16 MFMA
-  static_assert(!F16 || (KS == 1 && !PERSIST), "the f16 family has no 8-wave or persistent form");
+  static_assert(!F16 || KS == 1, "the f16 family has no 8-wave form");
   constexpr bool PIPE = TM * TN <= 2;         // slot-pipelined K loop (one or two 32x32 tiles per wave); else the plain loop
   constexpr int LDK = F16 ? BK + 8 : BK + 4;  // (f16: in halves, as LDA_KM / LDB_KM)
   constexpr int KQ = BK / 4;                 // float4 per row of a [row][k] tile
@@ -360,37 +355,14 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
   float* ctab = smem + 2 * A_TILE + 2 * B_TILE + MAX_TAPS;               // [3][channels]: folded BatchNorm coefficients
 
   // ------------------------------------------------------------------ work of this workgroup
-  constexpr bool persistent = PERSIST;
   const int nkt_total = (p.K + BK - 1) / BK;
   __shared__ int sk_last;
-  long long sk_it = 0, sk_end = 0;   // persistent: this workgroup's run of K-tile iterations [sk_it, sk_end)
-  unsigned sk_Lg = 0;
-  const unsigned long long sk_T = (unsigned long long)x.sk_gx * x.sk_gy * nkt_total;
-  if (persistent) {
-    // hardware id L runs on XCD L % 8: give every XCD a contiguous run of logical ids (neighbouring tiles share operands)
-    const unsigned L = blockIdx.x, G = (unsigned)x.sk_G, per = G >> 3;
-    sk_Lg = (x.xcd && L < 8u * per) ? (L & 7u) * per + (L >> 3) : L;
-    sk_it = (long long)((unsigned long long)sk_Lg * sk_T / G);
-    sk_end = (long long)((unsigned long long)(sk_Lg + 1) * sk_T / G);
-  }
-  for (bool sk_first = true;; sk_first = false) {
-  int tid = threadIdx.x;
-  if constexpr (persistent) asm volatile("" : "+v"(tid));   // per-thread state is rebuilt per segment, not hoisted and kept
+  const int tid = threadIdx.x;
   const int lane = tid & 63, wave = (tid >> 6) & 3, ks = tid >> 8;
   const int li = lane & 31, lh = lane >> 5;
   const int wm0 = (wave >> 1) * WM, wn0 = (wave & 1) * WN;
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-  int sk_tile = 0, sk_k0 = 0, sk_k1 = nkt_total;
-  if (persistent) {
-    if (sk_it >= sk_end) break;
-    sk_tile = (int)(sk_it / nkt_total);
-    sk_k0 = (int)(sk_it - (long long)sk_tile * nkt_total);
-    sk_k1 = (sk_end - sk_it < (long long)(nkt_total - sk_k0)) ? sk_k0 + (int)(sk_end - sk_it) : nkt_total;
-    sk_it += sk_k1 - sk_k0;
-    if (x.xcd == 2) { by = sk_tile % x.sk_gy; bx = sk_tile / x.sk_gy; } else { bx = sk_tile % x.sk_gx; by = sk_tile / x.sk_gx; }
-    bz = 0;
-    if (!sk_first) __syncthreads();   // the previous segment's epilogue is done with the shared memory
-  } else if (x.xcd) {
+  if (x.xcd) {
     // hardware id L goes to XCD L % 8; logical id Lg: XCD j owns the run [j*per, (j+1)*per), the < 8 ids past 8*per keep
     // their number.  xcd == 1: N-tiles of an M-panel are consecutive (they share operand A); 2: M-tiles of an N-panel are
     const unsigned gx = gridDim.x, gy = gridDim.y;
@@ -415,9 +387,9 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
   const int lm0 = m0, ln0 = n0;
 #endif
 
-  // K range of this split / segment
-  const int kt_begin = persistent ? sk_k0 : bz * p.ktiles_per_split;
-  int kt_end = persistent ? sk_k1 : kt_begin + p.ktiles_per_split;
+  // K range of this split
+  const int kt_begin = bz * p.ktiles_per_split;
+  int kt_end = kt_begin + p.ktiles_per_split;
   if (kt_end > nkt_total) kt_end = nkt_total;
   const int nkt = kt_end - kt_begin;
   const int k_begin = kt_begin * BK;
@@ -439,7 +411,7 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
   const int fold_C = A_ROWK ? p.g_Cs : BM;
   if (x.ldsc) {
     const BnFold& f = p.a_fold;
-    const bool pub = f.publish && (persistent ? (sk_Lg == 0 && sk_first) : (bx == 0 && by == 0 && bz == 0));
+    const bool pub = f.publish && bx == 0 && by == 0 && bz == 0;
     if constexpr (A_ROWK) {
       for (int c = tid; c < fold_C; c += NT) {
         float k0, k1, k2 = 0.f;
@@ -1419,22 +1391,13 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
     }
   };
 
-  if (persistent ? (!p.c_atomic && (sk_k0 != 0 || sk_k1 != nkt_total)) : (x.tick != 0)) {
-    // This workgroup covers only a part of its tile's K range (a cut segment of the persistent form, or one split of a
-    // ticketed split-K grid).  Every contributor publishes its partial tile (write-through stores, MI355X_MICROARCH
-    // "Valid forms": all stores of the handed-off bytes sc1, every storing wave drains them, a workgroup barrier, then
-    // ONE lane's agent-scope atomic) and draws a ticket; the contributor whose ticket is the last sums the partial
-    // tiles (sc1 loads; always in slot order, so the result does not depend on who came last) and runs the epilogue.
-    // Nobody waits for anybody.
-    int n_contrib, my, tile_id;
-    if (persistent) {
-      const unsigned long long G = (unsigned long long)x.sk_G;
-      const unsigned long long i0 = (unsigned long long)sk_tile * nkt_total, i1 = i0 + nkt_total - 1;
-      const int w_first = (int)(((i0 + 1) * G - 1) / sk_T), w_last = (int)(((i1 + 1) * G - 1) / sk_T);
-      n_contrib = w_last - w_first + 1; my = (int)sk_Lg - w_first; tile_id = sk_tile;
-    } else {
-      n_contrib = x.sk_slots; my = bz; tile_id = by * x.sk_gx + bx;
-    }
+  if (x.tick != 0) {
+    // This workgroup covers only a part of its tile's K range (one split of a ticketed split-K grid).  Every contributor
+    // publishes its partial tile (write-through stores, MI355X_MICROARCH "Valid forms": all stores of the handed-off
+    // bytes sc1, every storing wave drains them, a workgroup barrier, then ONE lane's agent-scope atomic) and draws a
+    // ticket; the contributor whose ticket is the last sums the partial tiles (sc1 loads; always in slot order, so the
+    // result does not depend on who came last) and runs the epilogue.  Nobody waits for anybody.
+    const int n_contrib = x.sk_slots, my = bz, tile_id = by * x.sk_gx + bx;
     constexpr int Q = BM * BN / 4;   // float4 of a tile
     __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)(x.sk_part + (size_t)tile_id * x.sk_slots * (BM * BN)), 0,
                                                                   x.sk_slots * BM * BN * 4, 0x00020000);
@@ -1455,7 +1418,6 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
     __syncthreads();
     if (!sk_last) {
       TRACE_MARK(4);
-      if (persistent) continue;
       return;
     }
     for (int i = tid; i < Q; i += NT) {
@@ -1486,7 +1448,7 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
       stv(P, (size_t)row * N + col, *reinterpret_cast<const f32x4*>(&ctile[rl * LDC + c4 * 4]));
     }
     TRACE_MARK(4);
-    return;   // (never with the persistent form: host-checked)
+    return;
   }
 
   if (p.c_atomic) {
@@ -1500,7 +1462,6 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
       if (row < M && cc < N) atomicAdd(&C[(size_t)row * ldc + cc], ctile[rl * LDC + cl]);
     }
     TRACE_MARK(4);
-    if (persistent) continue;   // partial or whole, a segment of an accumulating product just adds its tile
     return;
   }
 
@@ -1570,13 +1531,11 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
     return;
   }
 
-  general_epilogue<BM, BN, NT>(p, m0, n0, tid, smem, persistent ? by + bx * 7 : (int)(blockIdx.y + blockIdx.x * 7 + blockIdx.z * 3),
+  general_epilogue<BM, BN, NT>(p, m0, n0, tid, smem, (int)(blockIdx.y + blockIdx.x * 7 + blockIdx.z * 3),
                                [&](int rl, int cq) __attribute__((always_inline)) {
                                  return *reinterpret_cast<const f32x4*>(&ctile[rl * LDC + cq * 4]);
                                });
   TRACE_MARK(4);
-  if (!persistent) break;
-  }   // next segment
 }
 
 constexpr int FOLD_MAX_FLOATS = 3072;   // largest LDS table of folded BatchNorm coefficients (12 KB: 1024 channels x P, Q, R)
@@ -1646,7 +1605,7 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (!(attr_dev_mask >> (dev & 31) & 1)) {
-    HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<BM, BN, BK, KIND, NCHW, KS, false, PREC>,
+    HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<BM, BN, BK, KIND, NCHW, KS, PREC>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max));
     attr_dev_mask |= 1 << (dev & 31);
   }
@@ -1711,8 +1670,7 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
   }
   const size_t smem = ((tile_floats + fold_floats > epi_floats ? tile_floats + fold_floats : epi_floats)) * sizeof(float);
   dim3 grid((p.N + BN - 1) / BN, (p.M + BM - 1) / BM, p.splitk);
-  // persistent ("stream-K") form
-  x.sk_G = 0; x.sk_gx = (int)grid.x; x.sk_gy = (int)grid.y; x.sk_slots = 0; x.sk_part = nullptr; x.sk_cnt = nullptr; x.tick = 0;
+  x.pad0 = 0; x.sk_gx = (int)grid.x; x.sk_gy = (int)grid.y; x.sk_slots = 0; x.sk_part = nullptr; x.sk_cnt = nullptr; x.tick = 0;
   // split-K of a forward / data-gradient product: with the caller's tickets the last workgroup of a tile finishes it
   // (no second launch); MMVQA_SK_FINISH=1 keeps the finishing launch (A/B switch)
   static const bool finish_form = getenv("MMVQA_SK_FINISH") != nullptr;
@@ -1722,49 +1680,22 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
       x.tick = 1; x.part = nullptr; x.sk_slots = p.splitk; x.sk_part = p.sk_ws; x.sk_cnt = p.sk_cnt;
     }
   }
-  if (p.persist > 0 && PREC == MMVQA_PREC_F32 && !NCHW && BM == 64 && BN == 64 && p.epi_mode == EPI_PLAIN && !x.part && p.splitk == 1) {
-    const long long tiles = (long long)grid.x * grid.y, nkt = (p.K + BK - 1) / BK, T = tiles * nkt;
-    long long G = p.persist < T ? p.persist : T;
-    bool ok = G >= 8;
-    if (ok && !p.c_atomic) {
-      const long long per = T / G;                          // K-tile iterations per workgroup (at least)
-      const long long slots = (nkt + per - 1) / per + 1;    // a tile's K range meets at most this many runs
-      ok = slots <= SK_PART_MAX && p.sk_ws && p.sk_cnt && tiles <= p.sk_cnt_n &&
-           tiles * slots * (long long)(BM * BN) <= p.sk_ws_floats;
-      x.sk_slots = (int)slots; x.sk_part = p.sk_ws; x.sk_cnt = p.sk_cnt;
-    }
-    if (ok) { x.sk_G = (int)G; grid = dim3((unsigned)G, 1, 1); }
-  }
   static const int xcd_on = getenv("MMVQA_IGEMM_NOXCD") ? 0 : 1;   // A/B switch
   const long nwg = (long)grid.x * grid.y * grid.z;
   x.xcd = 0;
-  if (xcd_on && (nwg >= 32 || x.sk_G) && !NCHW) {
+  if (xcd_on && nwg >= 32 && !NCHW) {
     // bytes behind the row panels (A side) and the column panels (B side): keep the larger one XCD-local
     double a_bytes, b_bytes;
     if (KIND == KIND_WGRAD) { a_bytes = (double)p.K * p.M * (p.a_pro == PRO_DZ ? 2 : 1); b_bytes = (double)p.K * p.g_Cs; }
     else if (KIND == KIND_FWD) { a_bytes = (double)p.M * p.g_stride * p.g_stride * p.g_Cs; b_bytes = (double)p.N * p.K; }
     else { a_bytes = (double)p.M * p.g_Cs * (p.a_pro == PRO_DZ ? 2 : 1); b_bytes = (double)p.N * p.K; }
     x.xcd = (b_bytes > a_bytes && x.sk_gy > 1) ? 2 : (x.sk_gx > 1 ? 1 : 0);
-    if (x.sk_G && !x.xcd) x.xcd = 1;
   }
   if (getenv("MMVQA_IGEMM_LOG"))   // one line per launch: which loader family a shape gets (diagnostics)
-    fprintf(stderr, "igemm kind %d fast %d tile %dx%dx%d ks %d M %d N %d K %d Cs %d taps %d stride %d apro %d bpro %d splitk %d persist %d fold %d tick %d prec %s\n", KIND, x.fast,
-            BM, BN, BK, KS, p.M, p.N, p.K, p.g_Cs, p.g_KH * p.g_KW, p.g_stride, p.a_pro, p.b_pro, p.splitk, x.sk_G, x.ldsc, x.tick,
+    fprintf(stderr, "igemm kind %d fast %d tile %dx%dx%d ks %d M %d N %d K %d Cs %d taps %d stride %d apro %d bpro %d splitk %d fold %d tick %d prec %s\n", KIND, x.fast,
+            BM, BN, BK, KS, p.M, p.N, p.K, p.g_Cs, p.g_KH * p.g_KW, p.g_stride, p.a_pro, p.b_pro, p.splitk, x.ldsc, x.tick,
             PREC == MMVQA_PREC_F16 ? "f16" : "f32");
-  if constexpr (BM == 64 && BN == 64 && !NCHW && PREC == MMVQA_PREC_F32) {
-    if (x.sk_G) {
-      static int attr_dev_mask_p = 0;
-      if (!(attr_dev_mask_p >> (dev & 31) & 1)) {
-        HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<BM, BN, BK, KIND, NCHW, KS, true>,
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max));
-        attr_dev_mask_p |= 1 << (dev & 31);
-      }
-      hipLaunchKernelGGL((igemm_kernel<BM, BN, BK, KIND, NCHW, KS, true>), grid, dim3(256 * KS), smem, stream, p, x);
-      KERNEL_CHECK_RET();
-      return MMVQA_OK;
-    }
-  }
-  hipLaunchKernelGGL((igemm_kernel<BM, BN, BK, KIND, NCHW, KS, false, PREC>), grid, dim3(256 * KS), smem, stream, p, x);
+  hipLaunchKernelGGL((igemm_kernel<BM, BN, BK, KIND, NCHW, KS, PREC>), grid, dim3(256 * KS), smem, stream, p, x);
   KERNEL_CHECK_RET();
   if (x.part) {
     hipLaunchKernelGGL(splitk_finish_kernel, dim3((p.N + 63) / 64, (p.M + 63) / 64), dim3(256), 0, stream, p, x.part,
@@ -1813,6 +1744,7 @@ static int validate_desc(const GemmParams& p, int kind, int nchw) {
 #define BAD(...) return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: " __VA_ARGS__)
   if (kind < KIND_FWD || kind > KIND_WGRAD) BAD("unknown kind %d", kind);
   if (p.reserved0 != MMVQA_PREC_F32 && p.reserved0 != MMVQA_PREC_F16) BAD("unknown operand precision %d (reserved0)", p.reserved0);
+  if (p.reserved1 != 0) BAD("reserved1=%d must be 0 (the persistent form was removed)", p.reserved1);
   if (p.reserved0 == MMVQA_PREC_F16 && (p.a_pro == PRO_AFFINE_SILU || p.a_pro == PRO_SILU_GATE || p.b_pro == PRO_AFFINE_SILU ||
                                         p.b_pro == PRO_SILU_GATE || p.gate))
     BAD("the f16 operand family has no SiLU / gate prologues (a_pro %d, b_pro %d)", p.a_pro, p.b_pro);
@@ -1868,29 +1800,20 @@ int mmvqa_launch_igemm(GemmParams p, int kind, int nchw, int tile, hipStream_t s
   auto it = g_tuner->table.find(key);
   if (it == g_tuner->table.end()) {
     if (!g_tuner->tuning) return launch_one(p, kind, nchw, 0, stream);
-    struct Cand { int tile, splitk, persist; };
+    struct Cand { int tile, splitk; };
     std::vector<Cand> cands;
     const int tiles_f[] = {1, 2, 3, 4, 5, 6}, tiles_w[] = {1, 2, 3, 4, 5, 6};
-    static const bool persist_off = getenv("MMVQA_NO_PERSIST") != nullptr;   // A/B switch: no persistent candidates
-    // which products may take the persistent form: bit 0 forward / data gradient (caller's stream), bit 1 weight gradient;
-    // bit 2 (tests): a persistent candidate that ran wins its shape, so that a whole step runs in that form
-    const int persist_kinds = getenv("MMVQA_PERSIST_KINDS") ? atoi(getenv("MMVQA_PERSIST_KINDS")) : 0;   // (read per tuning pass: tests toggle it)
     if (kind == KIND_WGRAD && p.splitk <= 0) {
-      for (int t : tiles_w) for (int sk : {0, 1, 2, 3, 4, 6, 8, 12, 16}) cands.push_back({t, sk, 0});
-      // persistent form: an equal share of the K-tile iterations per workgroup, tiles accumulated with atomics as in any split
-      if (!persist_off && (persist_kinds & 2) && p.c_atomic && p.epi_mode == EPI_PLAIN)
-        for (int t : {3, 5, 6}) for (int g : {256, 512, 1024}) cands.push_back({t, 1, g});
+      for (int t : tiles_w) for (int sk : {0, 1, 2, 3, 4, 6, 8, 12, 16}) cands.push_back({t, sk});
     } else if (kind == KIND_WGRAD) {
-      for (int t : tiles_w) cands.push_back({t, p.splitk, 0});
+      for (int t : tiles_w) cands.push_back({t, p.splitk});
     } else if (sk_eligible(p, kind) && p.splitk <= 0 && (long)cdiv(p.M, 64) * cdiv(p.N, 64) <= 320) {
       // few output tiles: also try K split over workgroups with a finishing launch (needs the caller's scratch)
-      for (int t : {3, 5, 6}) for (int sk : {1, 2, 3, 4, 6, 8}) cands.push_back({t, sk, 0});
-      for (int t : {1, 2, 4}) cands.push_back({t, 1, 0});
+      for (int t : {3, 5, 6}) for (int sk : {1, 2, 3, 4, 6, 8}) cands.push_back({t, sk});
+      for (int t : {1, 2, 4}) cands.push_back({t, 1});
     } else {
-      for (int t : tiles_f) cands.push_back({t, p.splitk, 0});
+      for (int t : tiles_f) cands.push_back({t, p.splitk});
     }
-    if (!persist_off && (persist_kinds & 1) && kind != KIND_WGRAD && sk_eligible(p, kind) && p.sk_cnt && p.splitk <= 0)
-      for (int t : {3, 5, 6}) for (int g : {256, 512}) cands.push_back({t, 1, g});
     hipEvent_t e0, e1;
     HIP_CHECK_RET(hipEventCreate(&e0));
     HIP_CHECK_RET(hipEventCreate(&e1));
@@ -1902,7 +1825,6 @@ int mmvqa_launch_igemm(GemmParams p, int kind, int nchw, int tile, hipStream_t s
     for (const Cand& c : cands) {
       GemmParams q = p;
       q.splitk = c.splitk;
-      q.persist = c.persist;
       int r = launch_one(q, kind, nchw, c.tile, stream);  // warm-up (also sets the LDS attribute)
       if (r != MMVQA_OK) continue;
       // best of `tune_reps` batches of three launches (one batch left the choice between near-equal candidates to
@@ -1918,19 +1840,17 @@ int mmvqa_launch_igemm(GemmParams p, int kind, int nchw, int tile, hipStream_t s
         HIP_CHECK_RET(hipEventElapsedTime(&t, e0, e1));
         if (t < ms) ms = t;
       }
-      if (c.persist && (persist_kinds & 4)) ms *= 1e-3f;
       if (ms < best) { best = ms; bc = c; }
-      if (c.splitk <= 1 && !c.persist && ms < best_single) { best_single = ms; bc_single = c; }
+      if (c.splitk <= 1 && ms < best_single) { best_single = ms; bc_single = c; }
     }
     // K split with a finishing launch is timed here on an empty chip; inside the step it costs a second launch on the
     // dependency chain and takes the CUs the other stream would use: only worth it when clearly faster
     if (sk_partial && bc.splitk > 1 && best_single < 1e29f && best > sk_gain * best_single) { bc = bc_single; best = best_single; }
     hipEventDestroy(e0);
     hipEventDestroy(e1);
-    it = g_tuner->table.emplace(key, IgemmChoice{bc.tile, bc.splitk, bc.persist}).first;
+    it = g_tuner->table.emplace(key, IgemmChoice{bc.tile, bc.splitk}).first;
   }
   p.splitk = it->second.splitk;
-  p.persist = it->second.persist;
   return launch_one(p, kind, nchw, it->second.tile, stream);
 }
 
@@ -1956,18 +1876,11 @@ static int launch_one(GemmParams p, int kind, int nchw, int tile, hipStream_t st
   }
   if (nchw) tile = (kind == KIND_FWD) ? 2 : 3;
   const bool f16 = p.reserved0 == MMVQA_PREC_F16;
-  if (f16) {   // the f16 family has no 8-wave variant and no persistent form
-    if (tile == 5) tile = 3;
-    p.persist = 0;
-  }
+  if (f16 && tile == 5) tile = 3;   // the f16 family has no 8-wave variant
   const int bm = (tile == 1 || tile == 2) ? 128 : 64;
   const int bn = (tile == 1 || tile == 4) ? 128 : 64;
   const int bk = ((tile == 3 || tile == 5) && !nchw) ? 64 : 32;
   const int nkt = cdiv(p.K, bk);
-  if (p.persist > 0) {
-    // persistent form: the workgroups share the K-tile iterations themselves, no split of the grid
-    if (nchw || p.epi_mode != EPI_PLAIN) p.persist = 0; else p.splitk = 1;
-  }
   if (p.splitk <= 0) {
     p.splitk = 1;
     if (kind == KIND_WGRAD) {

@@ -7,7 +7,7 @@
 #include <utility>
 
 // per-shape (tile, split-K) choices of the implicit-GEMM launcher; see igemm.hip
-struct IgemmChoice { int tile, splitk, persist; };   // persist: workgroups of the persistent ("stream-K") form, 0 = off
+struct IgemmChoice { int tile, splitk; };
 struct IgemmTuner {
   bool tuning = false;
   std::unordered_map<std::string, IgemmChoice> table;

@@ -456,10 +456,6 @@ class Model(nn.Module):
         L.check(L.lib().mmvqa_engine_set_grad_callback(self._handle, C.cast(self._cb, C.c_void_p), None))
 
     # ------------------------------------------------------------------ per-shape kernel tuning
-    def tuned_persistent(self):
-        """how many of the tuned GEMM shapes run in the persistent (stream-K) form"""
-        return int(L.lib().mmvqa_engine_tune(self._handle, 2))
-
     def tune(self, img, input_ids, segment_ids, input_mask):
         """Time the candidate tile / split-K configurations of every GEMM shape of one training step
         (forward + backward on the given batch) and keep the fastest.  Parameters, BatchNorm buffers

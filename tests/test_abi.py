@@ -89,6 +89,9 @@ def test_igemm_refuses_inconsistent_descriptors():
     refused(d, L.KIND_DGRAD, "dact without Pre")
     d = desc(); d.drop_p = 1.5
     refused(d, L.KIND_FWD, "dropout p")
+    d = desc(); d.reserved1 = 256              # the slot that selected the removed persistent form
+    refused(d, L.KIND_FWD, "non-zero reserved1")
+    assert b"persistent form was removed" in lib.mmvqa_last_error()
     refused(desc(), 7, "unknown kind")
 
 
@@ -134,6 +137,11 @@ def test_model_protocol_on_cpu():
         mmvqa_amd.Model(O.make_args(transformer_model="lstm"))
     with pytest.raises(NotImplementedError):
         mmvqa_amd.Model(O.make_args(cnn_encoder="vgg16"))
+    # mmvqa_engine_tune: 0 / 1 switch the tuning pass, anything else (2 was a query once) is refused and changes nothing
+    from mmvqa_amd import _lib as L
+    lib = L.lib()
+    assert lib.mmvqa_engine_tune(m._handle, 2) == -1 and b"tune:" in lib.mmvqa_last_error()
+    assert lib.mmvqa_engine_tune(m._handle, 0) == 0
     with pytest.raises(mmvqa_amd.MMVQAError):
         m(torch.zeros(1, 3, 32, 32), torch.zeros(1, 8, dtype=torch.long), torch.zeros(1, 8, dtype=torch.long),
           torch.ones(1, 8, dtype=torch.long))

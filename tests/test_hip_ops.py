@@ -473,92 +473,6 @@ def test_bn_coef_and_add_relu():
     assert int(nbt) == 6
 
 
-PERSIST = [  # (N, H, W, Cin, Cout, K, stride, pad), tile, workgroups
-    ((2, 14, 14, 128, 192, 3, 1, 1), 3, 16), ((2, 14, 14, 128, 192, 3, 1, 1), 5, 29), ((2, 14, 14, 128, 192, 3, 1, 1), 6, 64),
-    ((3, 9, 9, 256, 72, 1, 1, 0), 5, 11), ((2, 12, 12, 64, 128, 3, 2, 1), 6, 37), ((2, 10, 10, 128, 64, 1, 1, 0), 3, 8),
-    ((1, 7, 7, 192, 200, 3, 1, 1), 5, 256),
-]
-
-
-@pytest.mark.parametrize("cfg,tile,G", PERSIST)
-def test_conv_persistent_form(cfg, tile, G):
-    """mmvqa_gemm_desc.persist: G workgroups walk equal shares of the launch's K-tile iterations; tiles whose K range is
-    cut over several workgroups are completed by the last arriver (tickets + partial tiles in sk_ws), accumulating
-    products just add.  Grids that do not divide (G = 29, 37, 11 ...), more workgroups than tiles, the fused BatchNorm
-    prologues / statistics epilogues and the folded coefficients all go through it; results against torch and against
-    the one-workgroup-per-tile launch; the tickets must read zero afterwards (the next launch relies on it)."""
-    N, H, W, Cin, Cout, K, s, p = cfg
-    torch.manual_seed(21)
-    x_raw = torch.randn(N, Cin, H, W)
-    sc, sh = torch.rand(Cin) + 0.5, torch.randn(Cin) * 0.3
-    w = torch.randn(Cout, Cin, K, K) / math.sqrt(Cin * K * K)
-    a = torch.relu(x_raw * sc[None, :, None, None] + sh[None, :, None, None]).requires_grad_(True)
-    wr = w.clone().requires_grad_(True)
-    z_ref = F.conv2d(a, wr, stride=s, padding=p)
-    OH, OW = z_ref.shape[2:]
-    xd, wd, scd, shd = nhwc(x_raw), w_ohwi(w), sc.to(dev()), sh.to(dev())
-    ws = torch.zeros(8 << 20, device=dev())
-    cnt = torch.zeros(4096, dtype=torch.int32, device=dev())
-
-    def fwd(persist):
-        z = torch.zeros(N * OH * OW, Cout, device=dev())
-        stat = torch.zeros(L.STAT_SLOTS, Cout, 2, dtype=torch.float64, device=dev())
-        d, _, _ = conv_desc_fwd(xd, wd, N, H, W, Cin, Cout, K, s, p, z)
-        d.a_pro, d.a_c0, d.a_c1 = L.PRO_AFFINE_RELU, P(scd), P(shd)
-        d.stat1, d.stat_bwd, d.stat_slots = P(stat), 0, 4
-        d.sk_ws, d.sk_ws_floats, d.sk_cnt, d.sk_cnt_n, d.persist, d.splitk = P(ws), ws.numel(), P(cnt), cnt.numel(), persist, 1
-        run_igemm(d, L.KIND_FWD, tile=tile)
-        assert float(stat[4:].abs().sum()) == 0.0 and float(stat[:4].abs().sum()) > 0.0   # stat_slots = 4: replicas 0..3 only
-        return z, stat.sum(0).cpu()
-
-    z0, st0 = fwd(0)
-    z1, st1 = fwd(G)
-    assert int(cnt.abs().sum()) == 0, "tickets not back to zero"
-    assert_close(from_nhwc(z1, N, OH, OW, Cout), z_ref, TOL, "persistent forward vs torch")
-    assert_close(z1, z0, 2e-6, "persistent vs one workgroup per tile")
-    assert_close(st1[:, 0], st0[:, 0], 1e-6, "sum")
-    assert_close(st1[:, 1], (z_ref.double() ** 2).sum(dim=(0, 2, 3)), 1e-5, "sumsq")
-    # data gradient with the BatchNorm-backward prologue, ReLU mask and backward statistics
-    Gr = torch.randn_like(z_ref)
-    Pc, Qc, Rc = torch.rand(Cout) + 0.5, torch.randn(Cout) * 0.1, torch.randn(Cout) * 0.1
-    dz = Gr * Pc[None, :, None, None] + z_ref.detach() * Qc[None, :, None, None] + Rc[None, :, None, None]
-    z_ref.backward(dz)
-    Gd, coef = nhwc(Gr), [t.to(dev()) for t in (Pc, Qc, Rc)]
-    mu, istd = (torch.randn(Cin) * 0.1).to(dev()), (torch.rand(Cin) + 0.5).to(dev())
-
-    def dgrad(persist):
-        dx = torch.zeros(N * H * W, Cin, device=dev())
-        bst = torch.zeros(L.STAT_SLOTS, Cin, 2, dtype=torch.float64, device=dev())
-        d = conv_desc_dgrad(Gd, wd, N, H, W, Cin, Cout, K, s, p, dx)
-        d.A2, d.a_pro, d.a_c0, d.a_c1, d.a_c2 = P(z0), L.PRO_DZ, P(coef[0]), P(coef[1]), P(coef[2])
-        d.Mk, d.mk_ld, d.mk_s, d.mk_b = P(xd), Cin, P(scd), P(shd)
-        d.stat1, d.stat_bwd, d.Z1, d.z1_ld, d.mean1, d.invstd1 = P(bst), 1, P(xd), Cin, P(mu), P(istd)
-        d.sk_ws, d.sk_ws_floats, d.sk_cnt, d.sk_cnt_n, d.persist, d.splitk = P(ws), ws.numel(), P(cnt), cnt.numel(), persist, 1
-        run_igemm(d, L.KIND_DGRAD, tile=tile)
-        return dx, bst.sum(0).cpu()
-
-    dx0, b0 = dgrad(0)
-    dx1, b1 = dgrad(G)
-    assert int(cnt.abs().sum()) == 0
-    mask = (x_raw * sc[None, :, None, None] + sh[None, :, None, None] > 0).float()
-    assert_close(from_nhwc(dx1, N, H, W, Cin), a.grad * mask, TOL, "persistent dgrad vs torch")
-    assert_close(dx1, dx0, 2e-6, "persistent dgrad vs one workgroup per tile")
-    assert_close(b1, b0, 1e-6, "backward statistics")
-
-    def wgrad(persist):
-        dw = torch.zeros(Cout, K * K * Cin, device=dev())
-        d = conv_desc_wgrad(Gd, xd, N, H, W, Cin, Cout, K, s, p, dw)
-        d.A2, d.a_pro, d.a_c0, d.a_c1, d.a_c2 = P(z0), L.PRO_DZ, P(coef[0]), P(coef[1]), P(coef[2])
-        d.b_pro, d.b_c0, d.b_c1 = L.PRO_AFFINE_RELU, P(scd), P(shd)
-        d.persist, d.splitk = persist, 1
-        run_igemm(d, L.KIND_WGRAD, tile=tile)
-        return dw
-
-    dw1 = wgrad(G)
-    assert_close(dw1.view(Cout, K, K, Cin).permute(0, 3, 1, 2), wr.grad, TOL, "persistent wgrad vs torch")
-    assert_close(dw1, wgrad(0), 1e-5, "persistent wgrad vs split grid")
-
-
 def _spread(sums, slots):
     """per-channel (sum, sum2) pairs scattered over the first `slots` statistic replicas, as the producers' atomics leave them"""
     Cc = sums.shape[0]

@@ -1,5 +1,5 @@
 # Same-box A/B of bench.py under environment switches: alternating runs, REPS repetitions.
-#   REPS=4 bash tools/rehearse/ab_bench.sh "MMVQA_X=1" "MMVQA_NO_BN_FOLD=1" ["MMVQA_PERSIST_KINDS=3" ...]
+#   REPS=4 bash tools/rehearse/ab_bench.sh "MMVQA_X=1" "MMVQA_NO_BN_FOLD=1" ["MMVQA_SK_FINISH=1" ...]
 # (MMVQA_X=1 is a no-op variable: the default build.)  Run it through gpurun; results also land in gpurun_out/ab/.
 set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "${GRAFT_STAGE:-${GRAFT_REPO_ROOT:?}}"
