@@ -386,6 +386,9 @@ int mmvqa_amp_update_scale(mmvqa_stream_t s, float* scale, int* growth_tracker, 
 int mmvqa_axpy(mmvqa_stream_t s, float* y, const float* x, float a, long n);
 int mmvqa_colsum(mmvqa_stream_t s, const float* x, int ld, int rows, int cols, float* out);
 int mmvqa_dropout(mmvqa_stream_t s, float* x, long n, float p, uint32_t seed);
+/* y = dropout(x), x untouched: the form the engine's backward pass runs on the gradient of a residual branch, with the
+ * (seed, linear index) stream of the forward epilogue that dropped the branch */
+int mmvqa_dropout_copy(mmvqa_stream_t s, const float* x, float* y, long n, float p, uint32_t seed);
 /* out[n*OH*OW + oy*OW + ox] = bit (kh*KW + kw) set iff input pixel (oy*stride - pad + kh, ox*stride - pad + kw) lies
  * inside the SH x SW image: the zero-padding pattern of torch.nn.Conv2d (torchvision Bottleneck.conv2), as consumed
  * by mmvqa_gemm_desc.pixmask */

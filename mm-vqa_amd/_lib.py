@@ -156,6 +156,7 @@ SIGNATURES = {
     "mmvqa_axpy": (_i, [_P, _P, _P, _f, _l]),
     "mmvqa_colsum": (_i, [_P, _P, _i, _i, _i, _P]),
     "mmvqa_dropout": (_i, [_P, _P, _l, _f, _u32]),
+    "mmvqa_dropout_copy": (_i, [_P, _P, _P, _l, _f, _u32]),
     "mmvqa_pixmask": (_i, [_P, _P] + [_i] * 9),
     "mmvqa_sizeof_resample_job": (_sz, []),
     "mmvqa_resample_coeffs": (_i, [_i, _d, _d, _i, _P, _P, _i]),

@@ -257,6 +257,9 @@ int mmvqa_colsum(mmvqa_stream_t s, const float* x, int ld, int rows, int cols, f
 int mmvqa_dropout(mmvqa_stream_t s, float* x, long n, float p, uint32_t seed) {
   return k_dropout(ST(s), x, n, p, seed);
 }
+int mmvqa_dropout_copy(mmvqa_stream_t s, const float* x, float* y, long n, float p, uint32_t seed) {
+  return k_dropout_copy(ST(s), x, y, n, p, seed);
+}
 
 int mmvqa_pixmask(mmvqa_stream_t s, int* out, int N, int OH, int OW, int SH, int SW, int KH, int KW, int stride,
                   int pad) {

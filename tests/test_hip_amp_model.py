@@ -12,6 +12,7 @@ import mmvqa_amd  # noqa: E402
 from mmvqa_amd import synth  # noqa: E402
 from oracle import mmbert_oracle as O  # noqa: E402
 from hip_helpers import dev, relerr  # noqa: E402
+from dropout_helpers import engine_seed  # noqa: E402
 from test_hip_model import build_pair, mini_args, oracle_loss  # noqa: E402
 
 
@@ -69,13 +70,14 @@ def emulate_f16(model):
     return model
 
 
-def run_mixed_case(args, B, T, hw, kind, seed=31, tune=False):
+def run_mixed_case(args, B, T, hw, kind, seed=31, tune=False, dropout_seed=None):
     """HIP mixed step (forward + loss + backward under fp16 autocast) against the emulating oracle in fp64: logits (and
     SupCon features), loss, every parameter gradient and the BatchNorm running statistics, each within
     max(1e-3, 5 x the fp32 emulating oracle's own distance from fp64) -- the rule of the fp32 parity tests.
-    tune="both": the default launch choices and the tuned ones (Model.tune under autocast) against one oracle run."""
+    tune="both": the default launch choices and the tuned ones (Model.tune under autocast) against one oracle run.
+    dropout_seed: training-mode dropout, the oracle under the engine's own masks (test_hip_model.run_case)."""
     import copy
-    orc, hip = build_pair(args, seed)
+    orc, hip = build_pair(args, seed, dropout_seed)
     init_sd = {k: v.detach().clone() for k, v in orc.state_dict().items()}
     orc.train()
     o64 = emulate_f16(copy.deepcopy(orc).double().train())
@@ -108,7 +110,11 @@ def run_mixed_case(args, B, T, hw, kind, seed=31, tune=False):
         with torch.autocast("cuda", dtype=torch.float16):
             if tuned:
                 assert hip.tune(dimg, dids, dseg, dmask) > 20
+            if dropout_seed is not None:
+                hip.set_seed(dropout_seed)
             out = hip(dimg, dids, dseg, dmask)
+            if dropout_seed is not None:   # the oracle's masks and the engine's come from one base seed
+                assert hip._seed_ctr == engine_seed(dropout_seed), (hip._seed_ctr, engine_seed(dropout_seed))
             if kind == "vqa":
                 logits, lr32, lr64 = out[0], ref[0], ref64[0]
                 loss = mmvqa_amd.asl_loss(logits, dtgt)
@@ -144,6 +150,12 @@ def run_mixed_case(args, B, T, hw, kind, seed=31, tune=False):
 @pytest.mark.parametrize("tm", ["transformer", "realformer"])
 def test_mixed_step_mlm(tm):
     run_mixed_case(mini_args(transformer_model=tm), B=3, T=12, hw=32, kind="mlm", tune="both")
+
+
+def test_mixed_step_mlm_dropout():
+    """the f16 epilogues and the unfused attention route under dropout (hidden 0.3, embeddings 0.1)"""
+    run_mixed_case(mini_args(hidden_dropout_prob=0.3, emb_dropout_prob=0.1, rf_dropout_prob=0.1), B=3, T=12, hw=32,
+                   kind="mlm", tune="both", dropout_seed=14)
 
 
 def test_mixed_step_mlm_supcon():

@@ -14,6 +14,7 @@ import mmvqa_amd  # noqa: E402
 from mmvqa_amd import synth  # noqa: E402
 from oracle import mmbert_oracle as O  # noqa: E402
 from hip_helpers import dev, relerr  # noqa: E402
+from dropout_helpers import engine_seed, inject_dropout  # noqa: E402
 from test_oracle_golden import MODEL_CASES, model_case_args  # noqa: E402
 
 TOL = 1e-3
@@ -32,8 +33,10 @@ def mini_args(**kw):
     return O.make_args(**d)
 
 
-def build_oracle(args, seed=0):
-    """the CPU oracle of a parity case: seeded weights, randomised BatchNorm / LayerNorm affine and running statistics"""
+def build_oracle(args, seed=0, dropout_seed=None):
+    """the CPU oracle of a parity case: seeded weights, randomised BatchNorm / LayerNorm affine and running statistics.
+    Dropout is off, or (dropout_seed given) every nn.Dropout draws the masks the engine draws in the first forward
+    after Model.set_seed(dropout_seed)"""
     torch.manual_seed(seed)
     oargs = O.make_args(**{**vars(args), "vocab_size": args.vocab_size})
     orc = O.OracleModel(oargs)
@@ -48,12 +51,15 @@ def build_oracle(args, seed=0):
             if isinstance(m, torch.nn.LayerNorm):
                 m.weight.uniform_(0.5, 1.5)
                 m.bias.normal_(0, 0.2)
-    zero_dropout(orc)
+    if dropout_seed is None:
+        zero_dropout(orc)
+    else:
+        inject_dropout(orc, engine_seed(dropout_seed))
     return orc
 
 
-def build_pair(args, seed=0):
-    orc = build_oracle(args, seed)
+def build_pair(args, seed=0, dropout_seed=None):
+    orc = build_oracle(args, seed, dropout_seed)
     hip = mmvqa_amd.Model(args)
     hip.load_state_dict(orc.state_dict())
     hip.to(dev())
@@ -94,12 +100,14 @@ def oracle_loss(kind, out, tgt, B):
     return O.mlm_loss(out, tgt)[0]
 
 
-def run_case(args, B, T, hw, kind, seed=0, stat_tol=1e-4, tune=False):
-    """tune=True: the launcher's timed per-shape choices (tile, split-K, K split + finishing launch) are
+def run_case(args, B, T, hw, kind, seed=0, stat_tol=1e-4, tune=False, dropout_seed=None):
+    """dropout_seed: training-mode dropout with the probabilities of `args`; the oracle applies the engine's own masks
+    (dropout_helpers.inject_dropout), so every assertion below holds as it does without dropout.
+    tune=True: the launcher's timed per-shape choices (tile, split-K, K split + finishing launch) are
     made first -- Model.tune() on the case's own inputs, as bench.py and train.py do -- so that the kernels compared
     with the oracle are the ones the timed steps run.  tune="both": the default launch choices AND the tuned ones against
     ONE evaluation of the CPU oracle (fp32 and fp64: the expensive part of a full-size case)."""
-    orc, hip = build_pair(args, seed)
+    orc, hip = build_pair(args, seed, dropout_seed)
     V = args.vocab_size
     if kind == "vqa":
         img, ids, seg, mask, tgt = synth.vqa_batch(B, T, hw, vocab=args.emb_vocab, n_classes=V, seed=5)
@@ -125,7 +133,11 @@ def run_case(args, B, T, hw, kind, seed=0, stat_tol=1e-4, tune=False):
             n = hip.tune(dimg, dids, dseg, dmask)
             assert n > 20, n
         what = "tuned launches: " if tuned else ""
+        if dropout_seed is not None:
+            hip.set_seed(dropout_seed)   # (after tune(): its throw-away forward advanced the stream)
         out = hip(dimg, dids, dseg, dmask)
+        if dropout_seed is not None:   # the base seed the oracle's masks were drawn from is the one the engine received
+            assert hip._seed_ctr == engine_seed(dropout_seed), (hip._seed_ctr, engine_seed(dropout_seed))
         if kind == "vqa":
             assert out[1] == 0 and out[2] == 0
             logits, logits_ref = out[0], out_ref[0]
@@ -161,6 +173,30 @@ def test_mlm_mini(tm):
 
 def test_mlm_supcon_mini():
     run_case(mini_args(transformer_model="realformer", supcon=True), B=4, T=11, hw=32, kind="supcon")
+
+
+# the reference's default probabilities (BertLayer attention / residual 0.3, embeddings 0.1, RealFormer 0.1)
+DROPOUT = dict(hidden_dropout_prob=0.3, emb_dropout_prob=0.1, rf_dropout_prob=0.1)
+
+
+@pytest.mark.parametrize("tm", ["transformer", "realformer"])
+def test_mlm_mini_dropout(tm):
+    """test_mlm_mini in training mode with dropout at every site: logits, loss and every gradient against the oracle
+    under the same masks.  A forward / backward pair that disagrees on a site seed, or a mask read in another layout,
+    moves a gradient by a few percent of its norm -- far outside compare_grads' tolerance"""
+    run_case(mini_args(transformer_model=tm, **DROPOUT), B=3, T=12, hw=32, kind="mlm", dropout_seed=11)
+
+
+def test_mlm_dropout_fused_qkv_tuned():
+    """T = 32 and head dimension 64: the fused QKV + attention launch draws site 0; hidden 768 gives proj / fc2 the
+    contractions (768, 3072) of the full model over few output tiles, so the tuner's tiles and split-K forms reach the
+    dropout epilogues"""
+    run_case(mini_args(hidden_size=768, heads=12, **DROPOUT), B=3, T=32, hw=32, kind="mlm", tune=True, dropout_seed=12)
+
+
+def test_mlm_supcon_mini_dropout():
+    run_case(mini_args(transformer_model="realformer", supcon=True, **DROPOUT), B=4, T=11, hw=32, kind="supcon",
+             dropout_seed=13)
 
 
 @pytest.mark.parametrize("tm", ["transformer", "realformer"])
