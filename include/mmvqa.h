@@ -304,6 +304,28 @@ int mmvqa_supcon_loss_masked(mmvqa_stream_t s, const float* f, const float* mask
  * or column outside the table gives NaN in the entries it touches.  All pointers are device pointers. */
 int mmvqa_jaccard_mask(mmvqa_stream_t s, const int* offsets, const int* ids, const int* rowsA, const int* colsA,
                        const int* rowsB, const int* colsB, float* mask, int n, int table_rows);
+/* Soft-target cross entropy over logits [rows][C] (leading dimension ld), forward AND backward in one launch, plus a
+ * one-workgroup launch for the mean; the criteria vqamed2019/train.py:164-174 selects with --smoothing:
+ *   mode 0 (MMVQA_SOFT_CE_HARD)      nn.CrossEntropyLoss, the eval branch (vqamed2019/utils.py:1261-1264)
+ *   mode 1 (MMVQA_SOFT_CE_UNIFORM)   LabelSmoothing (utils.py:178-200): soft_j = smoothing / C + (1 - smoothing) [j == t]
+ *   mode 2 (MMVQA_SOFT_CE_CATEGORY)  LabelSmoothByCategory, training branch (utils.py:1247-1260, 1296-1300):
+ *                                    soft = table[category[row]] with soft_t OVERWRITTEN by 1 - smoothing (:1254);
+ *                                    table [n_cat][table_ld] fp32 is computeCategoryTensors' (:1266-1293)
+ * row_loss[r] = sum_j soft_j (lse - x_j); *loss = mean over the rows, added in a fixed order (bit-equal from run to
+ * run); dlogits (nullable) [rows][dld] = (S p_j - soft_j) * gscale with S = sum_j soft_j (below 1 in mode 2 when t is
+ * in its category's set), p = softmax(x).  target / category are int64 device arrays [rows]; category and table are
+ * read in mode 2 only.  A target outside [0, C) or a category outside [0, n_cat) makes that row's loss and gradient NaN
+ * and reads nothing outside the table.  16-byte accesses where a leading dimension is a multiple of 4 and its base is
+ * 16-byte aligned (then the pad columns of dlogits up to round_up(C, 4) are written as 0), scalar otherwise.
+ * Refused on the host with MMVQA_ERR_ARG: an unknown mode, rows < 1, C < 1, a null logits / target / row_loss / loss,
+ * ld < C, dld < C with dlogits, mode 2 without table or category or with table_ld < C or n_cat < 1, smoothing outside
+ * [0, 1]. */
+#define MMVQA_SOFT_CE_HARD 0
+#define MMVQA_SOFT_CE_UNIFORM 1
+#define MMVQA_SOFT_CE_CATEGORY 2
+int mmvqa_soft_ce_loss(mmvqa_stream_t s, const float* logits, int ld, const long long* target, const long long* category,
+                       const float* table, int table_ld, int n_cat, int mode, double smoothing, float* row_loss,
+                       float* loss, float* dlogits, int dld, int rows, int C, float gscale);
 /* ---- EfficientNetV2 (timm tf_efficientnetv2_m as models/image_encoding.py:15,26,100-115 instantiates it) pieces,
  * NHWC fp32; sc/sh = BatchNorm scale/shift of the producing conv (applied on load), stat = [16][C][2] doubles.
  * depthwise 3x3 (MBConv conv_dw): z2 = dw(silu(z1*s1+b1)), statistics of z2; TF "SAME" padding via pad (begin) */

@@ -20,6 +20,7 @@ KIND_FWD, KIND_DGRAD, KIND_WGRAD = 0, 1, 2
 PRO_NONE, PRO_AFFINE_RELU, PRO_DZ, PRO_AFFINE, PRO_AFFINE_SILU, PRO_SILU_GATE = 0, 1, 2, 3, 4, 5
 EPI_PLAIN, EPI_TAP_FWD, EPI_TAP_BWD = 0, 1, 2
 PREC_F32, PREC_F16 = 0, 1   # mmvqa_gemm_desc.reserved0 / mmvqa_engine_set_precision
+SOFT_CE_HARD, SOFT_CE_UNIFORM, SOFT_CE_CATEGORY = 0, 1, 2   # mmvqa_soft_ce_loss modes
 STAT_SLOTS = 16
 
 
@@ -134,6 +135,7 @@ SIGNATURES = {
     "mmvqa_supcon_loss": (_i, [_P, _P, _P, _P, _P, _i, _i, _f, _f, _f]),
     "mmvqa_supcon_loss_masked": (_i, [_P, _P, _P, _P, _P, _P, _i, _i, _f, _f, _f]),
     "mmvqa_jaccard_mask": (_i, [_P] * 8 + [_i, _i]),
+    "mmvqa_soft_ce_loss": (_i, [_P, _P, _i, _P, _P, _P, _i, _i, _i, _d, _P, _P, _P, _i, _i, _i, _f]),
     "mmvqa_dwconv_fwd": (_i, [_P, _P, _P, _P, _P, _P, _P] + [_i] * 8),
     "mmvqa_dwconv_bwd_data": (_i, [_P] * 14 + [_i] * 8),
     "mmvqa_dwconv_bwd_weight": (_i, [_P] * 10 + [_i] * 8),

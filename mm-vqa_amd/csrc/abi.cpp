@@ -160,6 +160,12 @@ int mmvqa_jaccard_mask(mmvqa_stream_t s, const int* offsets, const int* ids, con
                        const int* rowsB, const int* colsB, float* mask, int n, int table_rows) {
   return k_jaccard_mask(ST(s), offsets, ids, rowsA, colsA, rowsB, colsB, mask, n, table_rows);
 }
+int mmvqa_soft_ce_loss(mmvqa_stream_t s, const float* logits, int ld, const long long* target, const long long* category,
+                       const float* table, int table_ld, int n_cat, int mode, double smoothing, float* row_loss,
+                       float* loss, float* dlogits, int dld, int rows, int C, float gscale) {
+  return k_soft_ce(ST(s), logits, ld, target, category, table, table_ld, n_cat, mode, smoothing, row_loss, loss, dlogits,
+                   dld, rows, C, gscale);
+}
 int mmvqa_dwconv_fwd(mmvqa_stream_t s, const float* z1, const float* s1, const float* b1, const float* w, float* z2,
                      double* stat, int N, int H, int W, int C, int OH, int OW, int stride, int pad) {
   return k_dwconv_fwd(ST(s), z1, s1, b1, w, z2, stat, N, H, W, C, OH, OW, stride, pad);

@@ -76,6 +76,10 @@ int k_supcon_masked(hipStream_t st, const float* f, const float* mask, float* lo
 // jaccard.hip: the Jaccard mask of a batch from the resident word-id CSR of the caption table
 int k_jaccard_mask(hipStream_t st, const int* offsets, const int* ids, const int* rowsA, const int* colsA,
                    const int* rowsB, const int* colsB, float* mask, int n, int table_rows);
+// softce.hip: soft-target cross entropy (hard / uniform smoothing / smoothing by question category), forward + backward
+int k_soft_ce(hipStream_t st, const float* logits, int ld, const long long* target, const long long* category,
+              const float* table, int table_ld, int n_cat, int mode, double smoothing, float* row_loss, float* loss,
+              float* dlogits, int dld, int rows, int C, float gscale);
 int k_adam(hipStream_t st, float* p, float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps,
            int step, float gscale, int zero_grad);
 int k_axpy(hipStream_t st, float* y, const float* x, float a, long n);

@@ -246,11 +246,30 @@ class RocoDataset(torch.utils.data.Dataset):
         return decode(path), ids, seg, mask, tgt, idx
 
 
-class VqaDataset(torch.utils.data.Dataset):
-    """item (epoch, index) -> (uint8 [H, W, 3], ids, seg, mask, answer index) as vqamed2019/utils.py:234-257"""
+def category_ids(rows):
+    """{category name: id}: id i is the i-th distinct category of `rows` (data.vqa_tables rows, row[3]) in row order,
+    the numbering of vqamed2019/utils.py:228-229 over the train table"""
+    ids = {}
+    for r in rows:
+        ids.setdefault(r[3], len(ids))
+    return ids
 
-    def __init__(self, rows, tokenizer, max_position_embeddings=28):
+
+class VqaDataset(torch.utils.data.Dataset):
+    """item (epoch, index) -> (uint8 [H, W, 3], ids, seg, mask, answer index) as vqamed2019/utils.py:234-257
+    categories = {category name: id} (category_ids of the train table, or CategorySmoothing.cat2idx): the item gains a
+    last element, the row's category id (utils.py:252, self.cats2ans[category]), and batches are packed by
+    collate_category.  A row whose category the map lacks is refused when the dataset is built.  Default (None): the
+    item and the batches are as before."""
+
+    def __init__(self, rows, tokenizer, max_position_embeddings=28, categories=None):
         self.rows, self.tok, self.T = list(rows), tokenizer, max_position_embeddings
+        self.categories = None if categories is None else dict(categories)
+        if self.categories is not None:
+            missing = sorted({r[3] for r in self.rows} - set(self.categories))
+            if missing:
+                raise ValueError(f"VqaDataset: categories {missing} of the rows are not in the category map")
+            self.collate = collate_category
 
     def __len__(self):
         return len(self.rows)
@@ -259,7 +278,8 @@ class VqaDataset(torch.utils.data.Dataset):
         _epoch, idx = key
         path, question, ans = self.rows[idx][:3]
         ids, seg, mask = (torch.tensor(v, dtype=torch.long) for v in text.encode_text_vqa(question, self.tok, self.T))
-        return decode(path), ids, seg, mask, torch.tensor(ans, dtype=torch.long), idx
+        item = decode(path), ids, seg, mask, torch.tensor(ans, dtype=torch.long), idx
+        return item if self.categories is None else item + (self.categories[self.rows[idx][3]],)
 
 
 def collate(items):
@@ -271,6 +291,14 @@ def collate(items):
                 ids=torch.stack([it[1] for it in items]), seg=torch.stack([it[2] for it in items]),
                 mask=torch.stack([it[3] for it in items]), target=torch.stack([it[4] for it in items]),
                 index=torch.tensor([it[5] for it in items], dtype=torch.int64))
+
+
+def collate_category(items):
+    """collate for items that end with the category id (VqaDataset(categories=...)): the same dict plus category [B]
+    int64 (like target)"""
+    out = collate([it[:6] for it in items])
+    out["category"] = torch.tensor([it[6] for it in items], dtype=torch.int64)
+    return out
 
 
 def collate_supcon(items):
@@ -461,10 +489,15 @@ class DeviceFeeder:
     RocoSupConDataset(report_aug_col=True)): the batch is a 6-tuple whose last element is (rows, cols), two int32 device
     tensors [n] naming the translation text (table row, WordSets column 1..3) of each sample.  They live in the slot and
     are copied on the feeder's stream with the rest of it: same ready event, same reuse rule.  The log entry gains
-    `aug_col`.  With pairs=False (default) the batch stays the 5-tuple."""
+    `aug_col`.  With pairs=False (default) the batch stays the 5-tuple.
+
+    category=True (VQA with label smoothing by category; the host batches must carry `category`, i.e. come from a
+    VqaDataset(categories=...)): the batch is a 6-tuple whose last element is category, an int64 device tensor [B] of
+    category ids.  It lives in the slot and is copied on the feeder's stream like the rest: same ready event, same reuse
+    rule.  The log entry gains `category`.  Not together with pairs."""
 
     def __init__(self, host: HostLoader, device, train=True, depth=2, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5),
-                 fused=True, pairs=False):
+                 fused=True, pairs=False, category=False):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("DeviceFeeder runs on the GPU only (no CPU fallback)")
@@ -472,7 +505,9 @@ class DeviceFeeder:
             raise ValueError("depth must be >= 1")
         self.host, self.dev, self.depth, self.fused = host, device, int(depth), fused
         self.views = getattr(host, "views", 1)
-        self.pairs = bool(pairs)
+        self.pairs, self.category = bool(pairs), bool(category)
+        if self.pairs and self.category:
+            raise ValueError("DeviceFeeder: pairs and category are the sixth element of different loops' batches")
         aug = host.aug or {}
         self.aug = DeviceAugment(size=host.size, train=train, mean=mean, std=std, device=device, **aug)
         self.stream, self.priority = low_priority_stream(device)
@@ -549,11 +584,22 @@ class DeviceFeeder:
                 rows.copy_(batch["row"], non_blocking=True)
                 cols.copy_(batch["aug_col"], non_blocking=True)
                 out.append((rows, cols))
+            if self.category:
+                if "category" not in batch:
+                    raise ValueError("DeviceFeeder(category=True): the host batches carry no `category` "
+                                     "(VqaDataset(categories=...) reports it)")
+                if buf.get("category") is None or buf["category"].shape[0] < B:
+                    buf["category"] = torch.empty(max(B, buf["ids"].shape[0]), dtype=torch.int64, device=self.dev)
+                cat = buf["category"][:B]
+                cat.copy_(batch["category"], non_blocking=True)
+                out.append(cat)
             slot.ready = torch.cuda.Event()
             slot.ready.record(s)
         entry = dict(meta, index=batch["index"].tolist(), params=params, shapes=batch["shapes"].tolist())
         if self.pairs:
             entry["aug_col"] = batch["aug_col"].tolist()
+        if self.category:
+            entry["category"] = batch["category"].tolist()
         self._queue.append((slot, tuple(out), entry))
         return True
 

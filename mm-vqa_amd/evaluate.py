@@ -72,6 +72,8 @@ def category_metrics(preds, targets, categories, idx2ans, prefix=""):
 @torch.no_grad()
 def _run(loader, model, criterion, categories, idx2ans, category, prefix):
     model.eval()
+    if hasattr(criterion, "eval"):
+        criterion.eval()                  # utils.py:693 / 772: a smoothing criterion evaluates as plain cross entropy
     losses, PREDS, TARGETS = [], [], []
     for img, question_token, segment_ids, attention_mask, target in loader:
         logits, _, _ = model(img, question_token, segment_ids, attention_mask)       # utils.py:711 / 789

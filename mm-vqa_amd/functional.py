@@ -3,6 +3,9 @@
   mlm_loss      -- pretrain/roco_utils.py:235-236 (log_softmax + NLLLoss over ALL positions) and
                    :257-265 (argmax accuracy over target > 0), one fused pass over the logits
   asl_loss      -- models/asl_singlelabel.py:23-53
+  soft_ce_loss  -- soft-target cross entropy, forward and gradient in one launch: hard target, LabelSmoothing
+                   (vqamed2019/utils.py:178-200), LabelSmoothByCategory (vqamed2019/utils.py:1234-1300)
+  CategorySmoothing, LabelSmoothing -- the two --smoothing criteria of vqamed2019/train.py:164-174 over it
   supcon_loss   -- models/SupConLoss/loss.py:21-98: features only (SimCLR), or with labels / a positive mask
   jaccard_mask  -- models/SupConLoss/supcon_utils.py:110-138 from word-id sets resident on the device
   split_feat    -- models/SupConLoss/supcon_utils.py:259-261
@@ -90,6 +93,149 @@ class _ASLLoss(torch.autograd.Function):
 
 def asl_loss(logits, target, gamma_pos=0.0, gamma_neg=4.0, eps=0.1):
     return _ASLLoss.apply(logits, target, gamma_pos, gamma_neg, eps)
+
+
+def _soft_ce(x, ld, tgt, mode, smoothing, table, category, want_grad):
+    """one mmvqa_soft_ce_loss call over the [rows, C] view x -> (loss (0-dim), row_loss [rows], dlogits [rows, ld'] or
+    None); dlogits already carries the 1 / rows of the mean"""
+    rows, Cc = x.shape
+    row_loss = torch.empty(rows, dtype=torch.float32, device=x.device)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    dl = torch.empty(rows, (Cc + 3) & ~3, dtype=torch.float32, device=x.device) if want_grad else None
+    n_cat, tld = (table.shape[0], table.stride(0)) if table is not None else (0, 0)
+    L.check(L.lib().mmvqa_soft_ce_loss(L.stream_ptr(), L.ptr(x), ld, L.ptr(tgt), L.ptr(category), L.ptr(table), tld, n_cat,
+                                       mode, float(smoothing), L.ptr(row_loss), L.ptr(loss), L.ptr(dl),
+                                       dl.stride(0) if want_grad else 0, rows, Cc, 1.0 / rows))
+    return loss, row_loss, dl
+
+
+class _SoftCE(torch.autograd.Function):
+    """forward: one launch writes the row losses AND dlogits (saved), a one-workgroup launch the mean; backward
+    multiplies the saved dlogits by the upstream gradient, as _ASLLoss does.  want_grad is decided by the caller
+    (soft_ce_loss): grad mode is always off inside forward and needs_input_grad does not see torch.no_grad.  Without
+    it dlogits is neither allocated, written nor saved."""
+
+    @staticmethod
+    def forward(ctx, logits, target, mode, smoothing, table, category, want_grad):
+        x, ld = _padded(logits)
+        tgt = target.reshape(-1).contiguous().long()
+        loss, _row_loss, dl = _soft_ce(x, ld, tgt, mode, smoothing, table, category, want_grad)
+        if dl is not None:
+            ctx.save_for_backward(dl)
+        ctx.C = x.shape[1]
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        (dl,) = ctx.saved_tensors
+        return (dl * gloss)[:, :ctx.C], None, None, None, None, None, None
+
+
+def soft_ce_loss(logits, target, mode=L.SOFT_CE_HARD, smoothing=0.0, table=None, category=None):
+    """Mean soft-target cross entropy of logits [rows, C] (fp32, on the GPU) against target [rows]:
+      mode SOFT_CE_HARD (0)      nn.CrossEntropyLoss; `smoothing` is not read
+      mode SOFT_CE_UNIFORM (1)   LabelSmoothing (vqamed2019/utils.py:178-200): soft = smoothing / C + (1 - smoothing) onehot
+      mode SOFT_CE_CATEGORY (2)  LabelSmoothByCategory's training branch (utils.py:1247-1260): soft = table[category],
+                                 then soft[target] = 1 - smoothing (overwritten, not added); `table` [n_cat, C] fp32 on the
+                                 device (unit column stride; CategorySmoothing builds it), `category` [rows] integer ids
+    A target outside [0, C) or a category outside [0, n_cat) makes the loss NaN (and that row's gradient); nothing is
+    read outside the table.  Runs on the current stream, nothing is synchronised; the loss is bit-equal from run to run.
+    Every tensor must already be on the logits' device: nothing is moved (a hidden host-to-device copy would stall the
+    step).  Under torch.no_grad(), or for logits that need no gradient, dlogits is not computed."""
+    if not logits.is_cuda:
+        raise L.MMVQAError("soft_ce_loss: GPU tensors only (no CPU fallback)")
+    if target.device != logits.device or (mode == L.SOFT_CE_CATEGORY and category is not None and category.device != logits.device):
+        raise L.MMVQAError("soft_ce_loss: target and category must be on the logits' device (GPU tensors only; nothing is moved)")
+    if logits.dim() != 2 or logits.dtype != torch.float32:
+        raise ValueError(f"soft_ce_loss: logits must be fp32 [rows, C], got {logits.dtype} {list(logits.shape)}")
+    if target.numel() != logits.shape[0]:
+        raise ValueError(f"soft_ce_loss: {target.numel()} targets for {logits.shape[0]} rows")
+    if mode == L.SOFT_CE_CATEGORY:
+        if table is None or category is None:
+            raise ValueError("soft_ce_loss: the category mode needs `table` and `category`")
+        if (table.device != logits.device or table.dtype != torch.float32 or table.dim() != 2 or table.stride(1) != 1
+                or table.shape[1] != logits.shape[1]):
+            raise ValueError("soft_ce_loss: `table` must be fp32 [n_cat, C] on the logits' device with unit column stride")
+        if category.numel() != logits.shape[0]:
+            raise ValueError(f"soft_ce_loss: {category.numel()} category ids for {logits.shape[0]} rows")
+        category = category.reshape(-1).long().contiguous()
+    else:
+        table = category = None
+    want_grad = torch.is_grad_enabled() and logits.requires_grad
+    return _SoftCE.apply(logits, target, int(mode), float(smoothing), table, category, want_grad)
+
+
+class _Criterion:
+    """what the loops ask of a criterion object: .to(device), .train() / .eval() (nn.Module's protocol: a fresh object
+    is in training mode) and __call__(logits, target, category=None).  In eval mode both criteria are the plain cross
+    entropy of the CE path (mlm_loss), as the reference's else branches are."""
+
+    training = True
+
+    def train(self, mode=True):
+        self.training = bool(mode)
+        return self
+
+    def eval(self):
+        return self.train(False)
+
+    def to(self, device):
+        return self
+
+
+class LabelSmoothing(_Criterion):
+    """vqamed2019/utils.py:178-200: training, mean_rows(sum_j -(smoothing / C + (1 - smoothing) [j == t]) log_softmax(x)_j);
+    eval, cross entropy.  `category` is accepted and ignored, so the loops call both criteria the same way."""
+
+    def __init__(self, smoothing=0.1):
+        self.smoothing, self.confidence = float(smoothing), 1.0 - float(smoothing)
+
+    def __call__(self, logits, target, category=None):
+        if not self.training:
+            return mlm_loss(logits, target)[0]
+        return soft_ce_loss(logits, target, L.SOFT_CE_UNIFORM, self.smoothing)
+
+
+class CategorySmoothing(_Criterion):
+    """LabelSmoothByCategory (vqamed2019/utils.py:1234-1300).  train_rows: the WHOLE train table as data.vqa_tables
+    gives it (row[2] = answer index, row[3] = category name).  categories: the distinct category names in row order --
+    category id i is categories[i], the numbering VqaDataset(categories=...) hands out (the dataset's own numbering,
+    utils.py:228-229; on VQA-Med 2019's table it is the order the reference hard-codes at :1292-1293).  table
+    [n_cat, num_classes] fp32 on the host: row i is smoothing / len(idx) at idx = the distinct answers of category i's
+    train rows (the double quotient rounded to fp32, as torch's indexed assignment stores it, :1266-1293), 0 elsewhere;
+    a category without rows keeps a zero row.  .to(device) puts a copy with 16-byte-aligned rows on the GPU.
+    Training mode: soft = table[category] with soft[target] = 1 - smoothing; eval mode: cross entropy, category ignored."""
+
+    def __init__(self, train_rows, num_classes, smoothing=0.1, categories=None):
+        self.smoothing, self.confidence, self.num_classes = float(smoothing), 1.0 - float(smoothing), int(num_classes)
+        answers = {c: [] for c in (categories or ())}
+        for r in train_rows:
+            answers.setdefault(r[3], []).append(int(r[2]))
+        self.categories = list(answers)
+        self.cat2idx = {c: i for i, c in enumerate(self.categories)}
+        self.table = torch.zeros(max(len(self.categories), 1), self.num_classes, dtype=torch.float32)
+        for i, c in enumerate(self.categories):
+            idx = sorted(set(answers[c]))
+            if idx:
+                self.table[i, torch.tensor(idx, dtype=torch.long)] = self.smoothing / len(idx)
+        self._dev = None
+
+    def to(self, device):
+        ld = (self.num_classes + 3) & ~3
+        buf = torch.zeros(self.table.shape[0], ld, dtype=torch.float32, device=device)
+        buf[:, :self.num_classes] = self.table
+        self._dev = buf[:, :self.num_classes]
+        return self
+
+    def __call__(self, logits, target, category=None):
+        if not self.training:
+            return mlm_loss(logits, target)[0]
+        if category is None:
+            raise ValueError("CategorySmoothing: the training branch needs the category ids of the batch")
+        if self._dev is None or self._dev.device != logits.device:
+            raise L.MMVQAError("CategorySmoothing: move the criterion to the logits' device first (.to(device)); "
+                               "GPU tensors only (no CPU fallback)")
+        return soft_ce_loss(logits, target, L.SOFT_CE_CATEGORY, self.smoothing, self._dev, category)
 
 
 class _SupCon(torch.autograd.Function):

@@ -42,6 +42,23 @@ def vqa_batch(B, T=32, hw=224, vocab=30522, n_classes=1552, seed=1234, device="c
 VQA_CATEGORIES = ("modality", "plane", "organ", "abnormality", "binary")   # the five question types of VQA-Med-2019
 
 
+def vqa_category_rows(n_classes):
+    """A synthetic train table for label smoothing by category: one row per class, class c in category
+    VQA_CATEGORIES[c % 5], in the row layout of data.vqa_tables (image path, question, answer index, category, mode).
+    In first-appearance order category id i is VQA_CATEGORIES[i]."""
+    return [(f"synpic{c}.jpg", f"what is shown in image {c}?", c, VQA_CATEGORIES[c % len(VQA_CATEGORIES)], "train")
+            for c in range(n_classes)]
+
+
+def vqa_categories(B, n_classes=1552, seed=1234, device="cpu"):
+    """category ids [B] (int64) of vqa_batch(B, ..., n_classes, seed): the batch's targets are drawn again from the
+    batch seed and sample b gets the category of its class, target_b % 5 -- the partition of vqa_category_rows, so
+    every target lies in its category's answer set"""
+    g = torch.Generator().manual_seed(seed + 77)
+    tgt = torch.randint(0, n_classes, (B,), generator=g)
+    return (tgt % len(VQA_CATEGORIES)).to(device)
+
+
 def vqa_test_table(n, n_classes, seed=1234, data_dir="../ImageClef-2019-VQA-Med"):
     """A synthetic stand-in for the test split's table as vqamed2019/utils.py:51-79 (load_data) + eval.py:84-97 leave
     it: columns (img_id, question, answer, category, mode) with img_id a path under <data_dir>/Test/images, answer the

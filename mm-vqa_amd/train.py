@@ -21,6 +21,7 @@ torch.distributed (RCCL).
     python -m mmvqa_amd.train mlm    --run_name r --mlm_prob 0.15 --epochs 2 --steps_per_epoch 20
     python -m mmvqa_amd.train supcon --run_name r --mlm_prob 0.15 --batch_size 32
     python -m mmvqa_amd.train vqa    --run_name r --loss ASLSingleLabel --batch_size 64
+    python -m mmvqa_amd.train vqa    --run_name r --smoothing 0.1 --batch_size 64
     python -m mmvqa_amd.train eval   --model_dir save/MLM/r.pt --num_classes 1552 --batch_size 16
     python -m mmvqa_amd.train mlm    --data_dir roco-dataset/data --vocab_file vocab.txt --num_workers 4
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --batch_size 32
@@ -36,7 +37,8 @@ import torch
 import torch.distributed as dist
 from torch.optim import lr_scheduler
 
-from . import FusedAdam, Model, asl_loss, checkpoint, evaluate, jaccard_mask, mlm_loss, split_feat, supcon_loss, synth
+from . import (CategorySmoothing, FusedAdam, LabelSmoothing, Model, asl_loss, checkpoint, evaluate, jaccard_mask, mlm_loss,
+               split_feat, supcon_loss, synth)
 from . import data as D
 from .amp import GradScaler
 from .ddp import GradReducer, comm_info, global_supcon_pairs, global_supcon_views, sync_replicas
@@ -90,12 +92,12 @@ def common_args(p):
     p.add_argument("--feeder_depth", type=int, default=2, help="device batches prepared ahead of the step")
 
 
-def feeder(args, ctx, dataset, train, aug=None, batch_size=None, views=1, pairs=False):
+def feeder(args, ctx, dataset, train, aug=None, batch_size=None, views=1, pairs=False, category=False):
     """DeviceFeeder over one split (shuffled and augmented for training, file order and val transforms otherwise)"""
     host = D.HostLoader(dataset, batch_size or args.batch_size, shuffle=train, seed=args.seed, rank=ctx.rank,
                         world=ctx.world, num_workers=args.num_workers, aug=aug if train else None, size=args.image_size,
                         views=views)
-    return D.DeviceFeeder(host, ctx.dev, train=train, depth=args.feeder_depth, pairs=pairs)
+    return D.DeviceFeeder(host, ctx.dev, train=train, depth=args.feeder_depth, pairs=pairs, category=category)
 
 
 def tokenizer(args):
@@ -304,12 +306,14 @@ def vqa_step(model, opt, red, world, batch, crit, clip=False, scaler=None):
     optional clip_grad_norm_(1.0) (:663-664); Adam; pred = softmax(1).argmax(1).
     With a scaler (--mixed_precision) the reference's sequence of utils.py:641-657: autocast
     forward + loss; scaler.scale(loss) is computed and DISCARDED; the backward is unscaled; the clip acts on those
-    gradients; scaler.step then unscales them by 1/scale all the same (and skips on a non-finite gradient)."""
-    img, ids, seg, mask, tgt = batch
+    gradients; scaler.step then unscales them by 1/scale all the same (and skips on a non-finite gradient).
+    A 6-tuple batch (--smoothing) ends with the category ids and the loss is criterion(logits, target, category)
+    (utils.py:648-649; also under a scaler, where the reference's call at :644 lacks the argument and raises)."""
+    img, ids, seg, mask, tgt = batch[:5]
     opt.zero_grad()
     with torch.autocast("cuda", dtype=torch.float16, enabled=scaler is not None):
         logits, _, _ = model(img, ids, seg, mask)       # utils.py:646
-        loss = crit(logits, tgt)
+        loss = crit(logits, tgt, batch[5]) if len(batch) == 6 else crit(logits, tgt)
     if scaler is not None:
         scaler.scale(loss)                          # utils.py:651: the scaled loss is not used
     loss.backward()
@@ -430,35 +434,57 @@ def run_supcon(args):
 
 
 # ----------------------------------------------------------------------------------------- VQA-Med-2019
+def vqa_criterion(args, ctx, train_rows=None):
+    """vqamed2019/train.py:164-174: --smoothing is tested first (then --loss is not consulted): LabelSmoothByCategory
+    over the WHOLE train table (every rank builds the same table, whatever its shard), with the flag's value (the
+    reference drops it and always smooths with 0.1); else ASLSingleLabel or cross entropy.  Without --data_dir the
+    train table is synth.vqa_category_rows."""
+    if getattr(args, "smoothing", None):
+        rows = synth.vqa_category_rows(args.num_classes) if train_rows is None else train_rows
+        return CategorySmoothing(rows, args.num_classes, args.smoothing).to(ctx.dev)
+    return (lambda lg, t: asl_loss(lg, t)) if args.loss == "ASLSingleLabel" else (lambda lg, t: mlm_loss(lg, t)[0])
+
+
 def run_vqa(args):
     ctx = Ctx(args)
     args.dataset, args.task = "VQA-Med", "MLM"
     tr_fd = va_fd = None
+    smooth = bool(getattr(args, "smoothing", None))
     if args.data_dir:                                   # train.py:100-105: the classes are the answers of the tables
         tok = tokenizer(args)
         _cols, tabs, idx2ans = D.vqa_tables(args.data_dir)
         args.num_classes = len(idx2ans)
-        tr_fd = feeder(args, ctx, D.VqaDataset(tabs["train"], tok, args.max_position_embeddings), True, D.VQA_AUG)
+        crit = vqa_criterion(args, ctx, tabs["train"])
+        tr_ds = D.VqaDataset(tabs["train"], tok, args.max_position_embeddings, categories=crit.cat2idx if smooth else None)
+        tr_fd = feeder(args, ctx, tr_ds, True, D.VQA_AUG, category=smooth)
         va_fd = feeder(args, ctx, D.VqaDataset(tabs["val"], tok, args.max_position_embeddings), False)
+    else:
+        crit = vqa_criterion(args, ctx)
     C = args.num_classes
     model, opt, sched, red = build(args, ctx, n_classes=C)
     scaler = GradScaler() if args.mixed_precision else None
     T, B = args.max_position_embeddings, args.batch_size
-    crit = (lambda lg, t: asl_loss(lg, t)) if args.loss == "ASLSingleLabel" else (lambda lg, t: mlm_loss(lg, t)[0])
+
+    def synthetic_train(epoch):
+        for i in range(args.steps_per_epoch):
+            sd = args.seed + 7919 * (epoch * 100003 + i) + ctx.rank
+            batch = synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=sd, device=ctx.dev)
+            yield batch + (synth.vqa_categories(B, C, seed=sd, device=ctx.dev),) if smooth else batch
     # (vqamed2019/train.py itself has no recorder / --resume; kept here like the two pre-training loops)
     start, kept = maybe_resume(args, model, opt, sched, "vqa")
     best_loss, best_acc1 = kept.get("best_loss", float("inf")), kept.get("best_acc1", 0.0)
     best_acc2, counter = kept.get("best_acc2", 0.0), kept.get("counter", 0)
     for epoch in range(start, args.epochs):
         model.train()
+        if smooth:
+            crit.train()        # every epoch: the reference leaves the criterion in eval mode after its first validate
         tl, steps = 0.0, 0
-        synthetic = (synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C,
-                                     seed=args.seed + 7919 * (epoch * 100003 + i) + ctx.rank, device=ctx.dev)
-                     for i in range(args.steps_per_epoch))
-        for img, ids, seg, mask, tgt in epoch_batches(tr_fd, epoch, synthetic):
-            loss, _ = vqa_step(model, opt, red, ctx.world, (img, ids, seg, mask, tgt), crit, clip=args.clip, scaler=scaler)
+        for batch in epoch_batches(tr_fd, epoch, synthetic_train(epoch)):
+            loss, _ = vqa_step(model, opt, red, ctx.world, batch, crit, clip=args.clip, scaler=scaler)
             tl, steps = tl + float(loss.detach()), steps + 1
         model.eval()
+        if smooth:
+            crit.eval()         # utils.py:693: validation is plain cross entropy
         vl, correct, total, vsteps = 0.0, 0, 0, 0
         with torch.no_grad():
             synthetic = (synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=10 ** 6 + i, device=ctx.dev)
@@ -505,7 +531,10 @@ def run_eval(args):
     <model_name>_res.txt in save_dir.  The test split is synthetic (mmvqa_amd.synth.vqa_test_table + vqa_batch: the
     dataset and its tokenizer are not in the image); everything after the loader is the reference's sequence."""
     ctx, model, cols, rows, idx2ans, batches = eval_setup(args)
-    crit = (lambda lg, t: asl_loss(lg, t)) if args.loss == "ASLSingleLabel" else (lambda lg, t: mlm_loss(lg, t)[0])
+    if getattr(args, "smoothing", None):     # eval.py:124-125; test() puts it in eval mode (utils.py:772): cross entropy
+        crit = LabelSmoothing(args.smoothing)
+    else:
+        crit = (lambda lg, t: asl_loss(lg, t)) if args.loss == "ASLSingleLabel" else (lambda lg, t: mlm_loss(lg, t)[0])
     cats = [r[3] for r in rows]
     with torch.autocast("cuda", dtype=torch.float16, enabled=args.mixed_precision):   # utils.py:786-792
         test_loss, predictions, acc, bleu = evaluate.test(batches, model, crit, cats, idx2ans, category=args.category)
@@ -619,6 +648,11 @@ def parse_args(argv=None):
         p.add_argument("--lr", type=float, default=1e-4)
         p.add_argument("--max_position_embeddings", type=int, default=28)
         p.add_argument("--loss", type=str, default="CrossEntropyLoss", choices=["CrossEntropyLoss", "ASLSingleLabel"])
+        p.add_argument("--smoothing", type=float, default=None,
+                       help="label smoothing by question category (LabelSmoothByCategory, vqamed2019/utils.py:1234-1300): the "
+                            "train step's target keeps 1 - SMOOTHING and SMOOTHING is spread over the answers of the "
+                            "question's category in the train table; validation and test use cross entropy.  Takes "
+                            "precedence over --loss (train.py:164).  0.1 is what the reference always uses")
         p.add_argument("--num_classes", type=int, default=1552)
         p.add_argument("--counter", type=int, default=20)
         p.add_argument("--clip", action="store_true", default=False, help="clip_grad_norm_(1.0), utils.py:663-664")
@@ -636,6 +670,8 @@ def parse_args(argv=None):
     if args.mixed_precision and args.overlap_adam:
         p.error("--overlap_adam cannot be combined with --mixed_precision: the whole gradient must be checked for "
                 "inf / nan before the first parameter update")
+    if getattr(args, "smoothing", None) is not None and not 0.0 <= args.smoothing <= 1.0:
+        p.error(f"--smoothing {args.smoothing} is outside [0, 1]")
     if mode == "supcon" and args.supcon_mask != "none":
         if args.con_task == "simclr":
             p.error(f"--con_task simclr contradicts --supcon_mask {args.supcon_mask}: SimCLR has no positive mask")
