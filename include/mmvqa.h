@@ -285,7 +285,8 @@ int mmvqa_l2norm_bwd(mmvqa_stream_t s, const float* dy, const float* y, const fl
 /* SupConLoss.forward(features) without labels/mask = SimCLR (models/SupConLoss/loss.py:21-98);
  * f is [2N][D] view-major (loss.py:57), D <= 256; df (nullable) = dloss/df * gscale; ws = 4*N floats of scratch
  * (row log-sums and row losses).  Tiled over row blocks: any N (the all-gathered view set 2N*world of a
- * data-parallel job, SURVEY 8(e) collective 2). */
+ * data-parallel job, SURVEY 8(e) collective 2).  Null f / loss / ws, N < 1, D < 1 or D > 256: MMVQA_ERR_ARG, before
+ * anything is launched. */
 int mmvqa_supcon_loss(mmvqa_stream_t s, const float* f, float* loss, float* df, float* ws, int N, int D, float temp,
                       float base_temp, float gscale);
 /* SupConLoss.forward(features, mask=mask) (loss.py:21-98, contrast_mode 'all', two views): mask is [N][N] fp32, any
@@ -293,7 +294,8 @@ int mmvqa_supcon_loss(mmvqa_stream_t s, const float* f, float* loss, float* df, 
  * positives of every anchor: loss = -(T/T_base) mean_a sum_b mt[a][b] (z[a][b] - lse[a]) / M[a], M[a] = sum_b mt[a][b].
  * A row with M[a] == 0 gives NaN, as the reference's division does.  f, df, N, D, gscale as mmvqa_supcon_loss;
  * ws = 6*N floats (2*N more than the unmasked call: the mask row sums M, which the gradient pass needs for both
- * mt[a][b] / M[a] and mt[b][a] / M[b]).  Null f / mask / loss / ws, D > 256 or N < 1: MMVQA_ERR_ARG. */
+ * mt[a][b] / M[a] and mt[b][a] / M[b]).  Null f / loss / ws, N < 1, D < 1 or D > 256: MMVQA_ERR_ARG, before anything
+ * is launched, as mmvqa_supcon_loss; a null mask is refused the same way (it does not select the unmasked loss). */
 int mmvqa_supcon_loss_masked(mmvqa_stream_t s, const float* f, const float* mask, float* loss, float* df, float* ws,
                              int N, int D, float temp, float base_temp, float gscale);
 /* Jaccard mask of a batch (SimilarityCalculator.jaccard, supcon_utils.py:110-138) from a word-id CSR on the device:

@@ -150,11 +150,13 @@ int mmvqa_l2norm_bwd(mmvqa_stream_t s, const float* dy, const float* y, const fl
 }
 int mmvqa_supcon_loss(mmvqa_stream_t s, const float* f, float* loss, float* df, float* ws, int N, int D, float temp,
                       float base_temp, float gscale) {
-  return k_supcon(ST(s), f, loss, df, ws, N, D, temp, base_temp, gscale);
+  return k_supcon(ST(s), f, nullptr, loss, df, ws, N, D, temp, base_temp, gscale);
 }
 int mmvqa_supcon_loss_masked(mmvqa_stream_t s, const float* f, const float* mask, float* loss, float* df, float* ws,
                              int N, int D, float temp, float base_temp, float gscale) {
-  return k_supcon_masked(ST(s), f, mask, loss, df, ws, N, D, temp, base_temp, gscale);
+  // a null mask is refused here: to the launcher it would mean the unmasked loss
+  if (!mask) return mmvqa_set_error(MMVQA_ERR_ARG, "supcon_masked: mask is null (mmvqa_supcon_loss is the loss without one)");
+  return k_supcon(ST(s), f, mask, loss, df, ws, N, D, temp, base_temp, gscale);
 }
 int mmvqa_jaccard_mask(mmvqa_stream_t s, const int* offsets, const int* ids, const int* rowsA, const int* colsA,
                        const int* rowsB, const int* colsB, float* mask, int n, int table_rows) {

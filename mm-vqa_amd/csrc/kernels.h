@@ -68,11 +68,10 @@ int k_asl(hipStream_t st, const float* logits, int ld, const long long* target, 
           int dld, int rows, int C, float gpos, float gneg, float eps, float gscale);
 int k_l2norm_fwd(hipStream_t st, const float* x, float* y, float* nrm, int rows, int D);
 int k_l2norm_bwd(hipStream_t st, const float* dy, const float* y, const float* nrm, float* dx, int rows, int D);
-int k_supcon(hipStream_t st, const float* f, float* loss, float* df, float* ws, int N, int D, float temp,
-             float base_temp, float gscale);
-// SupCon with a positive mask [N][N] (loss.py:45-55,76-96); ws = 6*N floats (lse, row losses, mask row sums)
-int k_supcon_masked(hipStream_t st, const float* f, const float* mask, float* loss, float* df, float* ws, int N, int D,
-                    float temp, float base_temp, float gscale);
+// supcon.hip: SupCon / SimCLR loss and gradient.  mask == nullptr: the other view is the only positive, ws = 4*N floats
+// (lse, row losses); mask [N][N] (loss.py:45-55,76-96): weighted positives, ws = 6*N floats (+ the mask row sums)
+int k_supcon(hipStream_t st, const float* f, const float* mask, float* loss, float* df, float* ws, int N, int D,
+             float temp, float base_temp, float gscale);
 // jaccard.hip: the Jaccard mask of a batch from the resident word-id CSR of the caption table
 int k_jaccard_mask(hipStream_t st, const int* offsets, const int* ids, const int* rowsA, const int* colsA,
                    const int* rowsB, const int* colsB, float* mask, int n, int table_rows);

@@ -239,33 +239,8 @@ class CategorySmoothing(_Criterion):
 
 
 class _SupCon(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, features, temperature, base_temperature):
-        if not features.is_cuda:
-            raise L.MMVQAError("supcon_loss: GPU tensors only (no CPU fallback)")
-        N, nv, D = features.shape
-        if nv != 2:
-            raise NotImplementedError("two views (supcon_utils.py:259-261)")
-        f = torch.cat(torch.unbind(features, dim=1), dim=0).contiguous().float()
-        loss = torch.empty(1, dtype=torch.float32, device=f.device)
-        df = torch.empty_like(f)
-        ws = torch.empty(4 * N, dtype=torch.float32, device=f.device)
-        L.check(L.lib().mmvqa_supcon_loss(L.stream_ptr(), L.ptr(f), L.ptr(loss), L.ptr(df), L.ptr(ws), N, D,
-                                          temperature, base_temperature, 1.0))
-        ctx.save_for_backward(df)
-        ctx.N = N
-        return loss[0].clone()
-
-    @staticmethod
-    def backward(ctx, gloss):
-        (df,) = ctx.saved_tensors
-        N = ctx.N
-        g = df * gloss
-        return torch.stack([g[:N], g[N:]], dim=1), None, None
-
-
-class _SupConMasked(torch.autograd.Function):
-    """SupConLoss.forward(features, mask=mask): the masked kernels (mmvqa_supcon_loss_masked); no gradient for the mask"""
+    """SupConLoss.forward(features) or (features, mask=mask): mmvqa_supcon_loss / mmvqa_supcon_loss_masked; no gradient
+    for the mask"""
 
     @staticmethod
     def forward(ctx, features, mask, temperature, base_temperature):
@@ -275,12 +250,17 @@ class _SupConMasked(torch.autograd.Function):
         if nv != 2:
             raise NotImplementedError("two views (supcon_utils.py:259-261)")
         f = torch.cat(torch.unbind(features, dim=1), dim=0).contiguous().float()
-        m = mask.detach().to(device=f.device, dtype=torch.float32).contiguous()      # loss.py:55
         loss = torch.empty(1, dtype=torch.float32, device=f.device)
         df = torch.empty_like(f)
-        ws = torch.empty(6 * N, dtype=torch.float32, device=f.device)
-        L.check(L.lib().mmvqa_supcon_loss_masked(L.stream_ptr(), L.ptr(f), L.ptr(m), L.ptr(loss), L.ptr(df), L.ptr(ws),
-                                                 N, D, temperature, base_temperature, 1.0))
+        if mask is None:
+            ws = torch.empty(4 * N, dtype=torch.float32, device=f.device)
+            L.check(L.lib().mmvqa_supcon_loss(L.stream_ptr(), L.ptr(f), L.ptr(loss), L.ptr(df), L.ptr(ws), N, D,
+                                              temperature, base_temperature, 1.0))
+        else:
+            m = mask.detach().to(device=f.device, dtype=torch.float32).contiguous()      # loss.py:55
+            ws = torch.empty(6 * N, dtype=torch.float32, device=f.device)
+            L.check(L.lib().mmvqa_supcon_loss_masked(L.stream_ptr(), L.ptr(f), L.ptr(m), L.ptr(loss), L.ptr(df),
+                                                     L.ptr(ws), N, D, temperature, base_temperature, 1.0))
         ctx.save_for_backward(df)
         ctx.N = N
         return loss[0].clone()
@@ -304,7 +284,7 @@ def supcon_loss(features, temperature=0.07, base_temperature=0.07, labels=None, 
     if labels is not None and mask is not None:
         raise ValueError("Cannot define both `labels` and `mask`")
     if labels is None and mask is None:
-        return _SupCon.apply(features, temperature, base_temperature)
+        return _SupCon.apply(features, None, temperature, base_temperature)
     N = features.shape[0]
     if labels is not None:
         labels = labels.contiguous().view(-1, 1)
@@ -313,7 +293,7 @@ def supcon_loss(features, temperature=0.07, base_temperature=0.07, labels=None, 
         mask = torch.eq(labels, labels.T).float().to(features.device)
     elif tuple(mask.shape) != (N, N):
         raise ValueError(f"`mask` must be [{N}, {N}] (one row and one column per sample), got {list(mask.shape)}")
-    return _SupConMasked.apply(features, mask, temperature, base_temperature)
+    return _SupCon.apply(features, mask, temperature, base_temperature)
 
 
 def jaccard_mask(words, rows_a, cols_a, rows_b=None, cols_b=None):

@@ -95,6 +95,29 @@ def test_igemm_refuses_inconsistent_descriptors():
     refused(desc(), 7, "unknown kind")
 
 
+def test_supcon_refuses_bad_arguments_on_the_host():
+    """both SupCon entry points share one launcher and one set of argument checks: each case returns MMVQA_ERR_ARG and
+    names the offending argument before any HIP call"""
+    from mmvqa_amd import _lib as L
+    lib = L.lib()
+    p = 0x1000                                 # never dereferenced: every case below is refused first
+    # (f, loss, df, ws, N, D) -> what the message must name
+    cases = (((None, p, p, p, 4, 8), b"f is null"), ((p, None, p, p, 4, 8), b"loss is null"),
+             ((p, p, p, None, 4, 8), b"ws is null"), ((p, p, p, p, 0, 8), b"N=0"), ((p, p, p, p, 4, 0), b"D=0"),
+             ((p, p, p, p, 4, 257), b"D=257"))
+    for (f, loss, df, ws, N, D), what in cases:
+        rc = lib.mmvqa_supcon_loss(None, f, loss, df, ws, N, D, 0.07, 0.07, 1.0)
+        err = lib.mmvqa_last_error()
+        assert rc == -1 and err.startswith(b"supcon: ") and what in err, (what, rc, err)
+        rc = lib.mmvqa_supcon_loss_masked(None, f, p, loss, df, ws, N, D, 0.07, 0.07, 1.0)
+        err = lib.mmvqa_last_error()
+        assert rc == -1 and err.startswith(b"supcon_masked: ") and what in err, (what, rc, err)
+    # a null mask is an error of the masked entry point, not a way to the unmasked kernels
+    rc = lib.mmvqa_supcon_loss_masked(None, p, None, p, p, p, 4, 8, 0.07, 0.07, 1.0)
+    err = lib.mmvqa_last_error()
+    assert rc == -1 and err.startswith(b"supcon_masked: ") and b"mask is null" in err, (rc, err)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from mmvqa_amd import _lib as L
     monkeypatch.setattr(L, "_lib", None)

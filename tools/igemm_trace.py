@@ -9,6 +9,7 @@ EXP_NOLOAD / EXP_NOSTORE / EXP_NOBAR (drop the K loop's global loads / LDS-write
 workgroup loads workgroup (0,0)'s tiles), EXP_NOADVANCE (every K-tile re-reads the first), EXP_NOSTOREC (no output store)."""
 import argparse
 import ctypes as C
+import glob
 import os
 import subprocess
 import sys
@@ -25,8 +26,8 @@ def build():
     os.makedirs(out, exist_ok=True)
     exp = os.environ.get("IGEMM_EXP", "")
     lib = os.path.join(out, "libmmvqa_trace%s.so" % exp.replace("-D", "_").replace(" ", ""))
-    srcs = [os.path.join(src, f) for f in ("igemm.hip", "attention.hip", "elementwise.hip", "augment.hip", "se.hip", "tapthin.hip", "qkvattn.hip", "engine.cpp",
-                                           "abi.cpp")]
+    # every kernel unit of the library plus the engine and the C surface; comm.cpp is the RCCL library's, not this one's
+    srcs = sorted(glob.glob(os.path.join(src, "*.hip"))) + [os.path.join(src, f) for f in ("engine.cpp", "abi.cpp")]
     if os.path.exists(lib) and all(os.path.getmtime(lib) > os.path.getmtime(s) for s in srcs):
         return lib
     cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wno-unused-value",
