@@ -306,6 +306,19 @@ int mmvqa_supcon_loss_masked(mmvqa_stream_t s, const float* f, const float* mask
  * or column outside the table gives NaN in the entries it touches.  All pointers are device pointers. */
 int mmvqa_jaccard_mask(mmvqa_stream_t s, const int* offsets, const int* ids, const int* rowsA, const int* colsA,
                        const int* rowsB, const int* colsB, float* mask, int n, int table_rows);
+/* Cosine mask of a batch from caption sentence embeddings resident on the device (SimilarityCalculator.sentence_trans /
+ * bert_embedd, supcon_utils.py:140-168; the encoder itself is not run: the embeddings are computed offline).
+ * mmvqa_normalize_rows, once per table, in place: x[r] = x[r] / max(|x[r]|_2, eps) for rows x D fp32 (eps > 0: a zero
+ * row stays zero).  mmvqa_cosine_mask: table is [table_rows][4][D] fp32, already normalised, text (row, col) with col in
+ * 0..3 (caption, three translations) as in mmvqa_jaccard_mask; mask[i][j] (n x n fp32) = 1 for i == j, else the dot
+ * product of text (rowsA[i], colsA[i]) and text (rowsB[j], colsB[j]), one fmaf chain per lane and a fixed-order wave
+ * reduction: the same inputs give the same bits on every launch.  Cosines may be negative; nothing is clamped.  A row
+ * or column outside the table gives NaN in the entries it touches and reads nothing.  16-byte loads when D % 4 == 0 and
+ * table is 16-byte aligned, scalar loads otherwise.  Refused on the host with MMVQA_ERR_ARG before any HIP call: a null
+ * operand, rows / n / table_rows < 1, D < 1, D > 4096.  All pointers are device pointers. */
+int mmvqa_normalize_rows(mmvqa_stream_t s, float* x, long long rows, int D, float eps);
+int mmvqa_cosine_mask(mmvqa_stream_t s, const float* table, const int* rowsA, const int* colsA, const int* rowsB,
+                      const int* colsB, float* mask, int n, int D, int table_rows);
 /* Soft-target cross entropy over logits [rows][C] (leading dimension ld), forward AND backward in one launch, plus a
  * one-workgroup launch for the mean; the criteria vqamed2019/train.py:164-174 selects with --smoothing:
  *   mode 0 (MMVQA_SOFT_CE_HARD)      nn.CrossEntropyLoss, the eval branch (vqamed2019/utils.py:1261-1264)

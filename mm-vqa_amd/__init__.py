@@ -6,11 +6,11 @@ points here).  All arithmetic is in libmmvqa_hip.so (mm-vqa_amd/csrc, C ABI in i
 from . import _lib
 from ._lib import MMVQAError
 from .model import Model, desc_from_args
-from .functional import mlm_loss, asl_loss, supcon_loss, split_feat, jaccard_mask
+from .functional import mlm_loss, asl_loss, supcon_loss, split_feat, jaccard_mask, embedding_mask
 from .functional import soft_ce_loss, CategorySmoothing, LabelSmoothing
 from .optim import FusedAdam
 from . import synth
 from . import amp
 
-__all__ = ["Model", "desc_from_args", "mlm_loss", "asl_loss", "supcon_loss", "split_feat", "jaccard_mask", "FusedAdam", "synth",
+__all__ = ["Model", "desc_from_args", "mlm_loss", "asl_loss", "supcon_loss", "split_feat", "jaccard_mask", "embedding_mask", "FusedAdam", "synth",
            "MMVQAError", "amp", "soft_ce_loss", "CategorySmoothing", "LabelSmoothing"]

@@ -135,6 +135,8 @@ SIGNATURES = {
     "mmvqa_supcon_loss": (_i, [_P, _P, _P, _P, _P, _i, _i, _f, _f, _f]),
     "mmvqa_supcon_loss_masked": (_i, [_P, _P, _P, _P, _P, _P, _i, _i, _f, _f, _f]),
     "mmvqa_jaccard_mask": (_i, [_P] * 8 + [_i, _i]),
+    "mmvqa_normalize_rows": (_i, [_P, _P, _ll, _i, _f]),
+    "mmvqa_cosine_mask": (_i, [_P] * 7 + [_i, _i, _i]),
     "mmvqa_soft_ce_loss": (_i, [_P, _P, _i, _P, _P, _P, _i, _i, _i, _d, _P, _P, _P, _i, _i, _i, _f]),
     "mmvqa_dwconv_fwd": (_i, [_P, _P, _P, _P, _P, _P, _P] + [_i] * 8),
     "mmvqa_dwconv_bwd_data": (_i, [_P] * 14 + [_i] * 8),

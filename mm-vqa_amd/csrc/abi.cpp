@@ -162,6 +162,13 @@ int mmvqa_jaccard_mask(mmvqa_stream_t s, const int* offsets, const int* ids, con
                        const int* rowsB, const int* colsB, float* mask, int n, int table_rows) {
   return k_jaccard_mask(ST(s), offsets, ids, rowsA, colsA, rowsB, colsB, mask, n, table_rows);
 }
+int mmvqa_normalize_rows(mmvqa_stream_t s, float* x, long long rows, int D, float eps) {
+  return k_normalize_rows(ST(s), x, rows, D, eps);
+}
+int mmvqa_cosine_mask(mmvqa_stream_t s, const float* table, const int* rowsA, const int* colsA, const int* rowsB,
+                      const int* colsB, float* mask, int n, int D, int table_rows) {
+  return k_cosine_mask(ST(s), table, rowsA, colsA, rowsB, colsB, mask, n, D, table_rows);
+}
 int mmvqa_soft_ce_loss(mmvqa_stream_t s, const float* logits, int ld, const long long* target, const long long* category,
                        const float* table, int table_ld, int n_cat, int mode, double smoothing, float* row_loss,
                        float* loss, float* dlogits, int dld, int rows, int C, float gscale) {

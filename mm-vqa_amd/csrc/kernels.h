@@ -75,6 +75,10 @@ int k_supcon(hipStream_t st, const float* f, const float* mask, float* loss, flo
 // jaccard.hip: the Jaccard mask of a batch from the resident word-id CSR of the caption table
 int k_jaccard_mask(hipStream_t st, const int* offsets, const int* ids, const int* rowsA, const int* colsA,
                    const int* rowsB, const int* colsB, float* mask, int n, int table_rows);
+// cosmask.hip: rows of the caption-embedding table to unit length, once; the cosine mask of a batch from that table
+int k_normalize_rows(hipStream_t st, float* x, long long rows, int D, float eps);
+int k_cosine_mask(hipStream_t st, const float* table, const int* rowsA, const int* colsA, const int* rowsB,
+                  const int* colsB, float* mask, int n, int D, int table_rows);
 // softce.hip: soft-target cross entropy (hard / uniform smoothing / smoothing by question category), forward + backward
 int k_soft_ce(hipStream_t st, const float* logits, int ld, const long long* target, const long long* category,
               const float* table, int table_ld, int n_cat, int mode, double smoothing, float* row_loss, float* loss,

@@ -195,6 +195,96 @@ class WordSets:
         return out
 
 
+class CaptionEmbeddings:
+    """Sentence embeddings of every text of a SupCon table, for the cosine mask (SimilarityCalculator.sentence_trans /
+    bert_embedd, supcon_utils.py:140-168).  The encoder is not run here: the embeddings are computed once, offline, with
+    any sentence encoder and read from a file.  table [rows, 4, D] fp32; text (row, column) as in WordSets (0 = caption,
+    1..3 = the translations of CSV columns 3..5).  On the host the table holds the embeddings as given; .to(device)
+    uploads it once and scales every text to unit length there (mmvqa_normalize_rows), which is the form
+    mmvqa_cosine_mask reads.  Held whole on every rank: rows x 4 x D x 4 bytes."""
+
+    TEXTS = 4
+    MAX_DIM = 4096
+
+    def __init__(self, table, normalised=False):
+        self.table, self.normalised = table, bool(normalised)
+        self.rows, self.dim = int(table.shape[0]), int(table.shape[2])
+
+    @classmethod
+    def from_array(cls, emb):
+        """emb [rows, 4, D], float16 / float32 / float64 (numpy or torch), finite -> held as fp32 on the host"""
+        emb = emb.detach().cpu().numpy() if isinstance(emb, torch.Tensor) else np.asarray(emb)
+        if emb.ndim != 3 or emb.shape[1] != cls.TEXTS:
+            raise ValueError(f"CaptionEmbeddings: embeddings must be [rows, {cls.TEXTS}, D] (caption and three "
+                             f"translations per row), got {list(emb.shape)}")
+        if emb.dtype not in (np.float16, np.float32, np.float64):
+            raise ValueError(f"CaptionEmbeddings: embeddings must be float16, float32 or float64, got {emb.dtype}")
+        if emb.shape[0] < 1 or not 1 <= emb.shape[2] <= cls.MAX_DIM:
+            raise ValueError(f"CaptionEmbeddings: need at least one row and 1 <= D <= {cls.MAX_DIM}, got {list(emb.shape)}")
+        emb = np.ascontiguousarray(emb, dtype=np.float32)
+        if not np.isfinite(emb).all():
+            raise ValueError("CaptionEmbeddings: the embeddings hold non-finite values")
+        return cls(torch.from_numpy(emb))
+
+    @classmethod
+    def from_file(cls, path, table):
+        """path: an .npz with `names` (image file names, a unicode array) and `emb` [len(names), 4, D]; table: rows of
+        roco_supcon_table.  Row r of the result is the entry named like the base name of table[r]'s image, so the file
+        may hold more rows than the table keeps, in any order."""
+        with np.load(path, allow_pickle=False) as z:
+            for key in ("names", "emb"):
+                if key not in z.files:
+                    raise ValueError(f"{path}: no array {key!r} (needs names [R] and emb [R, 4, D])")
+            names, emb = z["names"], z["emb"]
+        if names.ndim != 1 or names.dtype.kind != "U":
+            raise ValueError(f"{path}: names must be a one-dimensional unicode array, got {names.dtype} {list(names.shape)}")
+        if emb.ndim != 3 or emb.shape[1] != cls.TEXTS or emb.shape[0] != len(names):
+            raise ValueError(f"{path}: emb must be [{len(names)}, {cls.TEXTS}, D] (one row per name), got {list(emb.shape)}")
+        if emb.dtype.kind != "f":
+            raise ValueError(f"{path}: emb must be float16, float32 or float64, got {emb.dtype}")
+        where = {}
+        for k, name in enumerate(names.tolist()):
+            if where.setdefault(name, k) != k:
+                raise ValueError(f"{path}: name {name!r} appears more than once (entries {where[name]} and {k})")
+        want = [os.path.basename(str(r[0])) for r in table]
+        missing = [w for w in want if w not in where]
+        if missing:
+            raise ValueError(f"{path}: no embeddings for {len(missing)} of the table's {len(want)} rows: "
+                             + ", ".join(missing[:5]) + (" ..." if len(missing) > 5 else ""))
+        try:
+            return cls.from_array(emb[np.asarray([where[w] for w in want], dtype=np.int64)])
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
+
+    def to(self, device, eps=1e-8):
+        """the table on `device`, every text scaled to x / max(|x|, eps) there (once; on the current stream)"""
+        from . import _lib as L
+        if self.normalised:
+            return CaptionEmbeddings(self.table.to(device), True)
+        t = self.table.to(device).contiguous()
+        if not t.is_cuda:
+            raise L.MMVQAError("CaptionEmbeddings.to: the table is normalised by a HIP kernel (no CPU fallback); "
+                               "cosine_host gives the mask from the host copy")
+        if t.data_ptr() == self.table.data_ptr():
+            t = t.clone()
+        with torch.cuda.device(t.device):
+            L.check(L.lib().mmvqa_normalize_rows(L.stream_ptr(), L.ptr(t), self.rows * self.TEXTS, self.dim, float(eps)))
+        return CaptionEmbeddings(t, True)
+
+    def cosine_host(self, rows_a, cols_a, rows_b, cols_b, eps=1e-8):
+        """the mask mmvqa_cosine_mask computes, in numpy float64 from the host copy (tests, and the DDP rehearsal on
+        CPU): a / max(|a|, eps) . b / max(|b|, eps), diagonal 1 (supcon_utils.py:152-159)"""
+        if self.normalised or self.table.is_cuda:
+            raise ValueError("CaptionEmbeddings.cosine_host: needs the host copy of the embeddings as given")
+        t = self.table.numpy()
+        unit = lambda x: x / np.maximum(np.sqrt((x * x).sum(1, keepdims=True)), eps)   # noqa: E731
+        a = unit(t[np.asarray(rows_a, dtype=np.int64), np.asarray(cols_a, dtype=np.int64)].astype(np.float64))
+        b = unit(t[np.asarray(rows_b, dtype=np.int64), np.asarray(cols_b, dtype=np.int64)].astype(np.float64))
+        out = np.einsum("ik,jk->ij", a, b)
+        np.fill_diagonal(out, 1.0)
+        return out
+
+
 def vqa_tables(root):
     """-> (columns, {"train", "val", "test": [row]}, idx2ans).  A row is (image path, question, answer index, category,
     mode) -- the fields evaluate.write_test_files writes."""

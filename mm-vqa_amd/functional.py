@@ -8,6 +8,7 @@
   CategorySmoothing, LabelSmoothing -- the two --smoothing criteria of vqamed2019/train.py:164-174 over it
   supcon_loss   -- models/SupConLoss/loss.py:21-98: features only (SimCLR), or with labels / a positive mask
   jaccard_mask  -- models/SupConLoss/supcon_utils.py:110-138 from word-id sets resident on the device
+  embedding_mask -- models/SupConLoss/supcon_utils.py:140-168 from precomputed sentence embeddings resident on the device
   split_feat    -- models/SupConLoss/supcon_utils.py:259-261
 """
 from __future__ import annotations
@@ -316,6 +317,31 @@ def jaccard_mask(words, rows_a, cols_a, rows_b=None, cols_b=None):
     mask = torch.empty(n, n, dtype=torch.float32, device=words.offsets.device)
     L.check(L.lib().mmvqa_jaccard_mask(L.stream_ptr(), L.ptr(words.offsets), L.ptr(words.ids), *(L.ptr(t) for t in args),
                                        L.ptr(mask), n, words.rows))
+    return mask
+
+
+def embedding_mask(emb, rows_a, cols_a, rows_b=None, cols_b=None):
+    """SimilarityCalculator.sentence_trans / bert_embedd (supcon_utils.py:140-168) on the device -> [n, n] fp32:
+    mask[i][j] = 1 for i == j, else the cosine of the embeddings of text (rows_a[i], cols_a[i]) and text
+    (rows_b[j], cols_b[j]) in `emb`, a data.CaptionEmbeddings moved to the device with .to(device), which normalised it
+    (column 0 = caption, 1..3 = translations).  rows_* / cols_* are int32 device tensors [n]; rows_b defaults to rows_a.
+    Cosines may be negative and are used as they are, as in the reference.  Within (2 D + 8) 2^-24 of the exact cosine;
+    the same inputs give the same bits on every launch.  Runs on the current stream; nothing is synchronised."""
+    rows_b = rows_a if rows_b is None else rows_b
+    if cols_b is None:
+        raise ValueError("embedding_mask: cols_b (the translation column each sample drew) is required")
+    if not emb.table.is_cuda or not emb.normalised:
+        raise L.MMVQAError("embedding_mask: GPU tensors only (no CPU fallback); move the CaptionEmbeddings with "
+                           ".to(device), which also normalises them")
+    n = rows_a.shape[0]
+    args = []
+    for t in (rows_a, cols_a, rows_b, cols_b):
+        if t.dtype != torch.int32 or t.device != emb.table.device or t.shape != (n,):
+            raise ValueError("embedding_mask: rows / cols must be int32 tensors [n] on the device of the embeddings")
+        args.append(t.contiguous())
+    mask = torch.empty(n, n, dtype=torch.float32, device=emb.table.device)
+    L.check(L.lib().mmvqa_cosine_mask(L.stream_ptr(), L.ptr(emb.table), *(L.ptr(t) for t in args), L.ptr(mask), n,
+                                      emb.dim, emb.rows))
     return mask
 
 

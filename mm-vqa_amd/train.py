@@ -26,6 +26,8 @@ torch.distributed (RCCL).
     python -m mmvqa_amd.train mlm    --data_dir roco-dataset/data --vocab_file vocab.txt --num_workers 4
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --batch_size 32
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --supcon_mask jaccard
+    python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --supcon_mask embeddings \\
+                                     --caption_embeddings roco_train_embeddings.npz
 """
 from __future__ import annotations
 
@@ -37,8 +39,8 @@ import torch
 import torch.distributed as dist
 from torch.optim import lr_scheduler
 
-from . import (CategorySmoothing, FusedAdam, LabelSmoothing, Model, asl_loss, checkpoint, evaluate, jaccard_mask, mlm_loss,
-               split_feat, supcon_loss, synth)
+from . import (CategorySmoothing, FusedAdam, LabelSmoothing, Model, asl_loss, checkpoint, embedding_mask, evaluate,
+               jaccard_mask, mlm_loss, split_feat, supcon_loss, synth)
 from . import data as D
 from .amp import GradScaler
 from .ddp import GradReducer, comm_info, global_supcon_pairs, global_supcon_views, sync_replicas
@@ -116,18 +118,24 @@ def roco_feeders(args, ctx):
 
 def roco_supcon_feeders(args, ctx, pairs):
     """(train, validation) feeders of SupCon: `pairs` samples x 2 views per train batch (roco_supcon_train.py:134-139,
-    drop_last=False), the plain ROCO validation split at the full --batch_size.  With --supcon_mask jaccard the train
-    batches carry each sample's (row, translation column) and the third value is the table's word sets on the device
-    (else None)."""
+    drop_last=False), the plain ROCO validation split at the full --batch_size.  With --supcon_mask jaccard or
+    embeddings the train batches carry each sample's (row, translation column) and the third value is what the mask is
+    built from, on the device: the table's word sets, or its caption embeddings read from --caption_embeddings and
+    normalised (else None)."""
     tok, kw = tokenizer(args), D.load_keywords(args.data_dir)
     table = D.roco_supcon_table(args.data_dir)
-    jac = getattr(args, "supcon_mask", "none") == "jaccard"
-    words = D.WordSets.from_table(table).to(ctx.dev) if jac else None
+    kind = getattr(args, "supcon_mask", "none")
+    masked = kind != "none"
+    words = None
+    if kind == "jaccard":
+        words = D.WordSets.from_table(table).to(ctx.dev)
+    elif kind == "embeddings":
+        words = D.CaptionEmbeddings.from_file(args.caption_embeddings, table).to(ctx.dev)
     tr = D.RocoSupConDataset(table, tok, kw, args.num_vis, args.max_position_embeddings, args.mlm_prob, args.seed,
-                             report_aug_col=jac)
+                             report_aug_col=masked)
     va = D.RocoDataset(D.roco_table(args.data_dir, "validation"), tok, kw, args.num_vis, args.max_position_embeddings,
                        args.mlm_prob, args.seed)
-    return feeder(args, ctx, tr, True, D.ROCO_AUG, batch_size=pairs, views=2, pairs=jac), feeder(args, ctx, va, False), words
+    return feeder(args, ctx, tr, True, D.ROCO_AUG, batch_size=pairs, views=2, pairs=masked), feeder(args, ctx, va, False), words
 
 
 def epoch_batches(fd, epoch, synthetic):
@@ -280,7 +288,9 @@ def supcon_step(model, opt, red, world, batch, words=None):
     a mask => SimCLR, :287); under DDP the views of all ranks are gathered first.  Returns (loss, pred, stats).
     With `words` (--supcon_mask jaccard: the table's WordSets on the device) the batch is the feeder's 6-tuple and the
     loss is the call the reference leaves in a comment, supcon_loss(feat, mask=mask) with buildMask's Jaccard matrix
-    (:276-287): caption of sample i against the translation sample j drew.  Under DDP the (row, column) pairs of all
+    (:276-287): caption of sample i against the translation sample j drew.  When `words` is a data.CaptionEmbeddings
+    (--supcon_mask embeddings) the mask is the cosine of the two texts' sentence embeddings instead, as
+    sentence_trans(caption, aug) gives it (:162-168).  Under DDP the (row, column) pairs of all
     ranks are gathered and every rank builds the global mask, in the sample order of the gathered features; gather and
     mask launch go on the step's stream."""
     img, ids, seg, mask, tgt = batch[:5]
@@ -293,7 +303,8 @@ def supcon_step(model, opt, red, world, batch, words=None):
         loss = loss_mlm + supcon_loss(feat)        # 2N*world rows: the tiled kernel has no size cap
     else:
         rows, cols = global_supcon_pairs(*batch[5])
-        pos = jaccard_mask(words, rows, torch.zeros_like(cols), rows, cols)
+        build_mask = embedding_mask if isinstance(words, D.CaptionEmbeddings) else jaccard_mask
+        pos = build_mask(words, rows, torch.zeros_like(cols), rows, cols)
         loss = loss_mlm + supcon_loss(feat, mask=pos)
     loss.backward()
     red.allreduce()
@@ -640,10 +651,16 @@ def parse_args(argv=None):
         if mode == "supcon":
             p.add_argument("--con_task", type=str, default="supcon", choices=["simclr", "supcon"])
             p.add_argument("--similarity", type=str, default="sentence_transformers")      # accepted, not read
-            p.add_argument("--supcon_mask", type=str, default="none", choices=["none", "jaccard"],
+            p.add_argument("--supcon_mask", type=str, default="none", choices=["none", "jaccard", "embeddings"],
                            help="positives of the SupCon loss: none = the other view only (SimCLR, what the reference's "
                                 "loop runs); jaccard = caption / back-translation word overlap weights every pair "
-                                "(SimilarityCalculator.jaccard), built on the GPU per batch.  Needs --data_dir")
+                                "(SimilarityCalculator.jaccard); embeddings = the cosine of the two texts' sentence "
+                                "embeddings (SimilarityCalculator.sentence_trans) from --caption_embeddings.  Either "
+                                "mask is built on the GPU per batch and needs --data_dir")
+            p.add_argument("--caption_embeddings", type=str, default=None, metavar="FILE",
+                           help="with --supcon_mask embeddings: an .npz of precomputed sentence embeddings, names [R] "
+                                "(image file names) and emb [R, 4, D] (caption and the three translations); no "
+                                "encoder is run here")
     else:
         p.add_argument("--lr", type=float, default=1e-4)
         p.add_argument("--max_position_embeddings", type=int, default=28)
@@ -677,6 +694,11 @@ def parse_args(argv=None):
             p.error(f"--con_task simclr contradicts --supcon_mask {args.supcon_mask}: SimCLR has no positive mask")
         if not args.data_dir:
             p.error(f"--supcon_mask {args.supcon_mask} needs --data_dir: synthetic batches have no captions to compare")
+    if mode == "supcon":
+        if args.supcon_mask == "embeddings" and not args.caption_embeddings:
+            p.error("--supcon_mask embeddings needs --caption_embeddings FILE (the precomputed sentence embeddings)")
+        if args.supcon_mask != "embeddings" and args.caption_embeddings:
+            p.error(f"--caption_embeddings is read by --supcon_mask embeddings only, not by --supcon_mask {args.supcon_mask}")
     return mode, args
 
 

@@ -20,6 +20,14 @@ unmasked loss) against the same fed step without it, alternating blocks in one p
 launch and of the masked loss (forward + gradient) next to the unmasked loss, alone on an idle device.
 
     python tools/feeder_bench.py --config 4 --supcon_mask jaccard --out profiles/supcon_mask_cfg4.json
+
+--config 4 --supcon_mask embeddings: the same with a third kind of block, the step under the caption-embedding mask
+(train.py --supcon_mask embeddings: mmvqa_cosine_mask over a resident table of random non-negative 768-wide embeddings
+for the generated table), alternating unmasked / jaccard / embeddings blocks in one process; the cosine launch alone at
+(n, D) = (16, 768) and (128, 768) next to the Jaccard launch; and the one-off upload + normalisation of a
+65 536-row x 768 table.
+
+    python tools/feeder_bench.py --config 4 --supcon_mask embeddings --out profiles/supcon_embed_cfg4.json
 """
 import argparse
 import json
@@ -71,7 +79,8 @@ def cpu_seconds(pid):
 
 
 def mask_bench(a, dev, tmp, model, opt, red, tok, fd, T_):
-    """fed config-4 step with / without the Jaccard mask, and the two new launches alone"""
+    """fed config-4 step with / without the Jaccard mask (and, with --supcon_mask embeddings, under the
+    caption-embedding mask), and the mask / loss launches alone"""
     import mmvqa_amd
     from mmvqa_amd import _lib as L
     from mmvqa_amd import data as D
@@ -95,6 +104,14 @@ def mask_bench(a, dev, tmp, model, opt, red, tok, fd, T_):
             epoch += 1
 
     gens = {"unmasked": (batches(fd), None), "masked": (batches(fdm), words)}
+    embed = a.supcon_mask == "embeddings"
+    De = 768                                     # all-mpnet-base-v2, the reference's default encoder
+    if embed:                                    # a second feeder with pairs: every kind of block draws its own batches
+        erng = np.random.default_rng(2)
+        host_emb = D.CaptionEmbeddings.from_array((np.abs(erng.standard_normal((len(table), 4, De))) + 0.25).astype(np.float32))
+        emb = host_emb.to(dev)
+        hoste = D.HostLoader(ds, B, shuffle=True, seed=1, num_workers=a.workers, aug=D.ROCO_AUG, size=HW, views=2)
+        gens["embeddings"] = (batches(D.DeviceFeeder(hoste, dev, depth=2, pairs=True)), emb)
 
     def run(n, kind):
         g, w = gens[kind]
@@ -137,6 +154,9 @@ def mask_bench(a, dev, tmp, model, opt, red, tok, fd, T_):
             "unmasked_loss_fwd_bwd": lambda: lib.mmvqa_supcon_loss(sp, L.ptr(f), L.ptr(loss), L.ptr(df), L.ptr(ws), n, Dm,
                                                                    0.07, 0.07, 1.0),
         }
+        if embed:
+            calls[f"cosine_mask_D{De}"] = lambda: lib.mmvqa_cosine_mask(sp, L.ptr(emb.table), L.ptr(rows), L.ptr(zero),
+                                                                        L.ptr(rows), L.ptr(cols), L.ptr(mask), n, De, emb.rows)
         for key, call in calls.items():
             ts = []
             for r in range(a.aug_reps + 3):
@@ -153,14 +173,41 @@ def mask_bench(a, dev, tmp, model, opt, red, tok, fd, T_):
             alone[f"{key}_n{n}"] = round(statistics.median(ts), 4)
     un, ma = statistics.median(res["unmasked"]), statistics.median(res["masked"])
     spread = max(res["unmasked"]) - min(res["unmasked"])
+    extra = {}
+    if embed:
+        em = statistics.median(res["embeddings"])
+        # the one-off cost of a ROCO-sized table: 65 536 rows x 4 texts x 768 floats = 0.8 GB, upload + normalise
+        big = D.CaptionEmbeddings(torch.rand(65536, 4, De).pin_memory())
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        big_dev = big.to(dev)
+        torch.cuda.synchronize()
+        to_ms = 1e3 * (time.perf_counter() - t0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        L.check(L.lib().mmvqa_normalize_rows(L.stream_ptr(), L.ptr(big_dev.table), big.rows * 4, De, 1e-8))
+        e1.record()
+        e1.synchronize()
+        extra = dict(embeddings_ms_per_step=round(em, 3), embeddings_minus_unmasked_ms=round(em - un, 3),
+                     embeddings_minus_jaccard_ms=round(em - ma, 3), embeddings_within_unmasked_spread=bool(em - un <= spread),
+                     caption_embeddings=dict(table_rows=host_emb.rows, D=De, mbytes=round(host_emb.table.numel() * 4 / 2 ** 20, 2),
+                                             roco_sized_table_rows=65536, roco_sized_table_mbytes=round(65536 * 4 * De * 4 / 2 ** 20, 1),
+                                             roco_sized_to_device_ms=round(to_ms, 1),
+                                             roco_sized_normalize_rows_ms=round(e0.elapsed_time(e1), 3),
+                                             note="to_device = CaptionEmbeddings.to(device) from pinned host memory, upload "
+                                                  "+ mmvqa_normalize_rows, wall time to completion, once; normalize_rows = "
+                                                  "the kernel alone on that table (events)"))
+        del big, big_dev
     out = dict(
         workload="config 4 (tf_efficientnetv2_m + realformer + SupCon head, ROCO MLM + SupCon), 16 pairs = 32 views, 224^2, "
                  f"T 32, one GPU, fed by a DeviceFeeder (depth 2, views 2) over {a.images} generated JPEGs; unmasked = "
                  "supcon_step as train.py runs it without --supcon_mask (the launches of the default path); masked = "
-                 "--supcon_mask jaccard: feeder with pairs, mmvqa_jaccard_mask, mmvqa_supcon_loss_masked",
+                 "--supcon_mask jaccard: feeder with pairs, mmvqa_jaccard_mask, mmvqa_supcon_loss_masked"
+                 + ("; embeddings = --supcon_mask embeddings: feeder with pairs, mmvqa_cosine_mask over a resident "
+                    f"[{len(table)}, 4, {De}] table of random non-negative embeddings, mmvqa_supcon_loss_masked" if embed else ""),
         unmasked_ms_per_step=round(un, 3), masked_ms_per_step=round(ma, 3), ratio=round(ma / un, 4),
         unmasked_block_spread_ms=round(spread, 3), masked_minus_unmasked_ms=round(ma - un, 3),
-        within_unmasked_spread=bool(ma - un <= spread),
+        within_unmasked_spread=bool(ma - un <= spread), **extra,
         blocks={k: [round(x, 3) for x in v] for k, v in res.items()}, steps_per_block=a.steps, workers=host.num_workers,
         word_sets=dict(table_rows=host_words.rows, ids=int(host_words.ids.numel()), words=len(host_words.vocab),
                        host_build_ms=round(words_ms, 3)),
@@ -185,8 +232,9 @@ def main():
     ap.add_argument("--workers", type=int, default=None)
     ap.add_argument("--aug_reps", type=int, default=20)
     ap.add_argument("--out", type=str, default=None)
-    ap.add_argument("--supcon_mask", type=str, default="none", choices=["none", "jaccard"],
-                    help="jaccard (with --config 4): time the fed step with the Jaccard mask against the one without")
+    ap.add_argument("--supcon_mask", type=str, default="none", choices=["none", "jaccard", "embeddings"],
+                    help="jaccard (with --config 4): time the fed step with the Jaccard mask against the one without; "
+                         "embeddings: also the step with the caption-embedding mask, and the cosine launch")
     a = ap.parse_args()
     if a.supcon_mask != "none" and a.config != 4:
         ap.error("--supcon_mask needs --config 4 (the SupCon step)")
@@ -237,7 +285,7 @@ def main():
         ds = D.RocoDataset(D.roco_table(tmp, "train"), tok, D.load_keywords(tmp), 5, T, 0.15, seed=1)
     host = D.HostLoader(ds, B, shuffle=True, seed=1, num_workers=a.workers, aug=D.ROCO_AUG, size=HW, views=views)
     fd = D.DeviceFeeder(host, dev, depth=2)
-    if a.supcon_mask == "jaccard":
+    if a.supcon_mask != "none":
         return mask_bench(a, dev, tmp, model, opt, red, tok, fd, T)
 
     def fed_batches():
