@@ -192,7 +192,9 @@ typedef struct mmvqa_model_desc {
   int hidden, heads, n_layers;
   int emb_vocab, max_pos, type_vocab;
   int num_vis;
-  int head_kind;        /* 0 = roco (per-token MLM logits), 1 = VQA-Med (mean-pooled logits) */
+  int head_kind;        /* 0 = roco (per-token MLM logits), 1 = VQA-Med (mean-pooled logits), 2 = headless (roco with
+                         * task 'distillation', models/mmbert.py:159-161: the output is the encoder's h [B*T][hidden];
+                         * fc1 / classifier keep their parameters and never receive a gradient; supcon is ignored) */
   int n_classes;        /* width of classifier[2] */
   int supcon, feat_dim;
   int use_relu;
@@ -341,6 +343,26 @@ int mmvqa_cosine_mask(mmvqa_stream_t s, const float* table, const int* rowsA, co
 int mmvqa_soft_ce_loss(mmvqa_stream_t s, const float* logits, int ld, const long long* target, const long long* category,
                        const float* table, int table_ld, int n_cat, int mode, double smoothing, float* row_loss,
                        float* loss, float* dlogits, int dld, int rows, int C, float gscale);
+/* Distillation loss (pretrain/roco_train.py:94-95: nn.MSELoss; roco_utils.py:230-238: loss = MSELoss(h, target)) of the
+ * headless model's output h [B*T][ld] fp32 against the teacher's per-token states (roco_utils.py:112-132), forward AND
+ * backward in one launch plus a one-workgroup launch for the mean.  The states of every caption are resident on the
+ * device: table [table_rows][H], fp32 or (table_f16 = 1) fp16, a half converting to fp32 exactly; start[b] (int64) is the
+ * first table row of sample b's caption and count[b] (int32) its token count; first = num_vis + 2.  The dense target of
+ * encode_text's distillation branch (roco_utils.py:162-199) is never stored: row r = b*T + t has the target
+ * table[start[b] + t - first] for first <= t < first + n_b with n_b = min(count[b], T - first - 1) (the truncation of
+ * :175-176) and a ZERO target everywhere else (:196-197) -- CLS, the visual rows, both SEPs and the padding are trained
+ * towards zero, and the mean runs over all B*T*H elements (nn.MSELoss's default).
+ * row_sq[r] = sum_j (h - target)^2; *loss = (sum_r row_sq[r]) / (B*T*H), added in a fixed order (bit-equal from run to
+ * run); dh (nullable) [B*T][dld] = (h - target) * gscale, one subtraction and one multiplication in fp32 -- the caller
+ * passes gscale = float(2 * upstream / (B*T*H)).  A sample with start < 0, count < 0 or start + n_b > table_rows gets NaN
+ * in all its row_sq and dh rows and reads nothing from the table.  16-byte accesses of h / dh and whole-vector loads of
+ * the table (16 bytes fp32, 8 bytes fp16) when H % 4 == 0, ld and dld are multiples of 4 and the bases are aligned to
+ * the access; one element at a time otherwise.  With H % 4 == 0 no column lies between H and round_up(H, 4); columns
+ * from H on are not written.  Refused on the host with MMVQA_ERR_ARG before any HIP call: a null h / table / start /
+ * count / row_sq / loss, B, T, H or table_rows < 1, first outside [0, T), ld < H, dld < H with dh. */
+int mmvqa_distill_mse(mmvqa_stream_t s, const float* h, int ld, const void* table, int table_f16, long long table_rows,
+                      const long long* start, const int* count, int first, int B, int T, int H, float* row_sq, float* loss,
+                      float* dh, int dld, float gscale);
 /* ---- EfficientNetV2 (timm tf_efficientnetv2_m as models/image_encoding.py:15,26,100-115 instantiates it) pieces,
  * NHWC fp32; sc/sh = BatchNorm scale/shift of the producing conv (applied on load), stat = [16][C][2] doubles.
  * depthwise 3x3 (MBConv conv_dw): z2 = dw(silu(z1*s1+b1)), statistics of z2; TF "SAME" padding via pad (begin) */
@@ -454,7 +476,9 @@ size_t mmvqa_engine_plan(mmvqa_engine* e, int B, int T, int img_h, int img_w);
 int mmvqa_engine_bind(mmvqa_engine* e, float* params, float* grads, float* bufs, long long* nbt, void* workspace,
                       size_t workspace_bytes);
 /* img fp32 NCHW [B,3,h,w]; ids/seg/mask int64 [B,T]; logits [rows][ld] (rows = B*T or B);
- * feat [B][feat_dim] or NULL.  training != 0: batch-stat BN + dropout with `seed`. */
+ * feat [B][feat_dim] or NULL.  training != 0: batch-stat BN + dropout with `seed`.
+ * head_kind 2: `logits` receives the encoder output h [B*T][ld], ld >= hidden and ld % 4 == 0 (columns from hidden on are
+ * not written), and mmvqa_engine_backward takes the gradient of that buffer in the same layout. */
 int mmvqa_engine_forward(mmvqa_engine* e, mmvqa_stream_t s, const float* img, const long long* ids,
                          const long long* seg, const long long* mask, float* logits, int logits_ld, float* feat,
                          int training, uint32_t seed);

@@ -21,6 +21,7 @@ PRO_NONE, PRO_AFFINE_RELU, PRO_DZ, PRO_AFFINE, PRO_AFFINE_SILU, PRO_SILU_GATE = 
 EPI_PLAIN, EPI_TAP_FWD, EPI_TAP_BWD = 0, 1, 2
 PREC_F32, PREC_F16 = 0, 1   # mmvqa_gemm_desc.reserved0 / mmvqa_engine_set_precision
 SOFT_CE_HARD, SOFT_CE_UNIFORM, SOFT_CE_CATEGORY = 0, 1, 2   # mmvqa_soft_ce_loss modes
+HEAD_MLM, HEAD_VQA, HEAD_NONE = 0, 1, 2   # mmvqa_model_desc.head_kind
 STAT_SLOTS = 16
 
 
@@ -138,6 +139,7 @@ SIGNATURES = {
     "mmvqa_normalize_rows": (_i, [_P, _P, _ll, _i, _f]),
     "mmvqa_cosine_mask": (_i, [_P] * 7 + [_i, _i, _i]),
     "mmvqa_soft_ce_loss": (_i, [_P, _P, _i, _P, _P, _P, _i, _i, _i, _d, _P, _P, _P, _i, _i, _i, _f]),
+    "mmvqa_distill_mse": (_i, [_P, _P, _i, _P, _i, _ll, _P, _P, _i, _i, _i, _i, _P, _P, _P, _i, _f]),
     "mmvqa_dwconv_fwd": (_i, [_P, _P, _P, _P, _P, _P, _P] + [_i] * 8),
     "mmvqa_dwconv_bwd_data": (_i, [_P] * 14 + [_i] * 8),
     "mmvqa_dwconv_bwd_weight": (_i, [_P] * 10 + [_i] * 8),

@@ -175,6 +175,12 @@ int mmvqa_soft_ce_loss(mmvqa_stream_t s, const float* logits, int ld, const long
   return k_soft_ce(ST(s), logits, ld, target, category, table, table_ld, n_cat, mode, smoothing, row_loss, loss, dlogits,
                    dld, rows, C, gscale);
 }
+int mmvqa_distill_mse(mmvqa_stream_t s, const float* h, int ld, const void* table, int table_f16, long long table_rows,
+                      const long long* start, const int* count, int first, int B, int T, int H, float* row_sq, float* loss,
+                      float* dh, int dld, float gscale) {
+  return k_distill_mse(ST(s), h, ld, table, table_f16, table_rows, start, count, first, B, T, H, row_sq, loss, dh, dld,
+                       gscale);
+}
 int mmvqa_dwconv_fwd(mmvqa_stream_t s, const float* z1, const float* s1, const float* b1, const float* w, float* z2,
                      double* stat, int N, int H, int W, int C, int OH, int OW, int stride, int pad) {
   return k_dwconv_fwd(ST(s), z1, s1, b1, w, z2, stat, N, H, W, C, OH, OW, stride, pad);

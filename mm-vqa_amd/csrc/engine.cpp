@@ -1712,6 +1712,18 @@ static int heads_backward(mmvqa_engine* e, hipStream_t st, const float* h, const
   return MMVQA_OK;
 }
 
+// rows x cols floats between two row-major buffers on `st`.  Equal leading dimensions (what the Python shim passes:
+// hidden is a multiple of 8) make it one linear copy, which the runtime enqueues without waiting for the stream; the
+// strided form is correct for any ld but the runtime may hold the host until the stream has drained.
+static int copy_rows(hipStream_t st, float* dst, size_t dst_ld, const float* src, size_t src_ld, size_t rows, size_t cols) {
+  if (dst_ld == cols && src_ld == cols)
+    HIP_CHECK_RET(hipMemcpyAsync(dst, src, rows * cols * sizeof(float), hipMemcpyDeviceToDevice, st));
+  else
+    HIP_CHECK_RET(hipMemcpy2DAsync(dst, dst_ld * sizeof(float), src, src_ld * sizeof(float), cols * sizeof(float), rows,
+                                   hipMemcpyDeviceToDevice, st));
+  return MMVQA_OK;
+}
+
 // --------------------------------------------------------------------------- whole model
 // State that lives in the caller's workspace ACROSS calls (mmvqa.h, mmvqa_engine_bind): the tap-validity tables of the
 // 3x3 weight gradients and the (zero) arrival tickets of the ticketed split-K launches.  Put in place on the caller's stream
@@ -1738,8 +1750,10 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
   if (!e->planned || !e->bound) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_forward: plan/bind first");
   TRY(prepare_workspace(e, st));
   const mmvqa_model_desc& d = e->d;
-  if (logits_ld < d.n_classes || (logits_ld & 3))
-    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward: logits_ld=%d must be >= n_classes and %%4==0", logits_ld);
+  const int out_w = d.head_kind == 2 ? d.hidden : d.n_classes;   // headless: the caller's buffer receives h
+  if (logits_ld < out_w || (logits_ld & 3))
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward: logits_ld=%d must be >= %s=%d and %%4==0", logits_ld,
+                           d.head_kind == 2 ? "hidden" : "n_classes", out_w);
   e->img = img; e->ids = ids; e->seg = seg; e->mask = mask;
   e->logits = logits; e->logits_ld = logits_ld; e->feat = feat;
   e->training = training; e->seed = seed;
@@ -1760,6 +1774,9 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
   if (d.encoder == 0) TRY(bert_forward(e, st, WS(e->emb_out), &h));
   else TRY(rf_forward(e, st, WS(e->emb_out), &h));
   e->enc_out_final = (size_t)(h - e->ws);
+  if (d.head_kind == 2) {   // models/mmbert.py:159-161: logits = h; fc1 / classifier / head are not run
+    return copy_rows(st, logits, (size_t)logits_ld, h, (size_t)d.hidden, (size_t)e->B * e->T, (size_t)d.hidden);
+  }
   return heads_forward(e, st, h);
 }
 
@@ -1774,7 +1791,15 @@ int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int d
   const float* h = WS(e->enc_out_final);
   SideCtx sc_enc(e, st);
   SideReads sr(sc_enc);
-  TRY(heads_backward(e, st, h, dlogits, dl_ld, dfeat, sr));
+  if (d.head_kind == 2) {
+    // the caller's gradient IS dh: it goes where heads_backward leaves it; the head parameters' gradient ranges are not
+    // touched and are announced with the encoder's below, as always
+    if (dl_ld < d.hidden)
+      return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward: dlogits_ld=%d < hidden=%d", dl_ld, d.hidden);
+    TRY(copy_rows(st, WS(e->t_a), (size_t)d.hidden, dlogits, (size_t)dl_ld, (size_t)e->B * e->T, (size_t)d.hidden));
+  } else {
+    TRY(heads_backward(e, st, h, dlogits, dl_ld, dfeat, sr));
+  }
   if (d.encoder == 0) TRY(bert_backward(e, st, WS(e->emb_out), sr));
   else TRY(rf_backward(e, st, WS(e->emb_out), sr));
   if (e->grad_cb) {
@@ -1824,6 +1849,7 @@ int engine_backward_feature(mmvqa_engine* e, hipStream_t st, const float* dlogit
   if (e->prec != MMVQA_PREC_F32)
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward_feature: attribution runs with fp32 operands, not in the f16 operand mode");
   const mmvqa_model_desc& d = e->d;
+  if (d.head_kind == 2) return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward_feature: the headless model has no logits");
   if (!dlogits || !dA) return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward_feature: null pointer");
   if (dl_ld < d.n_classes || (dl_ld & 3))
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward_feature: dlogits_ld=%d must be >= n_classes and %%4==0", dl_ld);
@@ -1855,8 +1881,11 @@ int engine_create(const mmvqa_model_desc* desc, mmvqa_engine** out) {
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_create: heads=%d does not divide hidden=%d", d.heads, d.hidden);
   if (d.cnn == 0 && d.resnet_width % 8 != 0)
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_create: resnet_width=%d must be a multiple of 8", d.resnet_width);
+  if (d.head_kind < 0 || d.head_kind > 2)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_create: head_kind=%d (0 = MLM, 1 = VQA, 2 = headless)", d.head_kind);
   mmvqa_engine* e = new mmvqa_engine();
   e->d = d;
+  if (d.head_kind == 2) e->d.supcon = 0;   // models/mmbert.py:159-161 returns h alone, whatever args.supcon says
   if (getenv("MMVQA_NO_SIDE_STREAM")) e->use_side = 0;   // A/B switch: everything on the caller's stream
   if (getenv("MMVQA_NO_BN_FOLD")) e->bn_fold = 0;        // A/B switch: separate BatchNorm coefficient launches everywhere
   memset(e->prof_launch, 0, sizeof(e->prof_launch));

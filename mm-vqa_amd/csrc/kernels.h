@@ -83,6 +83,10 @@ int k_cosine_mask(hipStream_t st, const float* table, const int* rowsA, const in
 int k_soft_ce(hipStream_t st, const float* logits, int ld, const long long* target, const long long* category,
               const float* table, int table_ld, int n_cat, int mode, double smoothing, float* row_loss, float* loss,
               float* dlogits, int dld, int rows, int C, float gscale);
+// distill.hip: MSE against teacher states gathered from a resident table (the distillation task), forward + backward
+int k_distill_mse(hipStream_t st, const float* h, int ld, const void* table, int table_f16, long long table_rows,
+                  const long long* start, const int* count, int first, int B, int T, int H, float* row_sq, float* loss,
+                  float* dh, int dld, float gscale);
 int k_adam(hipStream_t st, float* p, float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps,
            int step, float gscale, int zero_grad);
 int k_axpy(hipStream_t st, float* y, const float* x, float a, long n);

@@ -285,6 +285,143 @@ class CaptionEmbeddings:
         return out
 
 
+class TeacherStates:
+    """The teacher's per-token states of every caption of a ROCO table, for the distillation task
+    (pretrain/roco_utils.py:112-132: last_hidden_state[1:len-1] of the teacher on the caption, CLS and SEP dropped).
+    The teacher and its tokenizer are not run here: the states are computed once, offline, and read from a file.
+    Caption r owns ids[offsets[r]:offsets[r + 1]] (the teacher tokenizer's ids, without CLS / SEP -- the student is fed
+    exactly the tokens the teacher saw, roco_utils.py:130) and the rows of `states` [total, D] of the same range.
+    offsets / ids are int64 numpy arrays on the host; states is a torch tensor, float16 as given or fp32 (float32 and
+    float64 input), uploaded once by .to(device) and held whole on every rank: total x D x 2 or 4 bytes."""
+
+    def __init__(self, offsets, ids, states, cls_id=101, sep_id=102):
+        self.offsets, self.ids, self.states = offsets, ids, states
+        self.cls_id, self.sep_id = int(cls_id), int(sep_id)
+        self.rows, self.dim = len(offsets) - 1, int(states.shape[1])
+
+    @classmethod
+    def from_arrays(cls, offsets, ids, states, cls_id=101, sep_id=102):
+        """offsets [rows + 1] non-decreasing from 0, ids [total] integers, states [total, D] float16 / 32 / 64 (numpy or
+        torch), finite"""
+        as_np = lambda a: a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)   # noqa: E731
+        offsets, ids, states = as_np(offsets), as_np(ids), as_np(states)
+        if offsets.ndim != 1 or ids.ndim != 1 or states.ndim != 2:
+            raise ValueError(f"TeacherStates: offsets and ids must be one-dimensional and states [total, D], got "
+                             f"{list(offsets.shape)}, {list(ids.shape)}, {list(states.shape)}")
+        if offsets.dtype.kind not in "iu" or ids.dtype.kind not in "iu":
+            raise ValueError(f"TeacherStates: offsets and ids must be integer arrays, got {offsets.dtype} and {ids.dtype}")
+        if states.dtype not in (np.float16, np.float32, np.float64):
+            raise ValueError(f"TeacherStates: states must be float16, float32 or float64, got {states.dtype}")
+        offsets = offsets.astype(np.int64)
+        if len(offsets) < 1 or offsets[0] != 0 or (np.diff(offsets) < 0).any():
+            raise ValueError("TeacherStates: offsets must start at 0 and never decrease")
+        if not offsets[-1] == len(ids) == states.shape[0]:
+            raise ValueError(f"TeacherStates: offsets end at {int(offsets[-1])}, there are {len(ids)} ids and "
+                             f"{states.shape[0]} states (all three must agree)")
+        if states.shape[1] < 1:
+            raise ValueError("TeacherStates: the states have no columns")
+        if not np.isfinite(states).all():
+            raise ValueError("TeacherStates: the states hold non-finite values")
+        if states.dtype != np.float16:
+            states = states.astype(np.float32)
+        if states.shape[0] == 0:
+            states = np.zeros((1, states.shape[1]), dtype=states.dtype)   # never read (every caption is empty); keeps the pointer non-null
+        return cls(offsets, ids.astype(np.int64), torch.from_numpy(np.ascontiguousarray(states)), cls_id, sep_id)
+
+    @classmethod
+    def from_file(cls, path, table):
+        """path: an .npz (no pickled objects) with names [R] (image file names, a unicode array), offsets [R + 1], ids
+        [total], states [total, D] and optionally the scalars cls_id / sep_id (default 101 / 102); table: rows of
+        roco_table.  Caption r of the result is the entry named like the base name of table[r]'s image, so the file may
+        hold more entries than the table keeps, in any order."""
+        with np.load(path, allow_pickle=False) as z:
+            for key in ("names", "offsets", "ids", "states"):
+                if key not in z.files:
+                    raise ValueError(f"{path}: no array {key!r} (needs names [R], offsets [R + 1], ids [total] and "
+                                     "states [total, D])")
+            names, offs, ids, states = z["names"], z["offsets"], z["ids"], z["states"]
+            cls_id = int(z["cls_id"]) if "cls_id" in z.files else 101
+            sep_id = int(z["sep_id"]) if "sep_id" in z.files else 102
+        if names.ndim != 1 or names.dtype.kind != "U":
+            raise ValueError(f"{path}: names must be a one-dimensional unicode array, got {names.dtype} {list(names.shape)}")
+        if offs.ndim != 1 or ids.ndim != 1 or states.ndim != 2:
+            raise ValueError(f"{path}: offsets and ids must be one-dimensional and states [total, D], got "
+                             f"{list(offs.shape)}, {list(ids.shape)}, {list(states.shape)}")
+        if offs.dtype.kind not in "iu" or ids.dtype.kind not in "iu":
+            raise ValueError(f"{path}: offsets and ids must be integer arrays, got {offs.dtype} and {ids.dtype}")
+        if states.dtype.kind != "f":
+            raise ValueError(f"{path}: states must be float16, float32 or float64, got {states.dtype}")
+        if len(offs) != len(names) + 1:
+            raise ValueError(f"{path}: {len(offs)} offsets for {len(names)} names (needs one more than names)")
+        offs = offs.astype(np.int64)
+        if offs[0] != 0 or (np.diff(offs) < 0).any():
+            raise ValueError(f"{path}: offsets must start at 0 and never decrease")
+        if not offs[-1] == len(ids) == states.shape[0]:
+            raise ValueError(f"{path}: offsets end at {int(offs[-1])}, there are {len(ids)} ids and {states.shape[0]} "
+                             "states (all three must agree)")
+        where = {}
+        for k, name in enumerate(names.tolist()):
+            if where.setdefault(name, k) != k:
+                raise ValueError(f"{path}: name {name!r} appears more than once (entries {where[name]} and {k})")
+        want = [os.path.basename(str(r[0])) for r in table]
+        missing = [w for w in want if w not in where]
+        if missing:
+            raise ValueError(f"{path}: no teacher states for {len(missing)} of the table's {len(want)} rows: "
+                             + ", ".join(missing[:5]) + (" ..." if len(missing) > 5 else ""))
+        pick = np.asarray([where[w] for w in want], dtype=np.int64)
+        lens = offs[pick + 1] - offs[pick]
+        new = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        take = (np.concatenate([np.arange(offs[k], offs[k + 1]) for k in pick]) if len(pick) else np.zeros(0)).astype(np.int64)
+        try:
+            return cls.from_arrays(new, ids[take], states[take], cls_id, sep_id)
+        except ValueError as e:
+            raise ValueError(f"{path}: {e}") from None
+
+    def to(self, device):
+        """the states on `device` (one upload); offsets and ids stay on the host, where batch() reads them"""
+        return TeacherStates(self.offsets, self.ids, self.states.to(device), self.cls_id, self.sep_id)
+
+    def check_vocab(self, emb_vocab):
+        """every id the student will be fed must index its embedding table"""
+        bad = [i for i in (self.cls_id, self.sep_id) if not 0 <= i < emb_vocab]
+        if len(self.ids) and (self.ids.min() < 0 or self.ids.max() >= emb_vocab):
+            bad.append(int(self.ids.max() if self.ids.max() >= emb_vocab else self.ids.min()))
+        if bad:
+            raise ValueError(f"TeacherStates: token id {bad[0]} is outside the embedding table [0, {emb_vocab}) "
+                             "(--emb_vocab must be the teacher's vocabulary size)")
+
+    def encode(self, row, T, num_vis=5):
+        """one caption in encode_text's distillation layout (roco_utils.py:162-199) -> (ids, seg, mask) lists of T"""
+        lo, hi = int(self.offsets[row]), int(self.offsets[row + 1])
+        part2 = self.ids[lo:hi][:max(T - (num_vis + 3), 0)].tolist()                     # :174-175
+        tokens = [self.cls_id] + [0] * num_vis + [self.sep_id] + part2 + [self.sep_id]   # :178
+        seg = [0] * (num_vis + 2) + [1] * (len(part2) + 1)                                # :181
+        n_pad = T - len(tokens)
+        if n_pad < 0:
+            raise ValueError(f"TeacherStates: T={T} has no room for [CLS], {num_vis} visual tokens and two [SEP]")
+        return tokens + [0] * n_pad, seg + [0] * n_pad, [1] * len(tokens) + [0] * n_pad
+
+    def batch(self, rows, T, num_vis=5):
+        """-> host (ids, seg, mask) int64 [B, T], start int64 [B] (first row of each caption in `states`) and count
+        int32 [B] (its token count, not truncated: mmvqa_distill_mse clamps it to T - num_vis - 3)"""
+        enc = [self.encode(int(r), T, num_vis) for r in rows]
+        ids, seg, mask = (torch.tensor([e[k] for e in enc], dtype=torch.int64).reshape(len(enc), T) for k in range(3))
+        rows = np.asarray(rows, dtype=np.int64)
+        start = torch.from_numpy(self.offsets[rows].astype(np.int64))
+        count = torch.from_numpy((self.offsets[rows + 1] - self.offsets[rows]).astype(np.int32))
+        return ids, seg, mask, start, count
+
+    def target_host(self, rows, T, num_vis=5):
+        """the dense target of roco_utils.py:196-197 as float64 [B, T, D], from the host copy of the states (tests)"""
+        st = self.states.cpu().double()
+        out = torch.zeros(len(rows), T, self.dim, dtype=torch.float64)
+        for b, r in enumerate(rows):
+            lo = int(self.offsets[int(r)])
+            n = min(int(self.offsets[int(r) + 1]) - lo, max(T - (num_vis + 3), 0))
+            out[b, num_vis + 2:num_vis + 2 + n] = st[lo:lo + n]
+        return out
+
+
 def vqa_tables(root):
     """-> (columns, {"train", "val", "test": [row]}, idx2ans).  A row is (image path, question, answer index, category,
     mode) -- the fields evaluate.write_test_files writes."""
@@ -334,6 +471,27 @@ class RocoDataset(torch.utils.data.Dataset):
         ids, seg, mask, tgt = text.encode_text(caption, self.tok, self.kw, self.num_vis, self.T, self.mlm_prob,
                                                sample_rng(self.seed, epoch, idx))
         return decode(path), ids, seg, mask, tgt, idx
+
+
+class DistillDataset(torch.utils.data.Dataset):
+    """item (epoch, index) -> (uint8 [H, W, 3], ids, seg, mask, (start, count)) of the distillation task: the text is
+    TeacherStates.encode of the row's caption, and in the target's place travel the two integers that name the caption's
+    states in the resident table (int64 [2]; a batch's fifth tensor is int64 [B, 2]).  Only the teacher's offsets and
+    ids are kept here (the worker processes get a copy of the dataset): the states stay with the caller."""
+
+    def __init__(self, rows, teacher, num_vis=5, max_position_embeddings=75):
+        if teacher.rows != len(rows):
+            raise ValueError(f"DistillDataset: {len(rows)} table rows, teacher states of {teacher.rows} captions")
+        self.rows, self.num_vis, self.T = list(rows), num_vis, max_position_embeddings
+        self.text = TeacherStates(teacher.offsets, teacher.ids, torch.zeros(1, teacher.dim), teacher.cls_id, teacher.sep_id)
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __getitem__(self, key):
+        _epoch, idx = key
+        ids, seg, mask, start, count = self.text.batch([idx], self.T, self.num_vis)
+        return decode(self.rows[idx][0]), ids[0], seg[0], mask[0], torch.tensor([int(start[0]), int(count[0])]), idx
 
 
 def category_ids(rows):

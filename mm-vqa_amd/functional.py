@@ -10,6 +10,8 @@
   jaccard_mask  -- models/SupConLoss/supcon_utils.py:110-138 from word-id sets resident on the device
   embedding_mask -- models/SupConLoss/supcon_utils.py:140-168 from precomputed sentence embeddings resident on the device
   split_feat    -- models/SupConLoss/supcon_utils.py:259-261
+  distill_loss  -- pretrain/roco_utils.py:230-238 (nn.MSELoss against the teacher's states) with the target gathered from
+                   a table resident on the device, forward and gradient in one launch
 """
 from __future__ import annotations
 
@@ -164,6 +166,67 @@ def soft_ce_loss(logits, target, mode=L.SOFT_CE_HARD, smoothing=0.0, table=None,
         table = category = None
     want_grad = torch.is_grad_enabled() and logits.requires_grad
     return _SoftCE.apply(logits, target, int(mode), float(smoothing), table, category, want_grad)
+
+
+class _Distill(torch.autograd.Function):
+    """forward: one launch writes the rows' squared distances AND dh = (h - target) * 2 / (B T H) (saved), a
+    one-workgroup launch the mean; backward multiplies the saved dh by the upstream gradient, as _SoftCE does.
+    want_grad is decided by the caller (distill_loss)."""
+
+    @staticmethod
+    def forward(ctx, h, teacher, start, count, first, want_grad):
+        B, T, H = h.shape
+        x, ld = _padded(h.reshape(B * T, H))
+        row_sq = torch.empty(B * T, dtype=torch.float32, device=x.device)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        dh = torch.empty(B * T, (H + 3) & ~3, dtype=torch.float32, device=x.device) if want_grad else None
+        L.check(L.lib().mmvqa_distill_mse(L.stream_ptr(), L.ptr(x), ld, L.ptr(teacher), int(teacher.dtype == torch.float16),
+                                          teacher.shape[0], L.ptr(start), L.ptr(count), first, B, T, H, L.ptr(row_sq),
+                                          L.ptr(loss), L.ptr(dh), dh.stride(0) if want_grad else 0,
+                                          2.0 / (float(B) * T * H)))
+        if dh is not None:
+            ctx.save_for_backward(dh)
+        ctx.shape = (B, T, H)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        (dh,) = ctx.saved_tensors
+        B, T, H = ctx.shape
+        return (dh * gloss)[:, :H].reshape(B, T, H), None, None, None, None, None
+
+
+def distill_loss(h, teacher, start, count, num_vis=5):
+    """nn.MSELoss()(h, target) of the distillation task (pretrain/roco_train.py:94-95, roco_utils.py:230-238) for the
+    headless model's output h [B, T, hidden] (fp32, on the GPU), the target being encode_text's distillation layout
+    (roco_utils.py:162-199) gathered on the fly and never stored: rows num_vis + 2 .. num_vis + 2 + n_b - 1 of sample b
+    are teacher[start[b] .. start[b] + n_b - 1] with n_b = min(count[b], T - num_vis - 3), every other row is zero, and
+    the mean runs over all B T hidden elements.  teacher: the per-token states of every caption, [rows, hidden] fp32 or
+    fp16 on h's device (a data.TeacherStates moved with .to(device), or its .states); start int64 [B] (first row of each
+    sample's caption), count int32 [B] (its token count), both on the device.  A sample whose rows leave the table makes
+    the loss (and that sample's gradient) NaN; nothing is read outside the table.  Runs on the current stream, nothing is
+    synchronised; the loss is bit-equal from run to run.  Under torch.no_grad(), or for an h that needs no gradient, the
+    gradient is not computed."""
+    teacher = getattr(teacher, "states", teacher)
+    if not h.is_cuda:
+        raise L.MMVQAError("distill_loss: GPU tensors only (no CPU fallback)")
+    if h.dim() != 3 or h.dtype != torch.float32:
+        raise ValueError(f"distill_loss: h must be fp32 [B, T, hidden], got {h.dtype} {list(h.shape)}")
+    B, T, H = h.shape
+    if (teacher.dim() != 2 or teacher.dtype not in (torch.float32, torch.float16) or teacher.device != h.device
+            or not teacher.is_contiguous() or teacher.shape[0] < 1):
+        raise ValueError("distill_loss: `teacher` must be a contiguous fp32 / fp16 table [rows, hidden] on h's device")
+    if teacher.shape[1] != H:
+        raise ValueError(f"distill_loss: the teacher's states are {teacher.shape[1]} wide, h is {H} wide")
+    if start.dtype != torch.int64 or tuple(start.shape) != (B,) or start.device != h.device:
+        raise ValueError(f"distill_loss: `start` must be int64 [{B}] on h's device")
+    if count.dtype != torch.int32 or tuple(count.shape) != (B,) or count.device != h.device:
+        raise ValueError(f"distill_loss: `count` must be int32 [{B}] on h's device")
+    first = int(num_vis) + 2
+    if not 0 <= first < T:
+        raise ValueError(f"distill_loss: num_vis + 2 = {first} does not fit T = {T}")
+    want_grad = torch.is_grad_enabled() and h.requires_grad
+    return _Distill.apply(h, teacher, start.contiguous(), count.contiguous(), first, want_grad)
 
 
 class _Criterion:

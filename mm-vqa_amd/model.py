@@ -2,7 +2,11 @@
 
 Reference interface mirrored here:
   * ``Model(args)``                      -- models/mmbert.py:129-148
-  * ``model(img, ids, seg, mask)``       -- models/mmbert.py:150-167 (Tensor | (logits, feat) | (logits, 0, 0))
+  * ``model(img, ids, seg, mask)``       -- models/mmbert.py:150-167 (Tensor | (logits, feat) | (logits, 0, 0));
+                                            with dataset 'roco' and task 'distillation' (:159-161) the Tensor is the
+                                            encoder output h [B, T, hidden]: no fc1, no classifier, no SupCon head even
+                                            when ``supcon`` is set; their parameters stay in the state_dict and never
+                                            receive a gradient (engine head kind 2)
   * ``.to() .train() .eval() .parameters() .state_dict() .load_state_dict()``
   * ``model.classifier[2] = nn.Linear(hidden, num_classes)`` -- vqamed2019/train.py:137
 Parameter names and logical shapes equal the reference's state_dict; storage is ONE flat fp32
@@ -56,9 +60,13 @@ def desc_from_args(args, feat_dim=128, n_classes=None) -> L.ModelDesc:
     d.type_vocab = 2
     d.num_vis = int(args.num_vis)
     if args.dataset == "roco":
-        if getattr(args, "task", "MLM") != "MLM":
-            raise NotImplementedError("only task='MLM' is on the hot path")
-        d.head_kind = 0
+        task = getattr(args, "task", "MLM")
+        if task == "MLM":
+            d.head_kind = L.HEAD_MLM
+        elif task == "distillation":          # models/mmbert.py:159-161: the model returns the encoder output h
+            d.head_kind = L.HEAD_NONE
+        else:
+            raise NotImplementedError(f"task={task!r}: only 'MLM' and 'distillation' are on the hot path")
     elif args.dataset == "VQA-Med":
         d.head_kind = 1
     else:
@@ -335,8 +343,8 @@ class Model(nn.Module):
         ids, seg, mask = (t.contiguous().long() for t in (ids, seg, mask))
         B, T = ids.shape
         self._ensure_plan(B, T, img.shape[2], img.shape[3])
-        rows = B * T if d.head_kind == 0 else B
-        V = d.n_classes
+        rows = B if d.head_kind == L.HEAD_VQA else B * T
+        V = d.hidden if d.head_kind == L.HEAD_NONE else d.n_classes   # headless: the buffer receives h
         ld = (V + 3) & ~3
         # (pad columns V..ld-1 are never read: the loss kernels mask them and the engine's GEMMs contract over V)
         buf = torch.empty(rows, ld, dtype=torch.float32, device=img.device)
@@ -350,7 +358,7 @@ class Model(nn.Module):
                                              self._seed_ctr))
         self._fwd_state = (img, ids, seg, mask, rows, V, ld)
         logits = buf[:, :V]
-        logits = logits.view(B, T, V) if d.head_kind == 0 else logits
+        logits = logits.view(B, T, V) if d.head_kind != L.HEAD_VQA else logits
         return (logits, feat) if d.supcon else logits
 
     def _engine_backward(self, dlogits, dfeat=None, prec=0):

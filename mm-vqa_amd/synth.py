@@ -39,6 +39,33 @@ def vqa_batch(B, T=32, hw=224, vocab=30522, n_classes=1552, seed=1234, device="c
     return tuple(t.to(device) for t in (img, ids, seg, mask, tgt))
 
 
+def distill_batch(B, T=32, hw=224, vocab=28996, D=768, seed=1234, device="cpu", num_vis=5):
+    """A batch of the distillation task (pretrain/roco_utils.py:162-199, task 'distillation') and a small seeded teacher
+    table: ((img, ids, seg, mask, start, count), table).  table [total, D] fp32 holds the per-token states of the batch's
+    captions back to back; start int64 [B] / count int32 [B] name each caption's rows.  Caption lengths include 0 and one
+    above T - num_vis - 3 (the surplus token is cut from ids, as encode_text cuts it; count keeps it), the rest are drawn."""
+    g = torch.Generator().manual_seed(seed)
+    img = torch.rand(B, 3, hw, hw, generator=g) * 2 - 1
+    ids = torch.zeros(B, T, dtype=torch.long)
+    seg = torch.zeros(B, T, dtype=torch.long)
+    mask = torch.zeros(B, T, dtype=torch.long)
+    n_max, first = T - (num_vis + 3), num_vis + 2
+    lo = min(1000, max(1, vocab // 2))
+    lens = [(0, n_max + 1)[b] if b < 2 else int(torch.randint(0, n_max + 1, (1,), generator=g)) for b in range(B)]
+    start = torch.tensor([sum(lens[:b]) for b in range(B)], dtype=torch.int64)
+    count = torch.tensor(lens, dtype=torch.int32)
+    table = torch.randn(max(sum(lens), 1), D, generator=g) * 0.5
+    for b, n_all in enumerate(lens):
+        n = min(n_all, n_max)
+        ids[b, 0] = 101 % vocab
+        ids[b, first - 1] = 102 % vocab
+        ids[b, first:first + n] = torch.randint(lo, vocab, (n_all,), generator=g)[:n]
+        ids[b, first + n] = 102 % vocab
+        seg[b, first:first + n + 1] = 1
+        mask[b, :first + n + 1] = 1
+    return tuple(t.to(device) for t in (img, ids, seg, mask, start, count)), table.to(device)
+
+
 VQA_CATEGORIES = ("modality", "plane", "organ", "abnormality", "binary")   # the five question types of VQA-Med-2019
 
 

@@ -3,6 +3,8 @@ which never ship to the GPU box (SURVEY.md 8(b) "Callers the build must supply")
 
   mlm      pretrain/roco_train.py:155-197 + pretrain/roco_utils.py:207-372 (train_one_epoch / validate)
   supcon   pretrain/roco_supcon_train.py:137,168-202 + models/SupConLoss/supcon_utils.py:253-379
+  distill  the same two files with --task distillation: the headless model against the teacher's per-token states
+           (roco_utils.py:112-132, 230-238), which are read from --teacher_states instead of running the teacher
   vqa      vqamed2019/train.py:125-296 + vqamed2019/utils.py:625-767
   eval     vqamed2019/eval.py:99-180 + vqamed2019/utils.py:769-843 (test-set run: metrics, <model>_preds.csv, <model>_res.txt)
   gradcam  vqamed2019/grad_cam2.py:99-188 over the test split (one overlay PNG per row + gradcam_index.csv)
@@ -20,6 +22,9 @@ torch.distributed (RCCL).
 
     python -m mmvqa_amd.train mlm    --run_name r --mlm_prob 0.15 --epochs 2 --steps_per_epoch 20
     python -m mmvqa_amd.train supcon --run_name r --mlm_prob 0.15 --batch_size 32
+    python -m mmvqa_amd.train distill --run_name r --emb_vocab 28996 --epochs 2 --steps_per_epoch 20
+    python -m mmvqa_amd.train distill --data_dir roco-dataset/data --emb_vocab 28996 --bert_weights clinicalbert.pt \\
+                                      --teacher_states roco_train_teacher.npz --val_teacher_states roco_val_teacher.npz
     python -m mmvqa_amd.train vqa    --run_name r --loss ASLSingleLabel --batch_size 64
     python -m mmvqa_amd.train vqa    --run_name r --smoothing 0.1 --batch_size 64
     python -m mmvqa_amd.train eval   --model_dir save/MLM/r.pt --num_classes 1552 --batch_size 16
@@ -39,8 +44,8 @@ import torch
 import torch.distributed as dist
 from torch.optim import lr_scheduler
 
-from . import (CategorySmoothing, FusedAdam, LabelSmoothing, Model, asl_loss, checkpoint, embedding_mask, evaluate,
-               jaccard_mask, mlm_loss, split_feat, supcon_loss, synth)
+from . import (CategorySmoothing, FusedAdam, LabelSmoothing, Model, asl_loss, checkpoint, distill_loss, embedding_mask,
+               evaluate, jaccard_mask, mlm_loss, split_feat, supcon_loss, synth)
 from . import data as D
 from .amp import GradScaler
 from .ddp import GradReducer, comm_info, global_supcon_pairs, global_supcon_views, sync_replicas
@@ -393,6 +398,115 @@ def validate_mlm(args, ctx, model, epoch, amp=False):
     return ctx.mean(vl / max(steps, 1)), 100.0 * nc / max(nm, 1)
 
 
+# ----------------------------------------------------------------------------------------- distillation
+def distill_feeders(args, ctx):
+    """(train feeder, validation feeder, train teacher states, validation teacher states): the ROCO tree with the MLM
+    transforms (roco_train.py:98-118); the text of an item is the teacher's own tokens (data.TeacherStates.batch) and
+    the fifth tensor of a batch is int64 [B, 2] = (start, count).  Both tables of states are uploaded once."""
+    out = []
+    for split, path in (("train", args.teacher_states), ("validation", args.val_teacher_states)):
+        table = D.roco_table(args.data_dir, split)
+        teacher = D.TeacherStates.from_file(path, table)
+        teacher.check_vocab(args.emb_vocab)
+        if teacher.dim != args.hidden_size:
+            raise ValueError(f"{path}: the teacher's states are {teacher.dim} wide, --hidden_size is {args.hidden_size}")
+        ds = D.DistillDataset(table, teacher, args.num_vis, args.max_position_embeddings)
+        out.append((feeder(args, ctx, ds, split == "train", D.ROCO_AUG), teacher.to(ctx.dev)))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+def distill_targets(batch):
+    """(start int64 [B], count int32 [B]) of a batch: its last two tensors, or the columns of a fed batch's [B, 2]"""
+    if len(batch) == 6:
+        return batch[4], batch[5]
+    return batch[4][:, 0].contiguous(), batch[4][:, 1].to(torch.int32)
+
+
+def distill_step(model, opt, red, world, batch, teacher, scaler=None, num_vis=5):
+    """pretrain/roco_utils.py:214-247 with task 'distillation' (:230-231, 237-238): zero_grad -> forward (the model
+    returns h) -> nn.MSELoss against the teacher's states -> backward -> (gradient all-reduce) -> Adam.  batch =
+    (img, ids, seg, mask, start, count) or (img, ids, seg, mask, [B, 2] of both); teacher = the resident table of
+    states.  Returns the loss.  With a scaler (--mixed_precision, :224-245): autocast forward, the loss in fp32, scaled
+    backward, scaler.step after the all-reduce, scaler.update."""
+    img, ids, seg, mask = batch[:4]
+    start, count = distill_targets(batch)
+    opt.zero_grad()
+    if scaler is None:
+        loss = distill_loss(model(img, ids, seg, mask), teacher, start, count, num_vis)
+        loss.backward()
+        red.allreduce()
+        opt.step(grad_scale=1.0 / world, zero_grad=True)
+        return loss
+    with torch.autocast("cuda", dtype=torch.float16):
+        loss = distill_loss(model(img, ids, seg, mask), teacher, start, count, num_vis)
+    scaler.scale(loss).backward()
+    red.allreduce()
+    scaler.step(opt, grad_scale=1.0 / world, zero_grad=True)
+    scaler.update()
+    return loss
+
+
+def synthetic_distill(args, ctx, seeds):
+    for sd in seeds:
+        batch, table = synth.distill_batch(args.batch_size, args.max_position_embeddings, args.image_size, args.emb_vocab,
+                                           args.hidden_size, seed=sd, device=ctx.dev, num_vis=args.num_vis)
+        yield batch, table
+
+
+def run_distill(args):
+    ctx = Ctx(args)
+    args.dataset, args.task = "roco", "distillation"
+    model, opt, sched, red = build(args, ctx)
+    scaler = GradScaler() if args.mixed_precision else None
+    tr_fd = tr_teacher = None
+    args.val_feeder = args.val_teacher = None
+    if args.data_dir:
+        tr_fd, args.val_feeder, tr_teacher, args.val_teacher = distill_feeders(args, ctx)
+    start, kept = maybe_resume(args, model, opt, sched, "distill")
+    best = kept.get("best", float("inf"))
+    for epoch in range(start, args.epochs):
+        model.train()
+        tl, steps = 0.0, 0
+        if tr_fd is not None:
+            batches = ((b, tr_teacher) for b in epoch_batches(tr_fd, epoch, None))
+        else:
+            batches = synthetic_distill(args, ctx, (args.seed + 7919 * (epoch * 100003 + i) + ctx.rank
+                                                    for i in range(args.steps_per_epoch)))
+        for batch, teacher in batches:
+            loss = distill_step(model, opt, red, ctx.world, batch, teacher, scaler=scaler, num_vis=args.num_vis)
+            tl, steps = tl + float(loss.detach()), steps + 1      # per-step host sync, as roco_utils.py:267
+        vl = validate_distill(args, ctx, model, epoch, amp=args.mixed_precision)
+        sched.step(vl)
+        if (epoch + 1) % 5 == 0 and ctx.rank == 0:
+            save_recorder(args, epoch, model, opt, sched, "distill", {"best": min(best, vl)})
+        tl = ctx.mean(tl / max(steps, 1))
+        if ctx.rank == 0:                                         # roco_train.py:190
+            print(f"Epoch {epoch + 1}/{args.epochs} Learning rate: {opt.param_groups[0]['lr']:.7f}, Train loss: {tl:.4f}, "
+                  f"Val loss: {vl:.4f}", flush=True)
+            if vl < best:
+                save_model(args, model)
+        best = min(best, vl)
+    return best
+
+
+@torch.no_grad()
+def validate_distill(args, ctx, model, epoch, amp=False):
+    """roco_utils.py:292-372 with task 'distillation': the mean of the per-batch losses; no accuracy (total_acc is None)"""
+    model.eval()
+    vl, steps = 0.0, 0
+    fd = getattr(args, "val_feeder", None)
+    if fd is not None:
+        batches = ((b, args.val_teacher) for b in epoch_batches(fd, epoch, None))
+    else:
+        batches = synthetic_distill(args, ctx, (10 ** 6 + i + ctx.rank for i in range(args.val_steps)))
+    for batch, teacher in batches:
+        with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
+            h = model(*batch[:4])
+        s, c = distill_targets(batch)
+        vl, steps = vl + float(distill_loss(h, teacher, s, c, args.num_vis)), steps + 1
+    return ctx.mean(vl / max(steps, 1))
+
+
 # ----------------------------------------------------------------------------------------- MLM + SupCon
 def run_supcon(args):
     ctx = Ctx(args)
@@ -641,13 +755,21 @@ def run_gradcam(args):
 def parse_args(argv=None):
     """-> (mode, args); contradictory options end in argparse's error exit before anything touches the GPU"""
     argv = list(sys.argv[1:] if argv is None else argv)
-    mode = argv.pop(0) if argv and argv[0] in ("mlm", "supcon", "vqa", "eval", "gradcam") else "mlm"
+    mode = argv.pop(0) if argv and argv[0] in ("mlm", "supcon", "distill", "vqa", "eval", "gradcam") else "mlm"
     p = argparse.ArgumentParser(description=f"mmvqa_amd training ({mode})")
     common_args(p)
-    if mode in ("mlm", "supcon"):
-        p.add_argument("--mlm_prob", type=float, default=0.15)
+    if mode in ("mlm", "supcon", "distill"):
+        if mode != "distill":
+            p.add_argument("--mlm_prob", type=float, default=0.15)
         p.add_argument("--lr", type=float, default=2e-5)
         p.add_argument("--max_position_embeddings", type=int, default=75)
+        if mode == "distill":
+            p.add_argument("--teacher_states", type=str, default=None, metavar="FILE",
+                           help="with --data_dir: an .npz of the teacher's precomputed per-token states of the train "
+                                "captions -- names [R], offsets [R + 1], ids [total] (the teacher tokenizer's ids without "
+                                "CLS / SEP), states [total, hidden_size]; no teacher is run here")
+            p.add_argument("--val_teacher_states", type=str, default=None, metavar="FILE",
+                           help="the same for the validation split")
         if mode == "supcon":
             p.add_argument("--con_task", type=str, default="supcon", choices=["simclr", "supcon"])
             p.add_argument("--similarity", type=str, default="sentence_transformers")      # accepted, not read
@@ -694,6 +816,13 @@ def parse_args(argv=None):
             p.error(f"--con_task simclr contradicts --supcon_mask {args.supcon_mask}: SimCLR has no positive mask")
         if not args.data_dir:
             p.error(f"--supcon_mask {args.supcon_mask} needs --data_dir: synthetic batches have no captions to compare")
+    if mode == "distill":
+        given = [o for o in ("teacher_states", "val_teacher_states") if getattr(args, o)]
+        if args.data_dir and len(given) != 2:
+            p.error("distill with --data_dir needs --teacher_states FILE and --val_teacher_states FILE (the teacher's "
+                    "precomputed states of both splits)")
+        if not args.data_dir and given:
+            p.error(f"--{given[0]} is read with --data_dir only: synthetic batches bring their own teacher table")
     if mode == "supcon":
         if args.supcon_mask == "embeddings" and not args.caption_embeddings:
             p.error("--supcon_mask embeddings needs --caption_embeddings FILE (the precomputed sentence embeddings)")
@@ -706,7 +835,7 @@ def main(argv=None):
     mode, args = parse_args(argv)
     if args.mixed_precision and mode == "supcon":
         print("--mixed_precision: the SupCon loop runs in fp32, as the reference's (supcon_utils.py:263-323 has no autocast)")
-    out = {"mlm": run_mlm, "supcon": run_supcon, "vqa": run_vqa, "eval": run_eval, "gradcam": run_gradcam}[mode](args)
+    out = {"mlm": run_mlm, "supcon": run_supcon, "distill": run_distill, "vqa": run_vqa, "eval": run_eval, "gradcam": run_gradcam}[mode](args)
     if dist.is_initialized():
         dist.destroy_process_group()
     return out
