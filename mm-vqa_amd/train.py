@@ -37,6 +37,7 @@ torch.distributed (RCCL).
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import sys
 
@@ -153,6 +154,21 @@ def epoch_batches(fd, epoch, synthetic):
     yield from fd
 
 
+def train_seeds(args, ctx, epoch):
+    """seeds of one epoch's synthetic train batches: another one for every epoch, step and rank"""
+    return (args.seed + 7919 * (epoch * 100003 + i) + ctx.rank for i in range(args.steps_per_epoch))
+
+
+def val_seeds(args, rank=0):
+    """seeds of the synthetic validation batches, the same every epoch (run_vqa: and on every rank)"""
+    return (10 ** 6 + i + rank for i in range(args.val_steps))
+
+
+def synthetic_roco(args, ctx, seed, batch_size=None):
+    return synth.roco_batch(batch_size or args.batch_size, args.max_position_embeddings, args.image_size,
+                            min(args.vocab_size, args.emb_vocab), seed=seed, device=ctx.dev, mlm_prob=args.mlm_prob)
+
+
 class Ctx:
     def __init__(self, args):
         self.world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -258,6 +274,25 @@ def maybe_resume(args, model, opt, sched, mode):
 
 
 # ----------------------------------------------------------------------------------------- one training step each
+def _update(loss, model, opt, red, world, scaler=None, scaled_backward=True, clip=False):
+    """What every step does once it has its loss: backward -> gradient all-reduce -> Adam on the gradients over `world`
+    (times the clip factor of clip_grad_norm_(1.0): global 2-norm over the averaged flat gradient buffer).  With a
+    scaler: backward of scaler.scale(loss), scaler.step after the all-reduce, scaler.update.  scaled_backward=False is
+    vqa_step's: scale(loss) is still called (it creates the scale tensor update() asserts), the backward is unscaled."""
+    scaled = loss if scaler is None else scaler.scale(loss)
+    (scaled if scaled_backward else loss).backward()
+    red.allreduce()
+    scale = 1.0 / world
+    if clip:
+        gn = float(model.flat_grads.norm()) * scale
+        scale *= min(1.0, 1.0 / (gn + 1e-6))
+    if scaler is None:
+        opt.step(grad_scale=scale, zero_grad=True)
+    else:
+        scaler.step(opt, grad_scale=scale, zero_grad=True)
+        scaler.update()
+
+
 def mlm_step(model, opt, red, world, batch, scaler=None):
     """pretrain/roco_utils.py:214-247,257-265: zero_grad -> forward -> log_softmax + NLLLoss -> backward ->
     (gradient all-reduce) -> Adam.  Returns (loss, pred[B,T], stats = {loss, #target>0, #correct}).
@@ -265,18 +300,9 @@ def mlm_step(model, opt, red, world, batch, scaler=None):
     after the all-reduce (every rank checks the same gradients), scaler.update."""
     img, ids, seg, mask, tgt = batch
     opt.zero_grad()
-    if scaler is None:
+    with torch.autocast("cuda", dtype=torch.float16) if scaler is not None else contextlib.nullcontext():
         loss, pred, stats = mlm_loss(model(img, ids, seg, mask), tgt)
-        loss.backward()
-        red.allreduce()
-        opt.step(grad_scale=1.0 / world, zero_grad=True)
-        return loss, pred, stats
-    with torch.autocast("cuda", dtype=torch.float16):
-        loss, pred, stats = mlm_loss(model(img, ids, seg, mask), tgt)
-    scaler.scale(loss).backward()
-    red.allreduce()
-    scaler.step(opt, grad_scale=1.0 / world, zero_grad=True)
-    scaler.update()
+    _update(loss, model, opt, red, world, scaler)
     return loss, pred, stats
 
 
@@ -311,9 +337,7 @@ def supcon_step(model, opt, red, world, batch, words=None):
         build_mask = embedding_mask if isinstance(words, D.CaptionEmbeddings) else jaccard_mask
         pos = build_mask(words, rows, torch.zeros_like(cols), rows, cols)
         loss = loss_mlm + supcon_loss(feat, mask=pos)
-    loss.backward()
-    red.allreduce()
-    opt.step(grad_scale=1.0 / world, zero_grad=True)
+    _update(loss, model, opt, red, world)
     return loss, pred, stats
 
 
@@ -330,72 +354,76 @@ def vqa_step(model, opt, red, world, batch, crit, clip=False, scaler=None):
     with torch.autocast("cuda", dtype=torch.float16, enabled=scaler is not None):
         logits, _, _ = model(img, ids, seg, mask)       # utils.py:646
         loss = crit(logits, tgt, batch[5]) if len(batch) == 6 else crit(logits, tgt)
-    if scaler is not None:
-        scaler.scale(loss)                          # utils.py:651: the scaled loss is not used
-    loss.backward()
-    red.allreduce()
-    scale = 1.0 / world
-    if clip:                                        # global 2-norm over the (averaged) flat gradient buffer
-        gn = float(model.flat_grads.norm()) * scale
-        scale *= min(1.0, 1.0 / (gn + 1e-6))
-    if scaler is None:
-        opt.step(grad_scale=scale, zero_grad=True)
-    else:
-        scaler.step(opt, grad_scale=scale, zero_grad=True)
-        scaler.update()
+    _update(loss, model, opt, red, world, scaler, scaled_backward=False, clip=clip)   # utils.py:651: the scaled loss is not used
     return loss, logits.detach().softmax(1).argmax(1)
 
 
-# ----------------------------------------------------------------------------------------- MLM
-def run_mlm(args):
-    ctx = Ctx(args)
-    args.dataset, args.task = "roco", "MLM"
-    model, opt, sched, red = build(args, ctx)
-    scaler = GradScaler() if args.mixed_precision else None
-    T, B, V = args.max_position_embeddings, args.batch_size, args.vocab_size
-    tr_fd, args.val_feeder = roco_feeders(args, ctx) if args.data_dir else (None, None)
-    start, kept = maybe_resume(args, model, opt, sched, "mlm")
+# ----------------------------------------------------------------------------------------- the pre-training loops
+@torch.no_grad()
+def validate(ctx, model, batches, value, amp=False):
+    """The validation loop of every mode: eval mode, no gradients, value(batch) -> host numbers (loss, #targets, #correct)
+    of one batch, computed under fp16 autocast when amp.  -> (mean of the per-batch losses, averaged over the ranks;
+    accuracy in percent over this rank's batches)"""
+    model.eval()
+    vl, nm, nc, steps = 0.0, 0, 0, 0
+    for batch in batches:
+        with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
+            s = value(batch)
+        vl, nm, nc, steps = vl + s[0], nm + s[1], nc + s[2], steps + 1
+    return ctx.mean(vl / max(steps, 1)), 100.0 * nc / max(nm, 1)
+
+
+def pretrain(args, ctx, mode, model, opt, sched, batches, step, val, line, rank_mean=True):
+    """The epoch loop of mlm, distill and supcon (roco_train.py:155-197, roco_supcon_train.py:168-202).  A mode supplies
+    batches(epoch) -> the epoch's train batches, step(batch) -> host numbers (loss, #targets, #correct) of one training
+    step, val(epoch) -> (validation loss, accuracy) and the tail of its epoch line, a format string over tl, ta, vl, va.
+    rank_mean=False is synthetic SupCon's line: this rank's loss sum over --steps_per_epoch.  -> best validation loss"""
+    start, kept = maybe_resume(args, model, opt, sched, mode)
     best = kept.get("best", float("inf"))
     for epoch in range(start, args.epochs):
         model.train()
-        tl, nm, nc, steps = 0.0, 0.0, 0.0, 0
-        synthetic = (synth.roco_batch(B, T, args.image_size, min(V, args.emb_vocab),
-                                      seed=args.seed + 7919 * (epoch * 100003 + i) + ctx.rank,
-                                      device=ctx.dev, mlm_prob=args.mlm_prob) for i in range(args.steps_per_epoch))
-        for img, ids, seg, mask, tgt in epoch_batches(tr_fd, epoch, synthetic):
-            _, _, stats = mlm_step(model, opt, red, ctx.world, (img, ids, seg, mask, tgt), scaler=scaler)
-            s = stats.tolist()               # per-step host sync, as roco_utils.py:267
+        tl, nm, nc, steps = 0.0, 0, 0, 0
+        for batch in batches(epoch):
+            s = step(batch)
             tl, nm, nc, steps = tl + s[0], nm + s[1], nc + s[2], steps + 1
-        vl, va = validate_mlm(args, ctx, model, epoch, amp=args.mixed_precision)
+        vl, va = val(epoch)
         sched.step(vl)
         if (epoch + 1) % 5 == 0 and ctx.rank == 0:
-            save_recorder(args, epoch, model, opt, sched, "mlm", {"best": min(best, vl)})
-        tl = ctx.mean(tl / max(steps, 1))
+            save_recorder(args, epoch, model, opt, sched, mode, {"best": min(best, vl)})
+        tl = ctx.mean(tl / max(steps, 1)) if rank_mean else tl / args.steps_per_epoch
         if ctx.rank == 0:
-            print(f"Epoch {epoch + 1}/{args.epochs} Learning rate: {opt.param_groups[0]['lr']:.7f}, Train loss: {tl:.4f}, "
-                  f"Train acc: {100.0 * nc / max(nm, 1):.4f} ,Val loss: {vl:.4f}, Val acc: {va:.4f}", flush=True)
+            print(f"Epoch {epoch + 1}/{args.epochs} Learning rate: {opt.param_groups[0]['lr']:.7f}, "
+                  + line.format(tl=tl, ta=100.0 * nc / max(nm, 1), vl=vl, va=va), flush=True)
             if vl < best:
                 save_model(args, model)
         best = min(best, vl)
     return best
 
 
-@torch.no_grad()
-def validate_mlm(args, ctx, model, epoch, amp=False):
-    """amp: the forwards under fp16 autocast (mlm --mixed_precision, roco_utils.py:310-311); SupCon validates in fp32"""
-    model.eval()
-    vl, nm, nc, steps = 0.0, 0.0, 0.0, 0
-    synthetic = (synth.roco_batch(args.batch_size, args.max_position_embeddings, args.image_size,
-                                  min(args.vocab_size, args.emb_vocab), seed=10 ** 6 + i + ctx.rank,
-                                  device=ctx.dev, mlm_prob=args.mlm_prob) for i in range(args.val_steps))
-    for img, ids, seg, mask, tgt in epoch_batches(getattr(args, "val_feeder", None), epoch, synthetic):
-        with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
-            out = model(img, ids, seg, mask)
-        logits = out[0] if isinstance(out, tuple) else out
-        _, _, stats = mlm_loss(logits, tgt)
-        s = stats.tolist()
-        vl, nm, nc, steps = vl + s[0], nm + s[1], nc + s[2], steps + 1
-    return ctx.mean(vl / max(steps, 1)), 100.0 * nc / max(nm, 1)
+MLM_LINE = "Train loss: {tl:.4f}, Train acc: {ta:.4f} ,Val loss: {vl:.4f}, Val acc: {va:.4f}"   # roco_train.py:190
+
+
+def validate_mlm(args, ctx, model, fd, epoch, amp=False):
+    """-> (loss, accuracy) over the validation feeder, or over synthetic batches without one.  amp: under fp16 autocast
+    (mlm --mixed_precision, roco_utils.py:310-311); SupCon validates in fp32"""
+    def value(batch):
+        out = model(*batch[:4])
+        return mlm_loss(out[0] if isinstance(out, tuple) else out, batch[4])[2].tolist()
+    synthetic = (synthetic_roco(args, ctx, sd) for sd in val_seeds(args, ctx.rank))
+    return validate(ctx, model, epoch_batches(fd, epoch, synthetic), value, amp)
+
+
+def run_mlm(args):
+    ctx = Ctx(args)
+    args.dataset, args.task = "roco", "MLM"
+    model, opt, sched, red = build(args, ctx)
+    scaler = GradScaler() if args.mixed_precision else None
+    tr_fd, va_fd = roco_feeders(args, ctx) if args.data_dir else (None, None)
+    return pretrain(
+        args, ctx, "mlm", model, opt, sched, line=MLM_LINE,
+        batches=lambda epoch: epoch_batches(tr_fd, epoch, (synthetic_roco(args, ctx, sd) for sd in train_seeds(args, ctx, epoch))),
+        step=lambda batch: mlm_step(model, opt, red, ctx.world, batch, scaler=scaler)[2].tolist(),   # per-step host sync, as roco_utils.py:267
+        val=lambda epoch: validate_mlm(args, ctx, model, va_fd, epoch, amp=args.mixed_precision))
 
 
 # ----------------------------------------------------------------------------------------- distillation
@@ -431,26 +459,19 @@ def distill_step(model, opt, red, world, batch, teacher, scaler=None, num_vis=5)
     img, ids, seg, mask = batch[:4]
     start, count = distill_targets(batch)
     opt.zero_grad()
-    if scaler is None:
+    with torch.autocast("cuda", dtype=torch.float16) if scaler is not None else contextlib.nullcontext():
         loss = distill_loss(model(img, ids, seg, mask), teacher, start, count, num_vis)
-        loss.backward()
-        red.allreduce()
-        opt.step(grad_scale=1.0 / world, zero_grad=True)
-        return loss
-    with torch.autocast("cuda", dtype=torch.float16):
-        loss = distill_loss(model(img, ids, seg, mask), teacher, start, count, num_vis)
-    scaler.scale(loss).backward()
-    red.allreduce()
-    scaler.step(opt, grad_scale=1.0 / world, zero_grad=True)
-    scaler.update()
+    _update(loss, model, opt, red, world, scaler)
     return loss
 
 
-def synthetic_distill(args, ctx, seeds):
-    for sd in seeds:
-        batch, table = synth.distill_batch(args.batch_size, args.max_position_embeddings, args.image_size, args.emb_vocab,
-                                           args.hidden_size, seed=sd, device=ctx.dev, num_vis=args.num_vis)
-        yield batch, table
+def distill_batches(args, ctx, fd, teacher, epoch, seeds):
+    """(batch, teacher table) of one epoch: the feeder's batches beside the resident table, or one synthetic batch per
+    seed, each with a table of its own"""
+    if fd is not None:
+        return ((b, teacher) for b in epoch_batches(fd, epoch, None))
+    return (synth.distill_batch(args.batch_size, args.max_position_embeddings, args.image_size, args.emb_vocab,
+                                args.hidden_size, seed=sd, device=ctx.dev, num_vis=args.num_vis) for sd in seeds)
 
 
 def run_distill(args):
@@ -458,53 +479,19 @@ def run_distill(args):
     args.dataset, args.task = "roco", "distillation"
     model, opt, sched, red = build(args, ctx)
     scaler = GradScaler() if args.mixed_precision else None
-    tr_fd = tr_teacher = None
-    args.val_feeder = args.val_teacher = None
-    if args.data_dir:
-        tr_fd, args.val_feeder, tr_teacher, args.val_teacher = distill_feeders(args, ctx)
-    start, kept = maybe_resume(args, model, opt, sched, "distill")
-    best = kept.get("best", float("inf"))
-    for epoch in range(start, args.epochs):
-        model.train()
-        tl, steps = 0.0, 0
-        if tr_fd is not None:
-            batches = ((b, tr_teacher) for b in epoch_batches(tr_fd, epoch, None))
-        else:
-            batches = synthetic_distill(args, ctx, (args.seed + 7919 * (epoch * 100003 + i) + ctx.rank
-                                                    for i in range(args.steps_per_epoch)))
-        for batch, teacher in batches:
-            loss = distill_step(model, opt, red, ctx.world, batch, teacher, scaler=scaler, num_vis=args.num_vis)
-            tl, steps = tl + float(loss.detach()), steps + 1      # per-step host sync, as roco_utils.py:267
-        vl = validate_distill(args, ctx, model, epoch, amp=args.mixed_precision)
-        sched.step(vl)
-        if (epoch + 1) % 5 == 0 and ctx.rank == 0:
-            save_recorder(args, epoch, model, opt, sched, "distill", {"best": min(best, vl)})
-        tl = ctx.mean(tl / max(steps, 1))
-        if ctx.rank == 0:                                         # roco_train.py:190
-            print(f"Epoch {epoch + 1}/{args.epochs} Learning rate: {opt.param_groups[0]['lr']:.7f}, Train loss: {tl:.4f}, "
-                  f"Val loss: {vl:.4f}", flush=True)
-            if vl < best:
-                save_model(args, model)
-        best = min(best, vl)
-    return best
+    tr_fd, va_fd, tr_teacher, va_teacher = distill_feeders(args, ctx) if args.data_dir else (None,) * 4
 
+    def step(pair):                                               # per-step host sync, as roco_utils.py:267
+        return float(distill_step(model, opt, red, ctx.world, *pair, scaler=scaler, num_vis=args.num_vis).detach()), 0, 0
 
-@torch.no_grad()
-def validate_distill(args, ctx, model, epoch, amp=False):
-    """roco_utils.py:292-372 with task 'distillation': the mean of the per-batch losses; no accuracy (total_acc is None)"""
-    model.eval()
-    vl, steps = 0.0, 0
-    fd = getattr(args, "val_feeder", None)
-    if fd is not None:
-        batches = ((b, args.val_teacher) for b in epoch_batches(fd, epoch, None))
-    else:
-        batches = synthetic_distill(args, ctx, (10 ** 6 + i + ctx.rank for i in range(args.val_steps)))
-    for batch, teacher in batches:
-        with torch.autocast("cuda", dtype=torch.float16, enabled=amp):
-            h = model(*batch[:4])
-        s, c = distill_targets(batch)
-        vl, steps = vl + float(distill_loss(h, teacher, s, c, args.num_vis)), steps + 1
-    return ctx.mean(vl / max(steps, 1))
+    def val_value(pair):    # roco_utils.py:292-372 with task 'distillation': no accuracy (total_acc is None)
+        return float(distill_loss(model(*pair[0][:4]), pair[1], *distill_targets(pair[0]), args.num_vis)), 0, 0
+
+    return pretrain(
+        args, ctx, "distill", model, opt, sched, step=step, line="Train loss: {tl:.4f}, Val loss: {vl:.4f}",   # roco_train.py:190
+        batches=lambda epoch: distill_batches(args, ctx, tr_fd, tr_teacher, epoch, train_seeds(args, ctx, epoch)),
+        val=lambda epoch: validate(ctx, model, distill_batches(args, ctx, va_fd, va_teacher, epoch, val_seeds(args, ctx.rank)),
+                                   val_value, amp=args.mixed_precision))
 
 
 # ----------------------------------------------------------------------------------------- MLM + SupCon
@@ -512,53 +499,35 @@ def run_supcon(args):
     ctx = Ctx(args)
     args.dataset, args.task, args.supcon = "roco", "MLM", True
     model, opt, sched, red = build(args, ctx)
-    T, V = args.max_position_embeddings, args.vocab_size
     n = args.batch_size // 2                      # roco_supcon_train.py:137: the loader yields bs//2 pairs
     if n < 1:
         raise ValueError("--batch_size must be >= 2 (two views per sample)")
-    tr_fd = words = None
-    if args.data_dir:                             # fed batches come in process_tensors' layout (data.collate_supcon)
-        tr_fd, args.val_feeder, words = roco_supcon_feeders(args, ctx, n)
-    start, kept = maybe_resume(args, model, opt, sched, "supcon")
-    best = kept.get("best", float("inf"))
+    # (fed batches come in process_tensors' layout: data.collate_supcon)
+    tr_fd, va_fd, words = roco_supcon_feeders(args, ctx, n) if args.data_dir else (None, None, None)
 
     def synthetic(epoch):
-        for i in range(args.steps_per_epoch):
-            sd = args.seed + 7919 * (epoch * 100003 + i) + ctx.rank
-            a = synth.roco_batch(n, T, args.image_size, min(V, args.emb_vocab), seed=sd, device=ctx.dev, mlm_prob=args.mlm_prob)
-            b = synth.roco_batch(n, T, args.image_size, min(V, args.emb_vocab), seed=sd + 1, device=ctx.dev, mlm_prob=args.mlm_prob)
+        for sd in train_seeds(args, ctx, epoch):
+            a, b = synthetic_roco(args, ctx, sd, n), synthetic_roco(args, ctx, sd + 1, n)
             yield process_tensors((a[0], b[0]), a[1], b[1], a[2], a[3], a[4], b[4])
 
-    for epoch in range(start, args.epochs):
-        model.train()
-        tl, nm, nc, steps = 0.0, 0.0, 0.0, 0
-        for batch in epoch_batches(tr_fd, epoch, synthetic(epoch)):
-            loss, _, stats = supcon_step(model, opt, red, ctx.world, batch, words=words)
-            tl, steps = tl + float(loss.detach()), steps + 1
-            if tr_fd is not None:                 # the MLM accuracy train_one_epoch returns (supcon_utils.py:296-318)
-                s = stats.tolist()
-                nm, nc = nm + s[1], nc + s[2]
-        vl, va = validate_mlm(args, ctx, model, epoch)
-        sched.step(vl)
-        if (epoch + 1) % 5 == 0 and ctx.rank == 0:       # roco_supcon_train.py:177-184
-            save_recorder(args, epoch, model, opt, sched, "supcon", {"best": min(best, vl)})
-        if tr_fd is not None:
-            tl = ctx.mean(tl / max(steps, 1))
-        if ctx.rank == 0:
-            if tr_fd is not None:                         # roco_supcon_train.py:193
-                print(f"Epoch {epoch + 1}/{args.epochs} Learning rate: {opt.param_groups[0]['lr']:.7f}, "
-                      f"Train loss: {tl:.4f}, Train acc: {100.0 * nc / max(nm, 1):.4f} ,Val loss: {vl:.4f}, "
-                      f"Val acc: {va:.4f}", flush=True)
-            else:
-                print(f"Epoch {epoch + 1}/{args.epochs} Learning rate: {opt.param_groups[0]['lr']:.7f}, "
-                      f"Train loss: {tl / args.steps_per_epoch:.4f}, Val loss: {vl:.4f}, Val acc: {va:.4f}", flush=True)
-            if vl < best:                                 # roco_supcon_train.py:199-202
-                save_model(args, model)
-        best = min(best, vl)
-    return best
+    def step(batch):
+        loss, _, stats = supcon_step(model, opt, red, ctx.world, batch, words=words)
+        # fed: the MLM accuracy train_one_epoch returns (supcon_utils.py:296-318); synthetic: `stats` stays on the device
+        return (float(loss.detach()), *(stats.tolist()[1:] if tr_fd is not None else (0, 0)))
+
+    return pretrain(
+        args, ctx, "supcon", model, opt, sched, rank_mean=tr_fd is not None,
+        batches=lambda epoch: epoch_batches(tr_fd, epoch, synthetic(epoch)), step=step,
+        val=lambda epoch: validate_mlm(args, ctx, model, va_fd, epoch),
+        line=MLM_LINE if tr_fd is not None else "Train loss: {tl:.4f}, Val loss: {vl:.4f}, Val acc: {va:.4f}")   # roco_supcon_train.py:193
 
 
 # ----------------------------------------------------------------------------------------- VQA-Med-2019
+def plain_criterion(args):
+    """--loss: ASLSingleLabel or cross entropy (vqamed2019/train.py:170-174, eval.py:126-130)"""
+    return (lambda lg, t: asl_loss(lg, t)) if args.loss == "ASLSingleLabel" else (lambda lg, t: mlm_loss(lg, t)[0])
+
+
 def vqa_criterion(args, ctx, train_rows=None):
     """vqamed2019/train.py:164-174: --smoothing is tested first (then --loss is not consulted): LabelSmoothByCategory
     over the WHOLE train table (every rank builds the same table, whatever its shard), with the flag's value (the
@@ -567,7 +536,7 @@ def vqa_criterion(args, ctx, train_rows=None):
     if getattr(args, "smoothing", None):
         rows = synth.vqa_category_rows(args.num_classes) if train_rows is None else train_rows
         return CategorySmoothing(rows, args.num_classes, args.smoothing).to(ctx.dev)
-    return (lambda lg, t: asl_loss(lg, t)) if args.loss == "ASLSingleLabel" else (lambda lg, t: mlm_loss(lg, t)[0])
+    return plain_criterion(args)
 
 
 def run_vqa(args):
@@ -591,10 +560,13 @@ def run_vqa(args):
     T, B = args.max_position_embeddings, args.batch_size
 
     def synthetic_train(epoch):
-        for i in range(args.steps_per_epoch):
-            sd = args.seed + 7919 * (epoch * 100003 + i) + ctx.rank
+        for sd in train_seeds(args, ctx, epoch):
             batch = synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=sd, device=ctx.dev)
             yield batch + (synth.vqa_categories(B, C, seed=sd, device=ctx.dev),) if smooth else batch
+
+    def val_value(batch):                               # utils.py:708-715, 673
+        logits, _, _ = model(*batch[:4])
+        return float(crit(logits, batch[4])), batch[4].shape[0], int((logits.softmax(1).argmax(1) == batch[4]).sum())
     # (vqamed2019/train.py itself has no recorder / --resume; kept here like the two pre-training loops)
     start, kept = maybe_resume(args, model, opt, sched, "vqa")
     best_loss, best_acc1 = kept.get("best_loss", float("inf")), kept.get("best_acc1", 0.0)
@@ -607,21 +579,10 @@ def run_vqa(args):
         for batch in epoch_batches(tr_fd, epoch, synthetic_train(epoch)):
             loss, _ = vqa_step(model, opt, red, ctx.world, batch, crit, clip=args.clip, scaler=scaler)
             tl, steps = tl + float(loss.detach()), steps + 1
-        model.eval()
         if smooth:
             crit.eval()         # utils.py:693: validation is plain cross entropy
-        vl, correct, total, vsteps = 0.0, 0, 0, 0
-        with torch.no_grad():
-            synthetic = (synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=10 ** 6 + i, device=ctx.dev)
-                         for i in range(args.val_steps))
-            for img, ids, seg, mask, tgt in epoch_batches(va_fd, epoch, synthetic):
-                with torch.autocast("cuda", dtype=torch.float16, enabled=args.mixed_precision):   # utils.py:708-715
-                    logits, _, _ = model(img, ids, seg, mask)
-                    vl += float(crit(logits, tgt))
-                correct += int((logits.softmax(1).argmax(1) == tgt).sum())   # utils.py:673
-                total += tgt.shape[0]
-                vsteps += 1
-        vl, acc = ctx.mean(vl / max(vsteps, 1)), 100.0 * correct / max(total, 1)
+        synthetic = (synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=sd, device=ctx.dev) for sd in val_seeds(args))
+        vl, acc = validate(ctx, model, epoch_batches(va_fd, epoch, synthetic), val_value, amp=args.mixed_precision)
         sched.step(vl)
         if ctx.rank == 0:
             print(f"Epoch {epoch + 1}/{args.epochs} lr {opt.param_groups[0]['lr']:.7f} train_loss {tl / max(steps, 1):.4f} "
@@ -659,7 +620,7 @@ def run_eval(args):
     if getattr(args, "smoothing", None):     # eval.py:124-125; test() puts it in eval mode (utils.py:772): cross entropy
         crit = LabelSmoothing(args.smoothing)
     else:
-        crit = (lambda lg, t: asl_loss(lg, t)) if args.loss == "ASLSingleLabel" else (lambda lg, t: mlm_loss(lg, t)[0])
+        crit = plain_criterion(args)
     cats = [r[3] for r in rows]
     with torch.autocast("cuda", dtype=torch.float16, enabled=args.mixed_precision):   # utils.py:786-792
         test_loss, predictions, acc, bleu = evaluate.test(batches, model, crit, cats, idx2ans, category=args.category)
@@ -811,11 +772,15 @@ def parse_args(argv=None):
                 "inf / nan before the first parameter update")
     if getattr(args, "smoothing", None) is not None and not 0.0 <= args.smoothing <= 1.0:
         p.error(f"--smoothing {args.smoothing} is outside [0, 1]")
-    if mode == "supcon" and args.supcon_mask != "none":
-        if args.con_task == "simclr":
+    if mode == "supcon":
+        if args.supcon_mask != "none" and args.con_task == "simclr":
             p.error(f"--con_task simclr contradicts --supcon_mask {args.supcon_mask}: SimCLR has no positive mask")
-        if not args.data_dir:
+        if args.supcon_mask != "none" and not args.data_dir:
             p.error(f"--supcon_mask {args.supcon_mask} needs --data_dir: synthetic batches have no captions to compare")
+        if args.supcon_mask == "embeddings" and not args.caption_embeddings:
+            p.error("--supcon_mask embeddings needs --caption_embeddings FILE (the precomputed sentence embeddings)")
+        if args.supcon_mask != "embeddings" and args.caption_embeddings:
+            p.error(f"--caption_embeddings is read by --supcon_mask embeddings only, not by --supcon_mask {args.supcon_mask}")
     if mode == "distill":
         given = [o for o in ("teacher_states", "val_teacher_states") if getattr(args, o)]
         if args.data_dir and len(given) != 2:
@@ -823,11 +788,6 @@ def parse_args(argv=None):
                     "precomputed states of both splits)")
         if not args.data_dir and given:
             p.error(f"--{given[0]} is read with --data_dir only: synthetic batches bring their own teacher table")
-    if mode == "supcon":
-        if args.supcon_mask == "embeddings" and not args.caption_embeddings:
-            p.error("--supcon_mask embeddings needs --caption_embeddings FILE (the precomputed sentence embeddings)")
-        if args.supcon_mask != "embeddings" and args.caption_embeddings:
-            p.error(f"--caption_embeddings is read by --supcon_mask embeddings only, not by --supcon_mask {args.supcon_mask}")
     return mode, args
 
 
