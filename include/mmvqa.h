@@ -181,6 +181,48 @@ typedef struct mmvqa_attn_desc {
   float* dprev_out;
 } mmvqa_attn_desc;
 
+/* Attention of one Feedback-Transformer window (models/feedback_transformer_pytorch.py:160-193): n in {1, 2} queries per
+ * sample and head (8 heads of width 64) against n_mem memory entries followed, when n == 2, by the window's own two keys.
+ * Rows are window-major: row b*n + i of q / out / dout / dq, row b*2 + i of the self keys and values; memory entry j of
+ * sample b lies at mem + (j/2)*mem_win + (b*2 + j%2)*mem_ld, head h at + h*64.  score = q.k * scale + bias[max(i - j, 0)][h]
+ * (row 1 of the 32 x 8 table for (query 1, key 0), row 0 elsewhere; key 0 is the oldest memory entry); query 0 does not see
+ * the window's second key (probability exactly 0).  probs[((b*8 + h)*n + i)*p_ld + j] keeps the probabilities before
+ * dropout; the dropout index of (b, h, i, j) is ((b*8 + h)*T + n_mem + i)*T + j.
+ * Backward: dq and the self dk / dv are written; rows < n_mem of dmem_k / dmem_v (addressed like mem_k) and rows 0, 1 of
+ * dbias are ADDED to (dbias may be NULL: no bias-table gradient). */
+typedef struct mmvqa_fb_attn_desc {
+  const float* q;
+  int q_ld;
+  const float* mem_k;
+  const float* mem_v;
+  long long mem_win;
+  int mem_ld;
+  const float* self_k;
+  const float* self_v;
+  int self_ld;
+  const float* bias;
+  float* probs;
+  int p_ld;
+  float* out;
+  int out_ld;
+  int B, n, n_mem, T;
+  float scale, drop_p;
+  uint32_t seed;
+  const float* dout;
+  int dout_ld;
+  float* dq;
+  int dq_ld;
+  float* dself_k;
+  float* dself_v;
+  int dself_ld;
+  float* dmem_k;
+  float* dmem_v;
+  float* dbias;
+} mmvqa_fb_attn_desc;
+
+#define MMVQA_FB_MAX_HIDDENS 16   /* hiddens one aggregation takes: n_layers + 1 */
+#define MMVQA_FB_MAX_T 256        /* mem_len of the reference (mmbert.py:118): memory truncation is not built */
+
 /* Architecture of one Model(args) instance: the option surface of pretrain/roco_train.py:23-60,
  * vqamed2019/train.py:32-79 that the hot path reads (SURVEY.md section 5 "Config"). */
 typedef struct mmvqa_model_desc {
@@ -188,7 +230,7 @@ typedef struct mmvqa_model_desc {
   int resnet_layers[4]; /* (3,8,36,3) = resnet152 */
   int resnet_width;     /* 64 */
   int effnet_depth_div; /* 1 = full depth; >1 divides stage repeats (tests) */
-  int encoder;          /* 0 = transformer (BertLayer pre-LN), 1 = realformer */
+  int encoder;          /* 0 = transformer (BertLayer pre-LN), 1 = realformer, 2 = feedback-transformer */
   int hidden, heads, n_layers;
   int emb_vocab, max_pos, type_vocab;
   int num_vis;
@@ -201,6 +243,9 @@ typedef struct mmvqa_model_desc {
   float p_drop;         /* --hidden_dropout_prob (BertLayer attention + residual dropouts) */
   float p_emb_drop;     /* BertEmbeddings dropout (0.1) */
   float p_rf_drop;      /* RealFormer dp1/dp2 (0.1) */
+  float p_fb_drop;      /* Feedback Transformer attn_dropout / ff_dropout (0.1) */
+  int fb_tokens;        /* Feedback Transformer num_tokens = args.vocab_size: rows of its never-used token_emb / to_logits.1
+                         * (n_classes changes when classifier[2] is replaced, these do not) */
 } mmvqa_model_desc;
 
 /* gradient-ready notification of mmvqa_engine_set_grad_callback: grads[lo, hi) (float offsets) are final */
@@ -214,6 +259,7 @@ const char* mmvqa_last_error(void);
 size_t mmvqa_sizeof_gemm_desc(void);
 size_t mmvqa_sizeof_attn_desc(void);
 size_t mmvqa_sizeof_model_desc(void);
+size_t mmvqa_sizeof_fb_attn_desc(void);
 
 /* ---- op level (each is what one torch op of the reference's hot path lowers to) ------------ */
 /* kind: MMVQA_KIND_*; nchw: 1 only for the 7x7 stem (NCHW image source); tile: 0 auto */
@@ -227,6 +273,22 @@ int mmvqa_attention(const mmvqa_attn_desc* d, int head_dim, int backward, mmvqa_
 int mmvqa_qkv_attention_fwd(mmvqa_stream_t s, const float* xn, const float* W, const float* bias, const long long* mask,
                             float* qkv, float* probs, float* ctx, int B, int T, int hidden, int heads, float drop_p,
                             uint32_t seed);
+
+/* ---- Feedback Transformer (each launch serves one window of two tokens, or the single token that ends an odd T) */
+int mmvqa_fb_attention(const mmvqa_fb_attn_desc* d, int backward, mmvqa_stream_t s);
+/* agg[rows][H] = sum_l softmax(layer_weight)_l * hid_l, hid_l = hid + l*hid_stride, n_hid <= MMVQA_FB_MAX_HIDDENS */
+int mmvqa_fb_aggregate_fwd(mmvqa_stream_t s, const float* hid, long long hid_stride, int n_hid, const float* layer_weight,
+                           float* agg, long rows, int H);
+/* dh_l = softmax(layer_weight)_l * dagg written to dh + l*dh_stride; with dtop != NULL the share of the last hidden is
+ * ADDED to dtop instead (and dh's last slot is left alone).  d_layer_weight (may be NULL) is ADDED to, through the softmax,
+ * from the dot products <dagg, hid_l>: with float atomics, one per block and hidden. */
+int mmvqa_fb_aggregate_bwd(mmvqa_stream_t s, const float* dagg, const float* hid, long long hid_stride, int n_hid,
+                           const float* layer_weight, float* dh, long long dh_stride, float* dtop, float* d_layer_weight,
+                           long rows, int H);
+/* pre [M][2F] = (u | gate) -> y [M][F] = dropout(gelu(gate) * u), erf GELU; the dropout index of (r, c) is idx0 + r*F + c */
+int mmvqa_geglu_fwd(mmvqa_stream_t s, const float* pre, float* y, long M, int F, float drop_p, uint32_t seed, uint32_t idx0);
+int mmvqa_geglu_bwd(mmvqa_stream_t s, const float* dy, const float* pre, float* dpre, long M, int F, float drop_p,
+                    uint32_t seed, uint32_t idx0);
 
 /* BatchNorm2d (train: batch stats + running update repeated `reps` times; eval: running stats) */
 int mmvqa_bn_coef_fwd(mmvqa_stream_t s, const double* stat, int C, double count, float eps, const float* gamma,

@@ -73,6 +73,22 @@ class AttnDesc(C.Structure):
     ]
 
 
+class FbAttnDesc(C.Structure):
+    """mirror of mmvqa_fb_attn_desc"""
+    _fields_ = [
+        ("q", c_ptr), ("q_ld", C.c_int), ("mem_k", c_ptr), ("mem_v", c_ptr), ("mem_win", C.c_longlong), ("mem_ld", C.c_int),
+        ("self_k", c_ptr), ("self_v", c_ptr), ("self_ld", C.c_int), ("bias", c_ptr), ("probs", c_ptr), ("p_ld", C.c_int),
+        ("out", c_ptr), ("out_ld", C.c_int), ("B", C.c_int), ("n", C.c_int), ("n_mem", C.c_int), ("T", C.c_int),
+        ("scale", C.c_float), ("drop_p", C.c_float), ("seed", C.c_uint32),
+        ("dout", c_ptr), ("dout_ld", C.c_int), ("dq", c_ptr), ("dq_ld", C.c_int),
+        ("dself_k", c_ptr), ("dself_v", c_ptr), ("dself_ld", C.c_int), ("dmem_k", c_ptr), ("dmem_v", c_ptr), ("dbias", c_ptr),
+    ]
+
+
+FB_MAX_HIDDENS, FB_MAX_T = 16, 256   # MMVQA_FB_MAX_HIDDENS / MMVQA_FB_MAX_T
+ENC_TRANSFORMER, ENC_REALFORMER, ENC_FEEDBACK = 0, 1, 2   # mmvqa_model_desc.encoder
+
+
 class ResampleJob(C.Structure):
     """mirror of mmvqa_resample_job"""
     _fields_ = [
@@ -101,6 +117,7 @@ class ModelDesc(C.Structure):
         ("emb_vocab", C.c_int), ("max_pos", C.c_int), ("type_vocab", C.c_int), ("num_vis", C.c_int),
         ("head_kind", C.c_int), ("n_classes", C.c_int), ("supcon", C.c_int), ("feat_dim", C.c_int),
         ("use_relu", C.c_int), ("p_drop", C.c_float), ("p_emb_drop", C.c_float), ("p_rf_drop", C.c_float),
+        ("p_fb_drop", C.c_float), ("fb_tokens", C.c_int),
     ]
 
 
@@ -113,9 +130,15 @@ SIGNATURES = {
     "mmvqa_sizeof_gemm_desc": (_sz, []),
     "mmvqa_sizeof_attn_desc": (_sz, []),
     "mmvqa_sizeof_model_desc": (_sz, []),
+    "mmvqa_sizeof_fb_attn_desc": (_sz, []),
     "mmvqa_igemm": (_i, [C.POINTER(GemmDesc), _i, _i, _i, _P]),
     "mmvqa_attention": (_i, [C.POINTER(AttnDesc), _i, _i, _P]),
     "mmvqa_qkv_attention_fwd": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _f, _u32]),
+    "mmvqa_fb_attention": (_i, [C.POINTER(FbAttnDesc), _i, _P]),
+    "mmvqa_fb_aggregate_fwd": (_i, [_P, _P, _ll, _i, _P, _P, _l, _i]),
+    "mmvqa_fb_aggregate_bwd": (_i, [_P, _P, _P, _ll, _i, _P, _P, _ll, _P, _P, _l, _i]),
+    "mmvqa_geglu_fwd": (_i, [_P, _P, _P, _l, _i, _f, _u32, _u32]),
+    "mmvqa_geglu_bwd": (_i, [_P, _P, _P, _P, _l, _i, _f, _u32, _u32]),
     "mmvqa_bn_coef_fwd": (_i, [_P, _P, _i, _d, _f, _P, _P, _P, _P, _P, _f, _i, _i, _P, _P, _P, _P]),
     "mmvqa_bn_coef_bwd": (_i, [_P, _P, _i, _d, _P, _P, _P, _i, _P, _P, _P, _P, _P]),
     "mmvqa_bn_add_relu": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _l, _i]),
@@ -223,7 +246,7 @@ def lib():
         fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
-    for nm, st in (("gemm", GemmDesc), ("attn", AttnDesc), ("model", ModelDesc), ("resample_job", ResampleJob),
+    for nm, st in (("gemm", GemmDesc), ("attn", AttnDesc), ("model", ModelDesc), ("fb_attn", FbAttnDesc), ("resample_job", ResampleJob),
                    ("aug_record", AugRecord)):
         if nm in ("resample_job", "aug_record"):
             got = getattr(L, f"mmvqa_sizeof_{nm}")()

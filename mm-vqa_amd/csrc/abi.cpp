@@ -22,6 +22,7 @@ const char* mmvqa_last_error(void) { return mmvqa_get_error(); }
 size_t mmvqa_sizeof_gemm_desc(void) { return sizeof(mmvqa_gemm_desc); }
 size_t mmvqa_sizeof_attn_desc(void) { return sizeof(mmvqa_attn_desc); }
 size_t mmvqa_sizeof_model_desc(void) { return sizeof(mmvqa_model_desc); }
+size_t mmvqa_sizeof_fb_attn_desc(void) { return sizeof(mmvqa_fb_attn_desc); }
 
 static int check_gemm(const mmvqa_gemm_desc* d, int kind, int nchw) {
   if (!d) return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: null descriptor");
@@ -65,6 +66,26 @@ int mmvqa_qkv_attention_fwd(mmvqa_stream_t s, const float* xn, const float* W, c
                             uint32_t seed) {
   if (B <= 0 || drop_p < 0.f || drop_p >= 1.f) return mmvqa_set_error(MMVQA_ERR_ARG, "qkv_attention_fwd: B=%d drop_p=%g", B, (double)drop_p);
   return k_qkv_attn_fwd(ST(s), xn, W, bias, mask, qkv, probs, ctx, B, T, hidden, heads, drop_p, seed);
+}
+int mmvqa_fb_attention(const mmvqa_fb_attn_desc* d, int backward, mmvqa_stream_t s) {
+  if (!d) return mmvqa_set_error(MMVQA_ERR_ARG, "fb_attention: null descriptor");
+  return k_fb_attention(ST(s), *d, backward ? 1 : 0);
+}
+int mmvqa_fb_aggregate_fwd(mmvqa_stream_t s, const float* hid, long long hid_stride, int n_hid, const float* layer_weight,
+                           float* agg, long rows, int H) {
+  return k_fb_aggregate_fwd(ST(s), hid, hid_stride, n_hid, layer_weight, agg, rows, H);
+}
+int mmvqa_fb_aggregate_bwd(mmvqa_stream_t s, const float* dagg, const float* hid, long long hid_stride, int n_hid,
+                           const float* layer_weight, float* dh, long long dh_stride, float* dtop, float* d_layer_weight,
+                           long rows, int H) {
+  return k_fb_aggregate_bwd(ST(s), dagg, hid, hid_stride, n_hid, layer_weight, dh, dh_stride, dtop, d_layer_weight, rows, H);
+}
+int mmvqa_geglu_fwd(mmvqa_stream_t s, const float* pre, float* y, long M, int F, float drop_p, uint32_t seed, uint32_t idx0) {
+  return k_geglu_fwd(ST(s), pre, y, M, F, drop_p, seed, idx0);
+}
+int mmvqa_geglu_bwd(mmvqa_stream_t s, const float* dy, const float* pre, float* dpre, long M, int F, float drop_p,
+                    uint32_t seed, uint32_t idx0) {
+  return k_geglu_bwd(ST(s), dy, pre, dpre, M, F, drop_p, seed, idx0);
 }
 int mmvqa_bn_coef_fwd(mmvqa_stream_t s, const double* stat, int C, double count, float eps, const float* gamma,
                       const float* beta, float* run_mean, float* run_var, long long* nbt, float momentum, int reps,

@@ -209,6 +209,28 @@ int build_tables(mmvqa_engine* e) {
       e->bert[i].fc1 = b.lin(f + "fc1", H, 4 * H, true);
       e->bert[i].fc2 = b.lin(f + "fc2", 4 * H, H, true);
     }
+  } else if (d.encoder == 2) {
+    // models/mmbert.py:110-127 -> FeedbackTransformer(num_tokens, dim, depth, seq_len=2, mem_len=256, dim_head=64, heads=8);
+    // names of its state_dict.  to_kv is ONE tensor (attn.to_kv = shared_kv_proj, :229-230): it is listed under the
+    // reference's first name, the Python shim adds the aliases (layers.l>0 and shared_kv_proj).
+    const std::string fb = "transformer.block.";
+    b.add(fb + "token_emb.weight", 0, {d.fb_tokens, H});                         // never used (:260 is commented out)
+    e->fb_rel = b.add(fb + "pos_emb.relative_attention_bias.weight", 0, {32, 8});
+    e->fb.resize(d.n_layers);
+    for (int i = 0; i < d.n_layers; ++i) {
+      FBLayerRef& L = e->fb[i];
+      const std::string p = fb + "layers." + std::to_string(i) + ".";
+      L.ln_a = b.ln(p + "0.fn.norm", H);
+      L.to_q = b.lin(p + "0.fn.fn.to_q", H, 512, false);
+      if (i == 0) e->fb_kv = b.lin(p + "0.fn.fn.to_kv", H, 1024, false);
+      L.to_out = b.lin(p + "0.fn.fn.to_out", 512, H, true);
+      L.ln_f = b.ln(p + "1.fn.norm", H);
+      L.w1 = b.lin(p + "1.fn.fn.net.0", H, 8 * H, true);
+      L.w2 = b.lin(p + "1.fn.fn.net.3", 4 * H, H, true);
+    }
+    e->fb_lw = b.add(fb + "layer_weight", 0, {d.n_layers + 1});
+    b.ln(fb + "to_logits.0", H);                                                 // never used (to_logits_bool = False)
+    b.lin(fb + "to_logits.1", H, d.fb_tokens, true);
   } else {
     e->rf.resize(d.n_layers);
     const int es = H / 8;
@@ -271,7 +293,12 @@ static inline int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) 
 
 size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
   const mmvqa_model_desc& d = e->d;
-  if (B <= 0 || T <= 0 || T > 128 || T > d.max_pos || T <= d.num_vis) {
+  if (d.encoder == 2 && (T < 2 || T > MMVQA_FB_MAX_T)) {
+    mmvqa_set_error(MMVQA_ERR_ARG, "plan: the feedback-transformer takes 2 <= T <= %d tokens (T=%d): one token has no keys, "
+                                   "beyond %d the reference truncates its memory, which is not built", MMVQA_FB_MAX_T, T, MMVQA_FB_MAX_T);
+    return 0;
+  }
+  if (B <= 0 || T <= 0 || (T > 128 && d.encoder != 2) || T > d.max_pos || T <= d.num_vis) {
     mmvqa_set_error(MMVQA_ERR_ARG, "plan: bad B=%d T=%d (max_pos %d, num_vis %d, T<=128)", B, T, d.max_pos, d.num_vis);
     return 0;
   }
@@ -408,6 +435,19 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
       L.y = a.f(M * H); L.xn2 = a.f(M * H); L.mean2 = a.f(M); L.rstd2 = a.f(M);
       L.pre1 = a.f(M * 4 * H); L.h1 = a.f(M * 4 * H); L.z = a.f(M * H);
     }
+  } else if (d.encoder == 2) {
+    const size_t nh = (size_t)d.n_layers + 1, W2 = (size_t)2 * B;
+    e->fb_hid = a.f(nh * M * H); e->fb_ghid = a.f(nh * M * H);
+    e->fb_mem = a.f(M * 1024); e->fb_dmem = a.f(M * 1024); e->fb_agg = a.f(M * H); e->fb_out = a.f(M * H);
+    e->fb_dhs = a.f(nh * W2 * H);
+    e->fb_s[0] = a.f(W2 * 4 * H); e->fb_s[1] = a.f(W2 * H); e->fb_s[2] = a.f(W2 * 512); e->fb_s[3] = a.f(W2 * H); e->fb_s[4] = a.f(W2 * H);
+    for (auto& L : e->fb) {
+      L.xn_a = a.f(M * H); L.mean_a = a.f(M); L.rstd_a = a.f(M);
+      L.q = a.f(M * 512); L.kv = a.f(M * 1024); L.probs = a.f((size_t)B * 8 * (T + 1) * T); L.ctx = a.f(M * 512);
+      L.xmid = a.f(M * H); L.xn_f = a.f(M * H); L.mean_f = a.f(M); L.rstd_f = a.f(M);
+      L.pre = a.f(M * 8 * H); L.gg = a.f(M * 4 * H);
+      L.g_pre = a.f(M * 8 * H); L.g_mid = a.f(M * H); L.g_q = a.f(M * 512); L.g_kv = a.f(M * 1024);
+    }
   } else {
     for (auto& L : e->rf) {
       L.kqvo = a.f(M * 3 * H); L.probs = a.f((size_t)B * 8 * T * T); L.prev = a.f((size_t)B * T * T * 8);
@@ -465,7 +505,7 @@ static int prof_begin(mmvqa_engine* e, hipStream_t st, int cls, double flops, in
   mmvqa_engine::ProfRec r;
   HIP_CHECK_RET(hipEventCreate(&r.a));
   HIP_CHECK_RET(hipEventCreate(&r.b));
-  r.cls = cls; r.reg = e->prof_reg; r.flops = flops; r.tag = tag; r.bytes = bytes;
+  r.cls = cls; r.reg = e->prof_reg; r.flops = flops; r.tag = tag != HB_NONE ? tag : e->prof_tag; r.bytes = bytes;
   HIP_CHECK_RET(hipEventRecord(r.a, st));
   e->prof.push_back(r);
   return MMVQA_OK;
@@ -1635,6 +1675,160 @@ static int rf_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, SideR
   return MMVQA_OK;
 }
 
+// models/feedback_transformer_pytorch.py:257-312 with seq_len = 2: a recurrence over windows of two tokens (an odd T ends in
+// a window of one).  Rows are window-major: window w holds rows [w*2B, w*2B + n*B), row b*n + i, so that every linear of a
+// window is one product with M = n*B.  DESIGN.md section 15.
+static inline int fb_windows(int T) { return (T + 1) / 2; }
+static inline int fb_tokens(int T, int w) { return 2 * w + 1 < T ? 2 : 1; }
+
+static void fb_attn_fill(mmvqa_engine* e, const FBLayerRef& L, int layer, int w, int n, float p, mmvqa_fb_attn_desc& a) {
+  const size_t r0 = (size_t)w * 2 * e->B;
+  memset(&a, 0, sizeof(a));
+  a.q = WS(L.q) + r0 * 512; a.q_ld = 512;
+  a.mem_k = WS(e->fb_mem); a.mem_v = a.mem_k + 512; a.mem_win = (long long)2 * e->B * 1024; a.mem_ld = 1024;
+  if (n == 2) { a.self_k = WS(L.kv) + r0 * 1024; a.self_v = a.self_k + 512; a.self_ld = 1024; }
+  a.bias = PRM(e->fb_rel);
+  a.probs = WS(L.probs) + (size_t)w * e->B * 8 * 2 * e->T; a.p_ld = e->T;
+  a.out = WS(L.ctx) + r0 * 512; a.out_ld = 512;
+  a.B = e->B; a.n = n; a.n_mem = 2 * w; a.T = e->T;
+  a.scale = 0.125f;   // dim_head ** -0.5
+  a.drop_p = p; a.seed = site_seed(e, layer, 0);
+}
+static int fb_attn_call(mmvqa_engine* e, hipStream_t st, const mmvqa_fb_attn_desc& a, int bwd) {
+  REG(REG_ATTN);
+  const double fl = (bwd ? 10.0 : 4.0) * (double)a.B * 8 * a.n * (a.n_mem + (a.n == 2 ? 2 : 0)) * 64;
+  RUN(PROF_ATTN, fl, k_fb_attention(st, a, bwd));
+  return MMVQA_OK;
+}
+
+static int fb_forward(mmvqa_engine* e, hipStream_t st, const float* x_in, const float** x_out) {
+  REG(REG_ENC);
+  const mmvqa_model_desc& d = e->d;
+  const int H = d.hidden, B = e->B, T = e->T, NL = d.n_layers, nwin = fb_windows(T);
+  const size_t M = (size_t)B * T;
+  const float p = e->training ? d.p_fb_drop : 0.f;
+  RUN(PROF_OTHER, 0, k_fb_reorder(st, x_in, WS(e->fb_hid), B, T, H, 1));
+  for (int w = 0; w < nwin; ++w) {
+    const int n = fb_tokens(T, w);
+    const long Mw = (long)n * B;
+    const size_t r0 = (size_t)w * 2 * B;
+    for (int i = 0; i < NL; ++i) {
+      FBLayerRef& L = e->fb[i];
+      const float* x = WS(e->fb_hid) + i * M * H + r0 * H;
+      // x = x + to_out(attn(LN_a(x)))
+      TRY(ln_fwd(e, st, x, L.ln_a, WS(L.xn_a) + r0 * H, WS(L.mean_a) + r0, WS(L.rstd_a) + r0, Mw, 1e-5f));
+      { REG(REG_QKV);
+        TRY(lin_fwd(e, st, WS(L.xn_a) + r0 * H, H, Mw, L.to_q, WS(L.q) + r0 * 512, 512, ACT_NONE, nullptr, 0.f, 0, nullptr, 0));
+        if (n == 2)   // "only self attend if going at greater than 1 token at a time" (:163)
+          TRY(lin_fwd(e, st, WS(L.xn_a) + r0 * H, H, Mw, e->fb_kv, WS(L.kv) + r0 * 1024, 1024, ACT_NONE, nullptr, 0.f, 0, nullptr, 0)); }
+      mmvqa_fb_attn_desc a;
+      fb_attn_fill(e, L, i, w, n, p, a);
+      TRY(fb_attn_call(e, st, a, 0));
+      TRY(lin_fwd(e, st, WS(L.ctx) + r0 * 512, 512, Mw, L.to_out, WS(L.xmid) + r0 * H, H, ACT_NONE, nullptr, 0.f, 0, x, H));
+      // x = x + W2(drop(gelu(gate) * u)), (u | gate) = W1 LN_f(x)
+      TRY(ln_fwd(e, st, WS(L.xmid) + r0 * H, L.ln_f, WS(L.xn_f) + r0 * H, WS(L.mean_f) + r0, WS(L.rstd_f) + r0, Mw, 1e-5f));
+      TRY(lin_fwd(e, st, WS(L.xn_f) + r0 * H, H, Mw, L.w1, WS(L.pre) + r0 * 8 * H, 8 * H, ACT_NONE, nullptr, 0.f, 0, nullptr, 0));
+      RUN(PROF_OTHER, 0, k_geglu_fwd(st, WS(L.pre) + r0 * 8 * H, WS(L.gg) + r0 * 4 * H, Mw, 4 * H, p, site_seed(e, i, 1),
+                                     (uint32_t)(r0 * 4 * H)));
+      TRY(lin_fwd(e, st, WS(L.gg) + r0 * 4 * H, 4 * H, Mw, L.w2, WS(e->fb_hid) + (i + 1) * M * H + r0 * H, H, ACT_NONE, nullptr, 0.f,
+                  0, WS(L.xmid) + r0 * H, H));
+    }
+    if (w + 1 < nwin) {   // the memory the last window would write is never read
+      RUN(PROF_OTHER, 0, k_fb_aggregate_fwd(st, WS(e->fb_hid) + r0 * H, (long long)(M * H), NL + 1, PRM(e->fb_lw),
+                                            WS(e->fb_agg) + r0 * H, Mw, H));
+      REG(REG_QKV);
+      TRY(lin_fwd(e, st, WS(e->fb_agg) + r0 * H, H, Mw, e->fb_kv, WS(e->fb_mem) + r0 * 1024, 1024, ACT_NONE, nullptr, 0.f, 0, nullptr, 0));
+    }
+  }
+  RUN(PROF_OTHER, 0, k_fb_reorder(st, WS(e->fb_hid) + NL * M * H, WS(e->fb_out), B, T, H, 0));
+  *x_out = WS(e->fb_out);
+  return MMVQA_OK;
+}
+
+// dh (in t_a, [B][T][H]) -> dx (left in t_a).  The time loop (windows last to first, layers last to first) runs the data
+// gradients only and leaves every linear's output gradient in a buffer of the full B*T rows; the weight gradients follow the
+// loop, one product over all rows per linear, on the side stream.
+static int fb_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, SideReads& sr) {
+  (void)x_in;
+  REG(REG_ENC);
+  const mmvqa_model_desc& d = e->d;
+  const int H = d.hidden, B = e->B, T = e->T, NL = d.n_layers, nwin = fb_windows(T);
+  const size_t M = (size_t)B * T;
+  const float p = e->training ? d.p_fb_drop : 0.f;
+  float* ghid = WS(e->fb_ghid);
+  RUN(PROF_OTHER, 0, k_fb_reorder(st, WS(e->t_a), ghid + NL * M * H, B, T, H, 1));
+  HIP_CHECK_RET(hipMemsetAsync(WS(e->fb_dmem), 0, M * 1024 * sizeof(float), st));
+  float *s1 = WS(e->fb_s[0]), *s2 = WS(e->fb_s[1]), *s3 = WS(e->fb_s[2]), *s4 = WS(e->fb_s[3]), *s5 = WS(e->fb_s[4]);
+  for (int w = nwin - 1; w >= 0; --w) {
+    const int n = fb_tokens(T, w);
+    const long Mw = (long)n * B;
+    const size_t r0 = (size_t)w * 2 * B;
+    const bool wrote_mem = w + 1 < nwin;
+    if (wrote_mem) {
+      // every later window has added its share: rows r0.. of dmem are final.  dagg through the shared projection, then
+      // softmax(layer_weight)_l * dagg into each hidden's gradient (the top one at once, the others when the loop gets there)
+      { REG(REG_QKV);
+        TRY(lin_dgrad(e, st, WS(e->fb_dmem) + r0 * 1024, 1024, Mw, e->fb_kv, s2, H, 0, nullptr, 0, nullptr, nullptr, 0)); }
+      RUN(PROF_OTHER, 0, k_fb_aggregate_bwd(st, s2, WS(e->fb_hid) + r0 * H, (long long)(M * H), NL + 1, PRM(e->fb_lw),
+                                            WS(e->fb_dhs), (long long)2 * B * H, ghid + NL * M * H + r0 * H,
+                                            sr.data_only ? nullptr : GRD(e->fb_lw), Mw, H));
+    }
+    for (int i = NL - 1; i >= 0; --i) {
+      FBLayerRef& L = e->fb[i];
+      const float* gout = ghid + (i + 1) * M * H + r0 * H;
+      TRY(lin_dgrad(e, st, gout, H, Mw, L.w2, s1, 4 * H, 0, nullptr, 0, nullptr, nullptr, 0));
+      RUN(PROF_OTHER, 0, k_geglu_bwd(st, s1, WS(L.pre) + r0 * 8 * H, WS(L.g_pre) + r0 * 8 * H, Mw, 4 * H, p, site_seed(e, i, 1),
+                                     (uint32_t)(r0 * 4 * H)));
+      TRY(lin_dgrad(e, st, WS(L.g_pre) + r0 * 8 * H, 8 * H, Mw, L.w1, s2, H, 0, nullptr, 0, nullptr, nullptr, 0));
+      TRY(ln_bwd(e, st, s2, WS(L.xmid) + r0 * H, L.ln_f, WS(L.mean_f) + r0, WS(L.rstd_f) + r0, gout, WS(L.g_mid) + r0 * H, Mw,
+                 sr.data_only));
+      TRY(lin_dgrad(e, st, WS(L.g_mid) + r0 * H, H, Mw, L.to_out, s3, 512, 0, nullptr, 0, nullptr, nullptr, 0));
+      mmvqa_fb_attn_desc a;
+      fb_attn_fill(e, L, i, w, n, p, a);
+      a.dout = s3; a.dout_ld = 512;
+      a.dq = WS(L.g_q) + r0 * 512; a.dq_ld = 512;
+      if (n == 2) { a.dself_k = WS(L.g_kv) + r0 * 1024; a.dself_v = a.dself_k + 512; a.dself_ld = 1024; }
+      a.dmem_k = WS(e->fb_dmem); a.dmem_v = a.dmem_k + 512;
+      a.dbias = sr.data_only ? nullptr : GRD(e->fb_rel);
+      TRY(fb_attn_call(e, st, a, 1));
+      const float* dxn = s4;
+      { REG(REG_QKV);
+        TRY(lin_dgrad(e, st, WS(L.g_q) + r0 * 512, 512, Mw, L.to_q, s4, H, 0, nullptr, 0, nullptr, nullptr, 0));
+        if (n == 2) {
+          TRY(lin_dgrad(e, st, WS(L.g_kv) + r0 * 1024, 1024, Mw, e->fb_kv, s5, H, 0, nullptr, 0, nullptr, s4, H));
+          dxn = s5;
+        } }
+      TRY(ln_bwd(e, st, dxn, WS(e->fb_hid) + i * M * H + r0 * H, L.ln_a, WS(L.mean_a) + r0, WS(L.rstd_a) + r0,
+                 WS(L.g_mid) + r0 * H, ghid + i * M * H + r0 * H, Mw, sr.data_only));
+      if (wrote_mem)
+        RUN(PROF_OTHER, 0, k_axpy(st, ghid + i * M * H + r0 * H, WS(e->fb_dhs) + (size_t)i * 2 * B * H, 1.0f, Mw * H));
+    }
+  }
+  if (!sr.data_only) {
+    // weight gradients: the same sums over the windows, each formed in one product over all rows.  The shared to_kv weight
+    // collects one product per layer (self keys / values: the rows of the two-token windows, which come first) and one for
+    // the memory projection (input agg, every window but the last).
+    const long Mfull = (long)2 * B * (T / 2), Mmem = (long)2 * B * (nwin - 1);
+    struct TagScope { mmvqa_engine* e; TagScope(mmvqa_engine* e_) : e(e_) { e->prof_tag = HB_FB_WGRAD; } ~TagScope() { e->prof_tag = HB_NONE; } } tag(e);
+    for (int i = NL - 1; i >= 0; --i) {
+      FBLayerRef& L = e->fb[i];
+      TRY(lin_wgrad_side(e, sr, st, ghid + (i + 1) * M * H, H, WS(L.gg), 4 * H, (long)M, L.w2, true));
+      TRY(lin_wgrad_side(e, sr, st, WS(L.g_pre), 8 * H, WS(L.xn_f), H, (long)M, L.w1, true));
+      TRY(lin_wgrad_side(e, sr, st, WS(L.g_mid), H, WS(L.ctx), 512, (long)M, L.to_out, true));
+      REG(REG_QKV);
+      TRY(lin_wgrad_side(e, sr, st, WS(L.g_q), 512, WS(L.xn_a), H, (long)M, L.to_q, false));
+      TRY(lin_wgrad_side(e, sr, st, WS(L.g_kv), 1024, WS(L.xn_a), H, Mfull, e->fb_kv, false));
+    }
+    if (Mmem > 0) {
+      REG(REG_QKV);
+      TRY(lin_wgrad_side(e, sr, st, WS(e->fb_dmem), 1024, WS(e->fb_agg), H, Mmem, e->fb_kv, false));
+    }
+  }
+  sr.write(WS(e->t_a));
+  RUN(PROF_OTHER, 0, k_fb_reorder(st, ghid, WS(e->t_a), B, T, H, 0));
+  return MMVQA_OK;
+}
+
 // --------------------------------------------------------------------------- heads (models/mmbert.py:150-167)
 static int heads_forward(mmvqa_engine* e, hipStream_t st, const float* h) {
   REG(REG_HEAD);
@@ -1772,6 +1966,7 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
   e->prof_reg = REG_BACKBONE;
   const float* h = nullptr;
   if (d.encoder == 0) TRY(bert_forward(e, st, WS(e->emb_out), &h));
+  else if (d.encoder == 2) TRY(fb_forward(e, st, WS(e->emb_out), &h));
   else TRY(rf_forward(e, st, WS(e->emb_out), &h));
   e->enc_out_final = (size_t)(h - e->ws);
   if (d.head_kind == 2) {   // models/mmbert.py:159-161: logits = h; fc1 / classifier / head are not run
@@ -1801,6 +1996,7 @@ int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int d
     TRY(heads_backward(e, st, h, dlogits, dl_ld, dfeat, sr));
   }
   if (d.encoder == 0) TRY(bert_backward(e, st, WS(e->emb_out), sr));
+  else if (d.encoder == 2) TRY(fb_backward(e, st, WS(e->emb_out), sr));
   else TRY(rf_backward(e, st, WS(e->emb_out), sr));
   if (e->grad_cb) {
     sr.join();   // the weight gradients of the range may still be queued on the side stream
@@ -1860,6 +2056,7 @@ int engine_backward_feature(mmvqa_engine* e, hipStream_t st, const float* dlogit
   SideReads sr(sc, true);
   TRY(heads_backward(e, st, WS(e->enc_out_final), dlogits, dl_ld, nullptr, sr));
   if (d.encoder == 0) TRY(bert_backward(e, st, WS(e->emb_out), sr));
+  else if (d.encoder == 2) TRY(fb_backward(e, st, WS(e->emb_out), sr));
   else TRY(rf_backward(e, st, WS(e->emb_out), sr));
   size_t off = 0; int h = 0, w = 0, C = 0;
   const int k = feature_tap(e, &off, &h, &w, &C);
@@ -1879,6 +2076,11 @@ int engine_create(const mmvqa_model_desc* desc, mmvqa_engine** out) {
                            d.n_layers, d.num_vis);
   if (d.encoder == 0 && (d.heads < 1 || d.hidden % d.heads != 0))
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_create: heads=%d does not divide hidden=%d", d.heads, d.hidden);
+  if (d.encoder < 0 || d.encoder > 2)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_create: encoder=%d (0 = transformer, 1 = realformer, 2 = feedback-transformer)", d.encoder);
+  if (d.encoder == 2 && (d.n_layers + 1 > MMVQA_FB_MAX_HIDDENS || d.fb_tokens < 1))
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_create: feedback-transformer with n_layers=%d (at most %d) fb_tokens=%d", d.n_layers,
+                           MMVQA_FB_MAX_HIDDENS - 1, d.fb_tokens);
   if (d.cnn == 0 && d.resnet_width % 8 != 0)
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_create: resnet_width=%d must be a multiple of 8", d.resnet_width);
   if (d.head_kind < 0 || d.head_kind > 2)

@@ -84,6 +84,15 @@ struct RFLayerRef {
   size_t kqvo, probs, prev, res, s1, x1, mean1, rstd1, pre, hact, s2, x2, mean2, rstd2;
 };
 
+// Feedback Transformer layer (models/feedback_transformer_pytorch.py:225-241): pre-LN attention on the memory, pre-LN GEGLU
+// feed-forward.  Every buffer holds the full B*T rows in window-major order.
+struct FBLayerRef {
+  LNRef ln_a, ln_f;
+  LinRef to_q, to_out, w1, w2;
+  size_t xn_a, mean_a, rstd_a, q, kv, probs, ctx, xmid, xn_f, mean_f, rstd_f, pre, gg;   // forward
+  size_t g_pre, g_mid, g_q, g_kv;   // backward: the output gradients of the linears, kept for the weight gradients after the loop
+};
+
 // launch classes of the profiler: igemm_kernel | attention | everything else without matrix work | matrix work OUTSIDE
 // igemm_kernel (the register-resident stem tap of tapthin.hip, the squeeze-excite fully connected layers of se.hip)
 enum { PROF_IGEMM = 0, PROF_ATTN = 1, PROF_OTHER = 2, PROF_MATRIX = 3, PROF_NCLS = 4 };
@@ -94,7 +103,8 @@ enum { REG_BACKBONE = 0, REG_TAP = 1, REG_QKV = 2, REG_ATTN = 3, REG_ENC = 4, RE
 // HBM-bound kernels the profiler reports one by one (algorithmic bytes / measured time against the 8 TB/s roofline)
 enum { HB_NONE = 0, HB_BN_ADD_RELU, HB_MAXPOOL_FWD, HB_MAXPOOL_BWD, HB_LAYERNORM_FWD, HB_LAYERNORM_BWD, HB_DROPOUT_COPY,
        HB_BN_ACT_ADD, HB_DWCONV_FWD, HB_DWCONV_BWD_DATA, HB_DWCONV_BWD_WEIGHT, HB_SE_POOL, HB_SE_DGATE, HB_ACT_BWD_STATS,
-       HB_TAP_THIN_FWD, HB_TAP_THIN_BWD, HB_N };
+       HB_TAP_THIN_FWD, HB_TAP_THIN_BWD,
+       HB_FB_WGRAD /* not a kernel: every launch of the feedback encoder's weight-gradient block after the time loop */, HB_N };
 
 constexpr size_t SK_WS_FLOATS = (size_t)8 << 20;   // 32 MB: 8 splits of a 224-tile (64x64) product
 constexpr int SK_CNT_N = 16384;                    // tiles a ticketed split-K launch may have (one arrival ticket each)
@@ -120,6 +130,12 @@ struct mmvqa_engine {
   LNRef norm1, norm2;        // BertLayer (norm2 never used: quirk 2)
   std::vector<BertLayerRef> bert;
   std::vector<RFLayerRef> rf;
+  std::vector<FBLayerRef> fb;   // encoder == 2
+  LinRef fb_kv;                  // the ONE to_kv weight: every layer's self keys / values and shared_kv_proj
+  long long fb_rel = 0, fb_lw = 0;   // pos_emb.relative_attention_bias.weight [32][8], layer_weight [n_layers + 1]
+  // workspace: hiddens / their gradients [n_layers + 1][B*T][H], memory (k | v) and its gradient [B*T][1024], agg [B*T][H],
+  // the encoder output back in [B][T][H] order, per-window scratch
+  size_t fb_hid = 0, fb_ghid = 0, fb_mem = 0, fb_dmem = 0, fb_agg = 0, fb_out = 0, fb_dhs = 0, fb_s[5] = {0, 0, 0, 0, 0};
   LinRef fc1, cls0, cls2, head0, head2;
   LNRef cls_ln;
 
@@ -173,6 +189,7 @@ struct mmvqa_engine {
   // ---- profiling
   int prof_on = 0;
   int prof_reg = REG_BACKBONE;
+  int prof_tag = HB_NONE;   // tag of the launches that name none themselves (set around a block that is timed as a whole)
   struct ProfRec { hipEvent_t a, b; int cls, reg; double flops; int tag; double bytes; };
   long long tag_launch[HB_N];
   double tag_ms[HB_N], tag_bytes[HB_N];

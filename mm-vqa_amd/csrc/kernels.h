@@ -87,6 +87,15 @@ int k_soft_ce(hipStream_t st, const float* logits, int ld, const long long* targ
 int k_distill_mse(hipStream_t st, const float* h, int ld, const void* table, int table_f16, long long table_rows,
                   const long long* start, const int* count, int first, int B, int T, int H, float* row_sq, float* loss,
                   float* dh, int dld, float gscale);
+// fbattn.hip: the Feedback Transformer's window attention, hidden aggregation, GEGLU and row permutation
+int k_fb_attention(hipStream_t st, const mmvqa_fb_attn_desc& p, int bwd);
+int k_fb_aggregate_fwd(hipStream_t st, const float* hid, long long hstride, int nh, const float* lw, float* agg, long rows, int H);
+int k_fb_aggregate_bwd(hipStream_t st, const float* dagg, const float* hid, long long hstride, int nh, const float* lw, float* dh,
+                       long long dstride, float* dtop, float* dlw, long rows, int H);
+int k_geglu_fwd(hipStream_t st, const float* pre, float* y, long M, int F, float drop_p, uint32_t seed, uint32_t idx0);
+int k_geglu_bwd(hipStream_t st, const float* dy, const float* pre, float* dpre, long M, int F, float drop_p, uint32_t seed,
+                uint32_t idx0);
+int k_fb_reorder(hipStream_t st, const float* src, float* dst, int B, int T, int H, int to_window);
 int k_adam(hipStream_t st, float* p, float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps,
            int step, float gscale, int zero_grad);
 int k_axpy(hipStream_t st, float* y, const float* x, float a, long n);

@@ -25,7 +25,17 @@ import torch.nn as nn
 from . import _lib as L
 
 # parameters the reference never uses => their .grad stays None
-_NEVER_USED = ("transformer.blocks.norm2.", "transformer.trans.model.fc.")
+_NEVER_USED = ("transformer.blocks.norm2.", "transformer.trans.model.fc.",
+               "transformer.block.token_emb.", "transformer.block.to_logits.")
+
+# the Feedback Transformer's one to_kv weight (feedback_transformer_pytorch.py:229-230,246): the engine lists it under the
+# reference's first name; the reference's state_dict carries it under every layer's name and as shared_kv_proj
+_FB = "transformer.block."
+_FB_KV = _FB + "layers.0.0.fn.fn.to_kv.weight"
+
+
+def _fb_kv_aliases(n_layers):
+    return [f"{_FB}layers.{i}.0.fn.fn.to_kv.weight" for i in range(1, n_layers)] + [_FB + "shared_kv_proj.weight"]
 
 
 def desc_from_args(args, feat_dim=128, n_classes=None) -> L.ModelDesc:
@@ -44,8 +54,8 @@ def desc_from_args(args, feat_dim=128, n_classes=None) -> L.ModelDesc:
     d.resnet_width = int(getattr(args, "resnet_width", 64))
     d.effnet_depth_div = int(getattr(args, "effnet_depth_div", 1))
     tm = args.transformer_model
-    if "feedback-transformer" in tm:
-        raise NotImplementedError("feedback-transformer is outside the hot path (SURVEY.md section 2, row 9)")
+    if "feedback-transformer" in tm:     # models/mmbert.py:38-43 tests this string first
+        d.encoder = L.ENC_FEEDBACK
     elif "realformer" in tm:
         d.encoder = 1
     elif "transformer" in tm:
@@ -78,6 +88,8 @@ def desc_from_args(args, feat_dim=128, n_classes=None) -> L.ModelDesc:
     d.p_drop = float(getattr(args, "hidden_dropout_prob", 0.3))
     d.p_emb_drop = float(getattr(args, "emb_dropout_prob", 0.1))
     d.p_rf_drop = float(getattr(args, "rf_dropout_prob", 0.1))
+    d.p_fb_drop = float(getattr(args, "fb_dropout_prob", 0.1))   # mmbert.py:118-119: attn_dropout = ff_dropout = 0.1
+    d.fb_tokens = int(args.vocab_size)
     return d
 
 
@@ -201,6 +213,16 @@ class Model(nn.Module):
                 self._params_by_name[name] = prm
             else:
                 mod.register_buffer(parts[-1], view)
+        if desc.encoder == L.ENC_FEEDBACK:
+            shared = self._params_by_name[_FB_KV]
+            for name in _fb_kv_aliases(desc.n_layers):
+                parts = name.split(".")
+                mod = self
+                for p in parts[:-1]:
+                    if p not in mod._modules:
+                        mod.add_module(p, _Node())
+                    mod = mod._modules[p]
+                mod.register_parameter(parts[-1], shared)   # the same Parameter: named_parameters() lists it once
         if init:
             self._init_weights()
         if old_state is not None:
@@ -232,6 +254,10 @@ class Model(nn.Module):
                 t.zero_()
             elif kind == 1:
                 t.fill_(1.0 if name.endswith("running_var") else 0.0)
+            elif name == _FB + "layer_weight":
+                t.fill_(1.0)          # torch.ones(depth + 1)
+            elif name in (_FB + "token_emb.weight", _FB + "pos_emb.relative_attention_bias.weight"):
+                t.normal_(0.0, 1.0)   # nn.Embedding
             elif name.endswith("embeddings.weight"):
                 t.normal_(0.0, 0.02)
                 if "word_embeddings" in name:
@@ -291,6 +317,16 @@ class Model(nn.Module):
                 mod._buffers[parts[-1]] = view
         return self
 
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """The Feedback Transformer's shared to_kv weight arrives under n_layers + 1 names; the aliases of a real
+        checkpoint are equal, so all of them take the tensor of layers.0 when it is there."""
+        if self._desc.encoder == L.ENC_FEEDBACK and _FB_KV in state_dict:
+            state_dict = dict(state_dict)
+            for name in _fb_kv_aliases(self._desc.n_layers):
+                if name in state_dict:
+                    state_dict[name] = state_dict[_FB_KV]
+        return super().load_state_dict(state_dict, strict=strict, **kw)
+
     def __del__(self):
         try:
             if self._handle is not None:
@@ -335,10 +371,13 @@ class Model(nn.Module):
         self._seed_ctr = int(seed) & 0x7FFFFFFF
 
     def _engine_forward(self, img, ids, seg, mask, prec=0):
+        d = self._desc
+        if d.encoder == L.ENC_FEEDBACK and not 2 <= ids.shape[1] <= L.FB_MAX_T:
+            raise ValueError(f"the feedback-transformer takes 2 <= T <= {L.FB_MAX_T} tokens, not T={ids.shape[1]}: one token "
+                             f"has no keys to attend to, and beyond {L.FB_MAX_T} the reference truncates its memory (not built)")
         if not img.is_cuda:
             raise L.MMVQAError("mm-vqa_amd runs on the GPU only: move the model and inputs to 'cuda' "
                                "(there is no CPU fallback by design)")
-        d = self._desc
         img = img.contiguous().float()
         ids, seg, mask = (t.contiguous().long() for t in (ids, seg, mask))
         B, T = ids.shape
@@ -516,7 +555,8 @@ class Model(nn.Module):
 
     HBM_KERNELS = ("bn_add_relu", "maxpool_fwd", "maxpool_bwd", "layernorm_fwd", "layernorm_bwd", "dropout_copy", "bn_act_add",
                    "dwconv_fwd", "dwconv_bwd_data", "dwconv_bwd_weight", "se_pool", "se_dgate", "act_bwd_stats",
-                   "tap_thin_fwd", "tap_thin_bwd")
+                   "tap_thin_fwd", "tap_thin_bwd",
+                   "fb_weight_gradients")   # (not a kernel: the feedback encoder's weight-gradient block after its time loop)
 
     def profile_read_hbm(self):
         """{kernel: {launches, ms, bytes}} of the HBM-bound kernels of the profiled step (mmvqa_engine_profile_read_hbm)"""
