@@ -62,10 +62,28 @@ struct GemmAux {
   int xcd;       // workgroup ids are dealt round-robin to the 8 XCDs: renumber so that an XCD gets a CONTIGUOUS run of
                  // tiles (1: the N-tiles of an M-panel, 2: the M-tiles of an N-panel share that XCD's L2 instead of
                  // pulling the panel into up to 8 of them)
+  // compact stride-2 data gradient (S2C instantiations only; appended so that every offset above stays where it was):
+  // the output pixels are split by parity (y&1, x&1) into four classes of s2_M = images * OH/2 * OW/2 rows; grid.y holds
+  // s2_tiles row tiles per class, class slot c = by / s2_tiles has parity bits (s2_ord >> 2c) & 3 = py*2 + px
+  FastDiv s2_hw, s2_w;   // row of a class -> (image, i, j): divisors OH/2 * OW/2 and OW/2
+  int s2_M, s2_tiles, s2_ord;
 };
+
+// class row (n, i, j) of a compact stride-2 data gradient -> pixel row (n, 2i + py, 2j + px) of the output grid
+struct S2Map {
+  FastDiv hw, w;
+  int hw2, w2, OW, py, px, M;   // M: rows of one class
+};
+struct NoMap {};
 
 __device__ __forceinline__ int fdiv(int n, const FastDiv& f) {
   return f.d == 1 ? n : (int)(__umulhi((uint32_t)n, f.mul) >> f.shr);
+}
+
+__device__ __forceinline__ int s2_pixel(const S2Map& mp, int m) {
+  const int n = fdiv(m, mp.hw), rem = m - n * mp.hw2;
+  const int i = fdiv(rem, mp.w), j = rem - i * mp.w2;
+  return n * 4 * mp.hw2 + (2 * i + mp.py) * mp.OW + 2 * j + mp.px;
 }
 
 __device__ __forceinline__ f32x4 ld4(const float* p) { return *reinterpret_cast<const f32x4*>(p); }
@@ -154,12 +172,18 @@ extern "C" int mmvqa_debug_set_trace(unsigned long long* buf) {
 // -> statistics.  src(rl, c4) yields columns c4*4..+3 of tile row rl: the LDS-staged accumulators in the GEMM kernel,
 // the sum of the partial tiles in the split-K finishing kernel.  smem: BN*3 doubles + BN floats for the reductions
 // (free to overwrite once every thread has read its rows).
-template <int BM, int BN, int NT, class Src>
-__device__ __forceinline__ void general_epilogue(const GemmParams& p, int m0, int n0, int tid, float* smem, int slot_seed, Src src) {
+// Map = S2Map (compact stride-2 data gradient): m0 and the tile's rows count inside one parity class of map.M rows, and
+// every row-indexed tensor is addressed at the pixel row s2_pixel(map, row).
+template <int BM, int BN, int NT, class Src, class Map = NoMap>
+__device__ __forceinline__ void general_epilogue(const GemmParams& p, int m0, int n0, int tid, float* smem, int slot_seed, Src src,
+                                                 Map map = Map{}) {
   constexpr int CH = BN / 4;            // float4 chunks per tile row
   constexpr int RP = NT / CH;           // rows per pass of the whole workgroup
   constexpr int NPASS = BM / RP;
-  const int M = p.M, N = p.N;
+  constexpr bool MAPPED = std::is_same<Map, S2Map>::value;
+  int M_;
+  if constexpr (MAPPED) M_ = map.M; else M_ = p.M;
+  const int M = M_, N = p.N;
   const int c4 = tid % CH, rg = tid / CH;
   const int col = n0 + c4 * 4;
   const bool full = col + 3 < N;          // whole float4 inside the matrix
@@ -211,11 +235,13 @@ __device__ __forceinline__ void general_epilogue(const GemmParams& p, int m0, in
       if (m0 + rg + ps0 * RP >= M || !cok) break;
       f32x4 vv[UP], pr[UP], rr[UP], mm[UP], zz[UP], zz2[UP];
       bool ok[UP];
+      int prow[UP];   // MAPPED: pixel row of the tile row
 #pragma unroll
       for (int u = 0; u < UP; ++u) {
         const int rl = rg + (ps0 + u) * RP, row = m0 + rl;
         ok[u] = row < M;
-        const size_t rw = ok[u] ? (size_t)row : (size_t)m0;   // clamped: loads of a row past the end are discarded
+        size_t rw = ok[u] ? (size_t)row : (size_t)m0;   // clamped: loads of a row past the end are discarded
+        if constexpr (MAPPED) { prow[u] = s2_pixel(map, (int)rw); rw = (size_t)prow[u]; }
         vv[u] = src(rl, c4);
         if (dact) pr[u] = ldv(Pre, rw * pre_ld + col);
         if (R) rr[u] = ldv(R, rw * r_ld + col);
@@ -228,7 +254,8 @@ __device__ __forceinline__ void general_epilogue(const GemmParams& p, int m0, in
 #pragma unroll
       for (int u = 0; u < UP; ++u) {
         if (!ok[u]) continue;
-        const int row = m0 + rg + (ps0 + u) * RP;
+        int row = m0 + rg + (ps0 + u) * RP;
+        if constexpr (MAPPED) row = prow[u];
         f32x4 v = vv[u] + bias;
         if (Cpre) stv(Cpre, (size_t)row * ldc + col, v);
         if (dact) {
@@ -324,8 +351,17 @@ __device__ __forceinline__ void general_epilogue(const GemmParams& p, int m0, in
 // KS = intra-workgroup split of every K-tile over KS groups of 4 waves (KS*256 threads): for problems
 // with fewer workgroups than CUs it doubles the waves per SIMD (latency hiding) at the price of one
 // LDS reduction at the end.
-template <int BM, int BN, int BK, int KIND, bool NCHW, int KS, int PREC = MMVQA_PREC_F32>
+//
+// S2C = compact stride-2 data gradient (an instantiation family of its own: the dense instantiations must not change,
+// DESIGN 4.2).  A dense stride-2 data gradient walks all KH*KW taps for every output pixel although only the taps with
+// kh = (y + pad) mod 2, kw = (x + pad) mod 2 reach a source pixel; the others are range-checked to zeros and multiplied.
+// Here the pixels are split by parity into four classes, each a dense contraction over its own taps (walked in
+// ascending (kh, kw), so an unsplit element is bit-identical to the dense walk), all in ONE launch: the class is folded
+// into the row-tile index (class with the most taps first), a tile's rows are class rows and reach their pixel through
+// S2Map.  A class without taps runs the epilogue on zero accumulators.  Uniform-tap loaders with the halo mask only.
+template <int BM, int BN, int BK, int KIND, bool NCHW, int KS, int PREC = MMVQA_PREC_F32, bool S2C = false>
 __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, const GemmAux x) {
+  static_assert(!S2C || (KIND == KIND_DGRAD && !NCHW && PREC == MMVQA_PREC_F32), "compact form: fp32 NHWC data gradient only");
   constexpr int NT = 256 * KS;
   constexpr int WM = BM / 2, WN = BN / 2, TM = WM / 32, TN = WN / 32;
   constexpr bool F16 = (PREC == MMVQA_PREC_F16);   // f16-operand family: halves in LDS, 32x32x16 MFMA
@@ -355,7 +391,7 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
   float* ctab = smem + 2 * A_TILE + 2 * B_TILE + MAX_TAPS;               // [3][channels]: folded BatchNorm coefficients
 
   // ------------------------------------------------------------------ work of this workgroup
-  const int nkt_total = (p.K + BK - 1) / BK;
+  int nkt_total = (p.K + BK - 1) / BK;
   __shared__ int sk_last;
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = (tid >> 6) & 3, ks = tid >> 8;
@@ -380,6 +416,22 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
       bz = (int)(r / gx);
     }
   }
+  // compact form: parity class of this row tile, first tap (c_kh0, c_kw0) and tap counts of the class
+  S2Map smap = {};
+  const int by_tile = by;   // row-tile index in the grid (by becomes the row tile inside the class)
+  int c_kh0 = 0, c_kw0 = 0, c_nkh = 1, c_nkw = 1;
+  if constexpr (S2C) {
+    const int T = x.s2_tiles;
+    const int slot = (by >= T ? 1 : 0) + (by >= 2 * T ? 1 : 0) + (by >= 3 * T ? 1 : 0);
+    by -= slot * T;
+    const int pp = (x.s2_ord >> (2 * slot)) & 3;
+    smap.hw = x.s2_hw; smap.w = x.s2_w; smap.hw2 = (p.g_OH >> 1) * (p.g_OW >> 1); smap.w2 = p.g_OW >> 1; smap.OW = p.g_OW;
+    smap.py = pp >> 1; smap.px = pp & 1; smap.M = x.s2_M;
+    c_kh0 = (smap.py + p.g_pad) & 1; c_kw0 = (smap.px + p.g_pad) & 1;
+    c_nkh = c_kh0 < p.g_KH ? (p.g_KH - c_kh0 + 1) >> 1 : 0;
+    c_nkw = c_kw0 < p.g_KW ? (p.g_KW - c_kw0 + 1) >> 1 : 0;
+    nkt_total = c_nkh * c_nkw * (p.g_Cs / BK);   // g_Cs % BK == 0 (uniform-tap loaders)
+  }
   const int m0 = by * BM, n0 = bx * BN;
 #ifdef EXP_SAMETILE   // experiment: every workgroup loads the tiles of workgroup (0,0) -> all loads hit in L2
   const int lm0 = 0, ln0 = 0;
@@ -388,10 +440,14 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
 #endif
 
   // K range of this split
-  const int kt_begin = bz * p.ktiles_per_split;
-  int kt_end = kt_begin + p.ktiles_per_split;
+  int per_split = p.ktiles_per_split;
+  if constexpr (S2C) per_split = gridDim.z == 1 ? nkt_total : (nkt_total + (int)gridDim.z - 1) / (int)gridDim.z;   // of this class
+  const int kt_begin = bz * per_split;
+  int kt_end = kt_begin + per_split;
   if (kt_end > nkt_total) kt_end = nkt_total;
-  const int nkt = kt_end - kt_begin;
+  int nkt_ = kt_end - kt_begin;
+  if constexpr (S2C) nkt_ = nkt_ > 0 ? nkt_ : 0;   // a short class leaves the last splits without K-tiles
+  const int nkt = nkt_;
   const int k_begin = kt_begin * BK;
 
   const int OHW = p.g_OH * p.g_OW;
@@ -409,9 +465,9 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
   // FWD / DGRAD: all g_Cs channels of the gathered operand (one channel per thread and pass); WGRAD: the BM channels
   // (= output rows) of this workgroup.  Workgroup (0,0,0) publishes what the separate coefficient launch would write.
   const int fold_C = A_ROWK ? p.g_Cs : BM;
-  if (x.ldsc) {
+  if (x.ldsc && (!S2C || nkt_total > 0)) {   // (a class without taps reads no coefficients; workgroup (0,0,0) has taps)
     const BnFold& f = p.a_fold;
-    const bool pub = f.publish && bx == 0 && by == 0 && bz == 0;
+    const bool pub = f.publish && bx == 0 && by_tile == 0 && bz == 0;
     if constexpr (A_ROWK) {
       for (int c = tid; c < fold_C; c += NT) {
         float k0, k1, k2 = 0.f;
@@ -441,7 +497,26 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
   int a_img[NAC];                             // PRO_SILU_GATE: image index of the row
   f32x4 ac0_i = {1, 1, 1, 1}, ac1_i = {0, 0, 0, 0}, ac2_i = {0, 0, 0, 0};   // WGRAD: loop-invariant A' coefficients
   const int akm_x4 = tid % A_X4, akm_k0 = tid / A_X4;
-  if constexpr (A_ROWK) {
+  if constexpr (S2C) {
+    // class row -> pixel (n, 2i + py, 2j + px); validity bit q = ih * c_nkw + iw of a_mask belongs to the class's q-th
+    // tap (kh, kw) = (c_kh0 + 2 ih, c_kw0 + 2 iw), whose source pixel is (qy - ih, qx - iw)
+#pragma unroll
+    for (int r = 0; r < NA; ++r) {
+      const int row = lm0 + a_r0 + RSTEP * r;
+      a_base[r] = 0; a_mask[r] = 0; a_pix[r] = 0; a_y0[r] = 0; a_x0[r] = 0; a_img[r] = 0;
+      if (row < smap.M) {
+        const int n = fdiv(row, smap.hw), rem = row - n * smap.hw2;
+        const int i = fdiv(rem, smap.w), j = rem - i * smap.w2;
+        const int qy = (2 * i + smap.py + p.g_pad) >> 1, qx = (2 * j + smap.px + p.g_pad) >> 1;
+        a_base[r] = ((n * p.g_SH + qy) * p.g_SW + qx) * p.a_ld;
+        uint32_t xb = 0;
+        for (int iw = 0; iw < c_nkw; ++iw) xb |= ((unsigned)(qx - iw) < (unsigned)p.g_SW ? 1u : 0u) << iw;
+        uint32_t mk = 0;
+        for (int ih = 0; ih < c_nkh; ++ih) mk |= ((unsigned)(qy - ih) < (unsigned)p.g_SH ? xb : 0u) << (ih * c_nkw);
+        a_mask[r] = mk;
+      }
+    }
+  } else if constexpr (A_ROWK) {
     if (x.fast == 0) {   // per-thread (tap, channel) walk of the general loaders only
       int k = k_begin + a_kq;
       if (taps > 1) { a_tap = k / p.g_Cs; a_c = k - a_tap * p.g_Cs; } else { a_c = k; a_tap = (k >= p.g_Cs) ? 1 : 0; }
@@ -797,6 +872,7 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
     int f_runT = 0, f_tapw = 0;                   // weight gradient of a 3x3: pixel-table offset, the workgroup's tap
     const int f_voffC = a_kq * 4;
     int f_tap = 0, f_c = 0, f_kh = 0, f_kw = 0;   // (tap, channel) of the next K-tile to load: wave-uniform
+    int f_q = 0;                                  // compact form: position of that tap among the taps of the class
     int f_runA = 0, f_runB = 0;                   // running byte offsets of the plain (non-gather) operands
     int f_sA = 0, f_sB = 0, f_sC = 0;             // soffsets of the tile being loaded
     const int f_sh = s - 1;                       // DGRAD: kh / stride as a shift (stride 1 or 2)
@@ -822,7 +898,12 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
           rC1 = __builtin_amdgcn_make_buffer_rsrc((void*)p.a_c1, 0, p.g_Cs * 4, FLAGS);
           rC2 = __builtin_amdgcn_make_buffer_rsrc((void*)(APRO == PRO_DZ ? p.a_c2 : p.a_c1), 0, p.g_Cs * 4, FLAGS);
         }
-        if (k_begin != 0) {
+        if constexpr (S2C) {
+          int qh = 0, qw = 0;
+          if (k_begin != 0) { f_q = k_begin / p.g_Cs; f_c = k_begin - f_q * p.g_Cs; qh = f_q / (c_nkw > 0 ? c_nkw : 1); qw = f_q - qh * c_nkw; }
+          f_kh = c_kh0 + 2 * qh; f_kw = c_kw0 + 2 * qw;
+          f_tap = f_kh * p.g_KW + f_kw;
+        } else if (k_begin != 0) {
           if (taps > 1) { f_tap = k_begin / p.g_Cs; f_c = k_begin - f_tap * p.g_Cs; } else { f_tap = 0; f_c = k_begin; }
           f_kh = f_tap / p.g_KW; f_kw = f_tap - f_kh * p.g_KW;
         }
@@ -888,7 +969,9 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
       } else if constexpr (FAST == 2) {
 #pragma unroll
         for (int r = 0; r < NAC; ++r) {
-          const int t = __builtin_amdgcn_sbfe((int)a_mask[r], f_tap & 31, 1);
+          int t;
+          if constexpr (S2C) t = (f_kh < p.g_KH && f_kw < p.g_KW) ? __builtin_amdgcn_sbfe((int)a_mask[r], f_q & 31, 1) : 0;
+          else t = __builtin_amdgcn_sbfe((int)a_mask[r], f_tap & 31, 1);
           S.tm[r] = t;
           f_ve[r] = (t & f_voffA[r]) | (~t & BIG);
         }
@@ -896,7 +979,8 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
     };
     auto f_scalars = [&](Stage& S) __attribute__((always_inline)) {
       if constexpr (A_ROWK) {
-        const bool live = f_tap < taps;
+        bool live = f_tap < taps;
+        if constexpr (S2C) live = f_kh < p.g_KH && f_kw < p.g_KW;   // past the class's last tap (or a class without taps)
         const int toff = (KIND == KIND_FWD) ? (f_kh * p.g_SW + f_kw) * p.a_ld
                                             : f_maxneg - ((f_kh >> f_sh) * p.g_SW + (f_kw >> f_sh)) * p.a_ld;
         f_sA = live ? (toff + f_c) * 4 : BIG;
@@ -927,7 +1011,14 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
 #ifdef EXP_NOADVANCE   // experiment: every K-tile re-reads the first tile (valid addresses, cache-resident)
       return;
 #endif
-      if constexpr (A_ROWK) {
+      if constexpr (S2C) {
+        f_c += BK;
+        if (f_c >= p.g_Cs) {
+          f_c = 0; ++f_q; f_kw += 2;
+          if (f_kw >= p.g_KW) { f_kw = c_kw0; f_kh += 2; }
+          f_tap = f_kh * p.g_KW + f_kw;
+        }
+      } else if constexpr (A_ROWK) {
         f_c += BK;
         if (f_c >= p.g_Cs) {
           f_c = 0; ++f_tap; ++f_kw;
@@ -1292,6 +1383,9 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
           default: run(I0{}, I0{}, G{}, L0{});
         }
       }
+    } else if constexpr (S2C) {   // (the host launches the compact form with x.fast == 2 only)
+      if (p.a_pro == PRO_DZ) { if (x.ldsc) run(I2{}, I0{}, F2{}, L1{}); else run(I2{}, I0{}, F2{}, L0{}); }
+      else run(I0{}, I0{}, F2{}, L0{});
     } else if constexpr (KIND == KIND_DGRAD) {
       if (x.fast == 1) {
         if (p.a_pro == PRO_DZ) { if (x.ldsc) run(I2{}, I0{}, F1{}, L1{}); else run(I2{}, I0{}, F1{}, L0{}); }
@@ -1369,7 +1463,9 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
   }
 
   TRACE_EPI(0);
-  const int M = p.M, N = p.N;
+  int M_;
+  if constexpr (S2C) M_ = smap.M; else M_ = p.M;   // compact form: m0 and the tile's rows count inside the parity class
+  const int M = M_, N = p.N;
   const int c4 = tid % CH, rg = tid / CH;
   const int col = n0 + c4 * 4;
   const bool full = col + 3 < N;          // whole float4 inside the matrix
@@ -1397,7 +1493,7 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
     // bytes sc1, every storing wave drains them, a workgroup barrier, then ONE lane's agent-scope atomic) and draws a
     // ticket; the contributor whose ticket is the last sums the partial tiles (sc1 loads; always in slot order, so the
     // result does not depend on who came last) and runs the epilogue.  Nobody waits for anybody.
-    const int n_contrib = x.sk_slots, my = bz, tile_id = by * x.sk_gx + bx;
+    const int n_contrib = x.sk_slots, my = bz, tile_id = by_tile * x.sk_gx + bx;
     constexpr int Q = BM * BN / 4;   // float4 of a tile
     __amdgpu_buffer_rsrc_t rP = __builtin_amdgcn_make_buffer_rsrc((void*)(x.sk_part + (size_t)tile_id * x.sk_slots * (BM * BN)), 0,
                                                                   x.sk_slots * BM * BN * 4, 0x00020000);
@@ -1440,17 +1536,20 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
 
   if (x.part) {
     // split-K over workgroups, finished by splitk_finish_kernel: this workgroup's partial tile, row-wise 16-byte stores
-    float* P = x.part + (size_t)bz * M * N;
+    float* P = x.part + (size_t)bz * p.M * N;
 #pragma unroll 1
     for (int ps = 0; ps < NPASS; ++ps) {
       const int rl = rg + ps * RP, row = m0 + rl;
       if (row >= M || col >= N) break;
-      stv(P, (size_t)row * N + col, *reinterpret_cast<const f32x4*>(&ctile[rl * LDC + c4 * 4]));
+      size_t prow = (size_t)row;   // the partial tiles are [split][pixel][N] also in the compact form
+      if constexpr (S2C) prow = (size_t)s2_pixel(smap, row);
+      stv(P, prow * N + col, *reinterpret_cast<const f32x4*>(&ctile[rl * LDC + c4 * 4]));
     }
     TRACE_MARK(4);
     return;
   }
 
+  if constexpr (!S2C) {   // (accumulating and tap epilogues: never in the compact form, host-checked)
   if (p.c_atomic) {
     // accumulate (weight gradients / split-K): one float per lane so that a wave-instruction adds to
     // 256 contiguous bytes (MI355X_MICROARCH "Global float atomics": full rate only in that shape)
@@ -1530,11 +1629,14 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
     TRACE_MARK(4);
     return;
   }
+  }
 
-  general_epilogue<BM, BN, NT>(p, m0, n0, tid, smem, (int)(blockIdx.y + blockIdx.x * 7 + blockIdx.z * 3),
-                               [&](int rl, int cq) __attribute__((always_inline)) {
-                                 return *reinterpret_cast<const f32x4*>(&ctile[rl * LDC + cq * 4]);
-                               });
+  auto staged = [&](int rl, int cq) __attribute__((always_inline)) {
+    return *reinterpret_cast<const f32x4*>(&ctile[rl * LDC + cq * 4]);
+  };
+  const int slot_seed = (int)(blockIdx.y + blockIdx.x * 7 + blockIdx.z * 3);
+  if constexpr (S2C) general_epilogue<BM, BN, NT>(p, m0, n0, tid, smem, slot_seed, staged, smap);
+  else general_epilogue<BM, BN, NT>(p, m0, n0, tid, smem, slot_seed, staged);
   TRACE_MARK(4);
 }
 
@@ -1591,7 +1693,7 @@ static FastDiv make_fastdiv(int d) {
   return f;
 }
 
-template <int BM, int BN, int BK, int KIND, bool NCHW, int KS = 1, int PREC = MMVQA_PREC_F32>
+template <int BM, int BN, int BK, int KIND, bool NCHW, int KS = 1, int PREC = MMVQA_PREC_F32, bool S2C = false>
 static int launch_cfg(GemmParams p, hipStream_t stream) {
   constexpr bool A_ROWK = (KIND != KIND_WGRAD);
   constexpr bool B_ROWK = (KIND == KIND_FWD);
@@ -1605,7 +1707,7 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   if (!(attr_dev_mask >> (dev & 31) & 1)) {
-    HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<BM, BN, BK, KIND, NCHW, KS, PREC>,
+    HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<BM, BN, BK, KIND, NCHW, KS, PREC, S2C>,
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max));
     attr_dev_mask |= 1 << (dev & 31);
   }
@@ -1642,6 +1744,8 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
         x.fast = 2;
     }
   }
+  if (S2C && x.fast != 2)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: the compact stride-2 data gradient needs the uniform-tap loaders");
   // BatchNorm coefficients of the A prologue folded in the kernel's setup (mmvqa_bn_fold).  The K loop reads the LDS table
   // only in its uniform-tap forms; the weight gradient keeps its (loop-invariant) coefficients in registers.  Anything
   // else -- general loaders, a table beyond FOLD_MAX_FLOATS -- gets the coefficient launch in front, as before.
@@ -1670,6 +1774,23 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
   }
   const size_t smem = ((tile_floats + fold_floats > epi_floats ? tile_floats + fold_floats : epi_floats)) * sizeof(float);
   dim3 grid((p.N + BN - 1) / BN, (p.M + BM - 1) / BM, p.splitk);
+  x.s2_hw = make_fastdiv(1); x.s2_w = make_fastdiv(1); x.s2_M = 0; x.s2_tiles = 0; x.s2_ord = 0;
+  if (S2C) {
+    // four parity classes of M / 4 rows each in one grid; the class with the most taps first (its tiles run longest)
+    x.s2_hw = make_fastdiv((p.g_OH / 2) * (p.g_OW / 2));
+    x.s2_w = make_fastdiv(p.g_OW / 2);
+    x.s2_M = p.M / 4;
+    x.s2_tiles = (x.s2_M + BM - 1) / BM;
+    grid.y = 4 * x.s2_tiles;
+    int cls[4] = {0, 1, 2, 3}, nt[4];
+    for (int c = 0; c < 4; ++c) {
+      const int h0 = ((c >> 1) + p.g_pad) & 1, w0 = ((c & 1) + p.g_pad) & 1;
+      nt[c] = (h0 < p.g_KH ? (p.g_KH - h0 + 1) / 2 : 0) * (w0 < p.g_KW ? (p.g_KW - w0 + 1) / 2 : 0);
+    }
+    for (int i = 1; i < 4; ++i)
+      for (int j = i; j > 0 && nt[cls[j]] > nt[cls[j - 1]]; --j) { const int t = cls[j]; cls[j] = cls[j - 1]; cls[j - 1] = t; }
+    for (int i = 0; i < 4; ++i) x.s2_ord |= cls[i] << (2 * i);
+  }
   x.pad0 = 0; x.sk_gx = (int)grid.x; x.sk_gy = (int)grid.y; x.sk_slots = 0; x.sk_part = nullptr; x.sk_cnt = nullptr; x.tick = 0;
   // split-K of a forward / data-gradient product: with the caller's tickets the last workgroup of a tile finishes it
   // (no second launch); MMVQA_SK_FINISH=1 keeps the finishing launch (A/B switch)
@@ -1692,10 +1813,10 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
     x.xcd = (b_bytes > a_bytes && x.sk_gy > 1) ? 2 : (x.sk_gx > 1 ? 1 : 0);
   }
   if (getenv("MMVQA_IGEMM_LOG"))   // one line per launch: which loader family a shape gets (diagnostics)
-    fprintf(stderr, "igemm kind %d fast %d tile %dx%dx%d ks %d M %d N %d K %d Cs %d taps %d stride %d apro %d bpro %d splitk %d fold %d tick %d prec %s\n", KIND, x.fast,
+    fprintf(stderr, "igemm kind %d fast %d tile %dx%dx%d ks %d M %d N %d K %d Cs %d taps %d stride %d apro %d bpro %d splitk %d fold %d tick %d prec %s%s\n", KIND, x.fast,
             BM, BN, BK, KS, p.M, p.N, p.K, p.g_Cs, p.g_KH * p.g_KW, p.g_stride, p.a_pro, p.b_pro, p.splitk, x.ldsc, x.tick,
-            PREC == MMVQA_PREC_F16 ? "f16" : "f32");
-  hipLaunchKernelGGL((igemm_kernel<BM, BN, BK, KIND, NCHW, KS, PREC>), grid, dim3(256 * KS), smem, stream, p, x);
+            PREC == MMVQA_PREC_F16 ? "f16" : "f32", S2C ? " compact" : "");
+  hipLaunchKernelGGL((igemm_kernel<BM, BN, BK, KIND, NCHW, KS, PREC, S2C>), grid, dim3(256 * KS), smem, stream, p, x);
   KERNEL_CHECK_RET();
   if (x.part) {
     hipLaunchKernelGGL(splitk_finish_kernel, dim3((p.N + 63) / 64, (p.M + 63) / 64), dim3(256), 0, stream, p, x.part,
@@ -1724,13 +1845,27 @@ void mmvqa_set_tuner(IgemmTuner* t) { g_tuner = t; }
 static thread_local int g_prec = MMVQA_PREC_F32;
 void mmvqa_set_igemm_precision(int prec) { g_prec = prec; }
 
+// Compact form of a stride-2 data gradient (igemm_kernel, S2C): the conditions of the uniform-tap loaders for both K-tile
+// depths, an output grid with even sides, a plain epilogue, fp32 operands.  Everything else -- and everything when
+// MMVQA_DGRAD_S2_DENSE is set (A/B switch) -- takes the dense walk over all KH*KW taps, as before.
+static bool s2c_eligible(const GemmParams& p, int kind, int nchw) {
+  static const bool dense = getenv("MMVQA_DGRAD_S2_DENSE") != nullptr;
+  if (dense || kind != KIND_DGRAD || nchw || p.g_KH <= 0 || p.g_KW <= 0 || p.g_stride != 2) return false;
+  if (p.reserved0 != MMVQA_PREC_F32 || p.epi_mode != EPI_PLAIN || p.c_atomic || p.gate || getenv("MMVQA_IGEMM_GENERAL")) return false;
+  if ((p.g_OH & 1) || (p.g_OW & 1) || p.M != (p.M / (p.g_OH * p.g_OW)) * p.g_OH * p.g_OW) return false;
+  if (((p.g_KH + 1) / 2) * ((p.g_KW + 1) / 2) > MAX_TAPS) return false;   // validity bits of one class
+  const double lim = 2147483648.0 - 16777216.0;
+  return (p.a_pro == PRO_NONE || p.a_pro == PRO_DZ) && p.b_pro == PRO_NONE && p.g_Cs % 64 == 0 && p.N % 4 == 0 &&
+         p.K == p.g_KH * p.g_KW * p.g_Cs && (double)p.M * p.a_ld * 4.0 < lim && (double)p.g_Cs * p.b_ld * 4.0 < lim;
+}
+
 static std::string tune_key(const GemmParams& p, int kind, int nchw) {
   char buf[176];
-  snprintf(buf, sizeof(buf), "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", p.reserved0, kind, nchw, p.M, p.N, p.K,
+  snprintf(buf, sizeof(buf), "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", p.reserved0, kind, nchw, p.M, p.N, p.K,
            p.g_KH * p.g_KW, p.g_stride, p.g_Cs, p.a_pro, p.b_pro, p.epi_mode, p.act | (p.dact << 4),
            (p.stat1 ? 1 : 0) | (p.stat2 ? 2 : 0) | (p.Mk ? 4 : 0) | (p.R ? 8 : 0) | (p.Cpre ? 16 : 0) |
                (p.colsum ? 32 : 0) | (p.bias ? 64 : 0) | (p.sk_ws ? 128 : 0) | (p.a_fold.stat ? 256 : 0) | (p.sk_cnt ? 512 : 0),
-           p.c_atomic, p.splitk);
+           p.c_atomic, p.splitk, s2c_eligible(p, kind, nchw) ? 1 : 0);
   return buf;
 }
 
@@ -1859,7 +1994,8 @@ int mmvqa_launch_igemm(GemmParams p, int kind, int nchw, int tile, hipStream_t s
 static int launch_one(GemmParams p, int kind, int nchw, int tile, hipStream_t stream) {
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return MMVQA_OK;
   if (p.g_KH <= 0) { p.g_KH = p.g_KW = 1; p.g_stride = 1; p.g_pad = 0; }
-  if (!nchw && p.g_KH * p.g_KW > MAX_TAPS)
+  const bool s2c = s2c_eligible(p, kind, nchw);   // (a compact class has at most MAX_TAPS taps)
+  if (!nchw && p.g_KH * p.g_KW > MAX_TAPS && !s2c)
     return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: at most %d taps in the NHWC gather", MAX_TAPS);
   // 32-bit element offsets inside the loaders
   if ((double)p.M * p.a_ld > 2.0e9 && kind != KIND_WGRAD)
@@ -1922,6 +2058,7 @@ static int launch_one(GemmParams p, int kind, int nchw, int tile, hipStream_t st
       return launch_cfg<BM_, BN_, BK_, KIND_WGRAD, false, 1, MMVQA_PREC_F16>(p, stream);                         \
     }                                                                                                              \
     if (kind == KIND_FWD) return launch_cfg<BM_, BN_, BK_, KIND_FWD, false>(p, stream);                            \
+    if (kind == KIND_DGRAD && s2c) return launch_cfg<BM_, BN_, BK_, KIND_DGRAD, false, 1, MMVQA_PREC_F32, true>(p, stream); \
     if (kind == KIND_DGRAD) return launch_cfg<BM_, BN_, BK_, KIND_DGRAD, false>(p, stream);                        \
     return launch_cfg<BM_, BN_, BK_, KIND_WGRAD, false>(p, stream);                                                \
   } while (0)
@@ -1942,6 +2079,7 @@ static int launch_one(GemmParams p, int kind, int nchw, int tile, hipStream_t st
     case 6: GO(64, 64, 32);
     case 5:
       if (kind == KIND_FWD) return launch_cfg<64, 64, 64, KIND_FWD, false, 2>(p, stream);
+      if (kind == KIND_DGRAD && s2c) return launch_cfg<64, 64, 64, KIND_DGRAD, false, 2, MMVQA_PREC_F32, true>(p, stream);
       if (kind == KIND_DGRAD) return launch_cfg<64, 64, 64, KIND_DGRAD, false, 2>(p, stream);
       return launch_cfg<64, 64, 64, KIND_WGRAD, false, 2>(p, stream);
     default: GO(64, 64, 64);
