@@ -522,18 +522,21 @@ struct RegScope {   // tags the launches of a scope with a profiler region
 };
 #define REG(r) RegScope _reg_scope(e, r)
 // an HBM-bound launch: `bytes` = the tensors it has to read and write once (algorithmic bytes, fp32)
-#define RUNB(tag, bytes, call)                             \
-  do {                                                     \
-    TRY(prof_begin(e, st, PROF_OTHER, 0, tag, (double)(bytes))); \
-    TRY(call);                                             \
-    TRY(prof_end(e, st));                                  \
+#define RUNB_ON(s, tag, bytes, call)                             \
+  do {                                                           \
+    TRY(prof_begin(e, s, PROF_OTHER, 0, tag, (double)(bytes)));  \
+    TRY(call);                                                   \
+    TRY(prof_end(e, s));                                         \
   } while (0)
-#define RUN(cls, flops, call)          \
+#define RUN_ON(s, cls, flops, call)    \
   do {                                 \
-    TRY(prof_begin(e, st, cls, flops)); \
+    TRY(prof_begin(e, s, cls, flops)); \
     TRY(call);                         \
-    TRY(prof_end(e, st));              \
+    TRY(prof_end(e, s));               \
   } while (0)
+// the common case: the launch goes to the stream the enclosing function calls `st`
+#define RUNB(tag, bytes, call) RUNB_ON(st, tag, bytes, call)
+#define RUN(cls, flops, call) RUN_ON(st, cls, flops, call)
 
 static GemmParams gp_linear_geom() {
   GemmParams g;
@@ -646,9 +649,10 @@ static int ln_bwd(mmvqa_engine* e, hipStream_t st, const float* dy, const float*
 }
 
 // --------------------------------------------------------------------------- convolution helpers
-static void conv_geom(GemmParams& g, const ConvRef& c, int H, int W, int OH, int OW) {
+// the tensor the gather reads (SH x SW pixels of Cs channels) and the grid of positions the product's rows walk
+static void conv_geom(GemmParams& g, const ConvRef& c, int SH, int SW, int Cs, int OH, int OW) {
+  g.g_SH = SH; g.g_SW = SW; g.g_Cs = Cs; g.g_OH = OH; g.g_OW = OW;
   g.g_KH = g.g_KW = c.KH; g.g_stride = c.stride; g.g_pad = c.pad;
-  (void)H; (void)W; (void)OH; (void)OW;
 }
 
 static int bn_coef_fwd(mmvqa_engine* e, hipStream_t st, BNRef& bn) {
@@ -691,31 +695,40 @@ static void set_fold_bwd(mmvqa_engine* e, mmvqa_bn_fold& f, const BNRef& bn, boo
   f.dgamma = GRD(bn.gamma); f.dbeta = GRD(bn.beta);
 }
 
-// z = conv(x) with x optionally = relu(bn_in(x_raw)); accumulates the batch statistics of z
-static int conv_fwd(mmvqa_engine* e, hipStream_t st, const ConvRef& c, const float* x, const BNRef* bn_in, int N,
-                    int H, int W, int OH, int OW, float* z, BNRef& bn_out) {
+// Input side of a convolution product: x as stored (no BatchNorm), or act(bn(x)) [* squeeze-excite gate] applied on load.
+// The ResNet path passes PRO_AFFINE_RELU, the EfficientNet path PRO_AFFINE_SILU, or PRO_SILU_GATE with the gate.
+struct ConvIn {
+  const BNRef* bn = nullptr;
+  int pro = 0;
+  const float* gate = nullptr;
+  int gate_hw(int OH, int OW) const { return bn && pro != PRO_AFFINE_RELU ? OH * OW : 0; }   // (the SiLU loaders decode the image of a row)
+};
+
+// z = conv(x) with x as `in` describes it; accumulates the batch statistics of z.  !coef: the consumer of bn_out folds its
+// coefficients itself (under folding(e) every consumer does: next convolution / block end)
+static int conv_fwd(mmvqa_engine* e, hipStream_t st, const ConvRef& c, const float* x, const ConvIn& in, int N,
+                    int H, int W, int OH, int OW, float* z, BNRef& bn_out, bool coef = true) {
   GemmParams g;
   memset(&g, 0, sizeof(g));
   g.M = N * OH * OW; g.N = c.Cout; g.K = c.KH * c.KH * c.Cin;
   g.A = x; g.a_ld = c.Cin;
-  if (bn_in) {
-    g.a_pro = PRO_AFFINE_RELU; g.a_c0 = WS(bn_in->scale); g.a_c1 = WS(bn_in->shift);
-    if (folding(e)) set_fold_fwd(e, g.a_fold, *const_cast<BNRef*>(bn_in));   // this launch is bn_in's first consumer
+  if (in.bn) {
+    g.a_pro = in.pro; g.a_c0 = WS(in.bn->scale); g.a_c1 = WS(in.bn->shift);
+    g.gate = in.gate; g.gate_hw = in.gate_hw(OH, OW);
+    if (folding(e)) set_fold_fwd(e, g.a_fold, *const_cast<BNRef*>(in.bn));   // this launch is in.bn's first consumer
   }
-  g.g_SH = H; g.g_SW = W; g.g_Cs = c.Cin; g.g_OH = OH; g.g_OW = OW;
-  conv_geom(g, c, H, W, OH, OW);
+  conv_geom(g, c, H, W, c.Cin, OH, OW);
   g.B = PRM(c.w); g.b_ld = g.K;
   g.C = z; g.c_ld = c.Cout;
   if (e->training) { g.stat1 = stat_ptr(e, bn_out.stat_f); g.stat_bwd = 0; g.stat_slots = bn_out.slots; }
   set_sk(e, st, g);
   RUN(PROF_IGEMM, 2.0 * g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_FWD, 0, 0, st));
-  if (folding(e)) return MMVQA_OK;   // bn_out's coefficients: folded by its consumer (next convolution / block end)
-  return bn_coef_fwd(e, st, bn_out);
+  return folding(e) || !coef ? MMVQA_OK : bn_coef_fwd(e, st, bn_out);
 }
 
-// dW += dz^T * x_gathered with dz = P*G + Q*z + R (BatchNorm backward of bn_out), x optionally relu(bn_in(.))
+// dW += dz^T * x_gathered with dz = P*G + Q*z + R (BatchNorm backward of bn_out), x as `in` describes it
 static int conv_wgrad(mmvqa_engine* e, hipStream_t st, const ConvRef& c, const float* G, const float* z,
-                      const BNRef& bn_out, const float* x, const BNRef* bn_in, int N, int H, int W, int OH, int OW) {
+                      const BNRef& bn_out, const float* x, const ConvIn& in, int N, int H, int W, int OH, int OW) {
   GemmParams g;
   memset(&g, 0, sizeof(g));
   g.M = c.Cout; g.N = c.KH * c.KH * c.Cin; g.K = N * OH * OW;
@@ -723,9 +736,11 @@ static int conv_wgrad(mmvqa_engine* e, hipStream_t st, const ConvRef& c, const f
   g.a_c0 = WS(bn_out.P); g.a_c1 = WS(bn_out.Q); g.a_c2 = WS(bn_out.R);
   if (folding(e)) set_fold_bwd(e, g.a_fold, bn_out, false);   // (the data gradient of the same BatchNorm publishes)
   g.B = x; g.b_ld = c.Cin;
-  if (bn_in) { g.b_pro = PRO_AFFINE_RELU; g.b_c0 = WS(bn_in->scale); g.b_c1 = WS(bn_in->shift); }
-  g.g_SH = H; g.g_SW = W; g.g_Cs = c.Cin; g.g_OH = OH; g.g_OW = OW;
-  conv_geom(g, c, H, W, OH, OW);
+  if (in.bn) {
+    g.b_pro = in.pro; g.b_c0 = WS(in.bn->scale); g.b_c1 = WS(in.bn->shift);
+    g.gate = in.gate; g.gate_hw = in.gate_hw(OH, OW);
+  }
+  conv_geom(g, c, H, W, c.Cin, OH, OW);
   g.C = GRD(c.w); g.c_ld = g.N; g.c_atomic = 1;
   if (c.KH > 1 && c.stride == 1 && OH == H && OW == W) {
     // stride-1 "same" convolution: hand the kernel the per-pixel tap-validity table (one per geometry)
@@ -747,8 +762,7 @@ static int conv_dgrad(mmvqa_engine* e, hipStream_t st, const ConvRef& c, const f
   g.A = G; g.A2 = z; g.a_ld = c.Cout; g.a_pro = PRO_DZ;
   g.a_c0 = WS(bn_out.P); g.a_c1 = WS(bn_out.Q); g.a_c2 = WS(bn_out.R);
   if (folding(e)) set_fold_bwd(e, g.a_fold, bn_out, true);
-  g.g_SH = OH; g.g_SW = OW; g.g_Cs = c.Cout; g.g_OH = H; g.g_OW = W;
-  conv_geom(g, c, H, W, OH, OW);
+  conv_geom(g, c, OH, OW, c.Cout, H, W);   // gathers dz, one row per input pixel
   g.B = PRM(c.w); g.b_ld = c.KH * c.KH * c.Cin; g.b_tapstride = c.Cin;
   g.C = dx; g.c_ld = c.Cin;
   apply_epi(e, g, o);
@@ -758,33 +772,70 @@ static int conv_dgrad(mmvqa_engine* e, hipStream_t st, const ConvRef& c, const f
   return MMVQA_OK;
 }
 
+// The stem convolution of either backbone, gathered from the NCHW image.  KIND_FWD: z0 = conv(img) and the statistics of z0.
+// KIND_WGRAD: dW += dz^T img, dz from g0 and z0 through the stem BatchNorm's backward coefficients.
+static GemmParams stem_desc(mmvqa_engine* e, int kind, const float* g0 = nullptr) {
+  const ConvRef& c = e->stem_conv;
+  const int pixels = e->B * e->SH * e->SW, taps = c.KH * c.KH * c.Cin;
+  GemmParams g;
+  memset(&g, 0, sizeof(g));
+  g.g_nchw = 1;
+  conv_geom(g, c, e->IH, e->IW, c.Cin, e->SH, e->SW);
+  if (kind == KIND_FWD) {
+    g.M = pixels; g.N = c.Cout; g.K = taps;
+    g.A = e->img;
+    g.B = PRM(c.w); g.b_ld = taps;
+    g.C = WS(e->z0); g.c_ld = c.Cout;
+    if (e->training) g.stat1 = stat_ptr(e, e->stem_bn.stat_f);
+  } else {
+    g.M = c.Cout; g.N = taps; g.K = pixels;
+    g.A = g0; g.A2 = WS(e->z0); g.a_ld = c.Cout; g.a_pro = PRO_DZ;
+    g.a_c0 = WS(e->stem_bn.P); g.a_c1 = WS(e->stem_bn.Q); g.a_c2 = WS(e->stem_bn.R);
+    g.B = e->img;
+    g.C = GRD(c.w); g.c_ld = taps; g.c_atomic = 1;
+  }
+  return g;
+}
+
 // --------------------------------------------------------------------------- taps (models/image_encoding.py:53-62,72-86)
 static int tap_act(const mmvqa_engine* e) { return e->d.use_relu ? ACT_RELU : ACT_SERF; }
 
-static int tap_fwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, const BNRef* bn_in) {
-  REG(REG_TAP);
-  const TapRef& t = e->taps[k];
+// a tap with few channels on a huge map (EfficientNet's stem tap): weights stay in registers, no tile machinery (tapthin.hip)
+// (C = 64 with BatchNorm+ReLU on load needs 256 VGPRs there and only ties the GEMM kernel: measured, round 2)
+// (fp32 operands: not in the f16 mode, whose contract rounds every tap product's operands -- the implicit GEMM)
+static bool tap_is_thin(const mmvqa_engine* e, const TapRef& t) {
   static const bool thin_off = getenv("MMVQA_NO_TAP_THIN") != nullptr;   // A/B switch
-  // (C = 64 with BatchNorm+ReLU on load needs 256 VGPRs there and only ties the GEMM kernel: measured, round 2)
-  // (fp32 operands: not in the f16 mode, whose contract rounds every tap product's operands -- the implicit GEMM below)
-  if (!thin_off && e->prec == MMVQA_PREC_F32 && t.C <= 32 && k_tap_thin_ok(t.M, e->d.hidden, t.C, t.HW)) {
-    // few channels, huge map (EfficientNet's stem tap): weights stay in registers, no tile machinery (tapthin.hip)
-    TRY(prof_begin(e, st, PROF_MATRIX, 2.0 * (double)t.M * e->d.hidden * t.C, HB_TAP_THIN_FWD, 4.0 * (double)t.M * t.C));
-    TRY(k_tap_thin_fwd(st, fmap, bn_in ? WS(bn_in->scale) : nullptr, bn_in ? WS(bn_in->shift) : nullptr,
-                                      PRM(t.w), WS(e->vis) + (size_t)k * e->B * e->d.hidden, t.M, e->d.hidden, t.C, t.HW,
-                                      tap_act(e)));
-    TRY(prof_end(e, st));
-    return MMVQA_OK;
-  }
+  return !thin_off && e->prec == MMVQA_PREC_F32 && t.C <= 32 && k_tap_thin_ok(t.M, e->d.hidden, t.C, t.HW);
+}
+
+// u = act(fmap W_tap^T), consumed by the epilogue: EPI_TAP_FWD pools it into the visual token, EPI_TAP_BWD turns it into du.
+// The caller sets the epilogue's pointers and C.
+static GemmParams tap_desc(mmvqa_engine* e, hipStream_t st, const TapRef& t, const float* fmap, const BNRef* bn_in, int epi_mode) {
   GemmParams g = gp_linear_geom();
   g.M = (int)t.M; g.N = e->d.hidden; g.K = t.C;
   g.A = fmap; g.a_ld = t.C; g.g_Cs = t.C;
   if (bn_in) { g.a_pro = PRO_AFFINE_RELU; g.a_c0 = WS(bn_in->scale); g.a_c1 = WS(bn_in->shift); }
   g.B = PRM(t.w); g.b_ld = t.C;
-  g.epi_mode = EPI_TAP_FWD; g.act = tap_act(e); g.tap_HW = t.HW;
-  g.tap_out = WS(e->vis) + (size_t)k * e->B * e->d.hidden;
-  g.C = g.tap_out; g.c_ld = g.N;  // unused by this epilogue
+  g.epi_mode = epi_mode; g.act = tap_act(e); g.tap_HW = t.HW;
+  g.c_ld = g.N;
   set_sk(e, st, g);
+  return g;
+}
+
+static int tap_fwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, const BNRef* bn_in) {
+  REG(REG_TAP);
+  const TapRef& t = e->taps[k];
+  float* vis = WS(e->vis) + (size_t)k * e->B * e->d.hidden;
+  if (tap_is_thin(e, t)) {
+    TRY(prof_begin(e, st, PROF_MATRIX, 2.0 * (double)t.M * e->d.hidden * t.C, HB_TAP_THIN_FWD, 4.0 * (double)t.M * t.C));
+    TRY(k_tap_thin_fwd(st, fmap, bn_in ? WS(bn_in->scale) : nullptr, bn_in ? WS(bn_in->shift) : nullptr,
+                                      PRM(t.w), vis, t.M, e->d.hidden, t.C, t.HW, tap_act(e)));
+    TRY(prof_end(e, st));
+    return MMVQA_OK;
+  }
+  GemmParams g = tap_desc(e, st, t, fmap, bn_in, EPI_TAP_FWD);
+  g.tap_out = vis;
+  g.C = vis;  // unused by this epilogue
   RUN(PROF_IGEMM, 2.0 * (double)g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_FWD, 0, 0, st));
   return MMVQA_OK;
 }
@@ -796,24 +847,18 @@ static int tap_bwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
   REG(REG_TAP);
   const TapRef& t = e->taps[k];
   const int Hd = e->d.hidden;
-  GemmParams g = gp_linear_geom();
-  g.M = (int)t.M; g.N = Hd; g.K = t.C;
-  g.A = fmap; g.a_ld = t.C; g.g_Cs = t.C;
-  if (bn_in) { g.a_pro = PRO_AFFINE_RELU; g.a_c0 = WS(bn_in->scale); g.a_c1 = WS(bn_in->shift); }
-  g.B = PRM(t.w); g.b_ld = t.C;
-  g.epi_mode = EPI_TAP_BWD; g.act = tap_act(e); g.tap_HW = t.HW;
-  g.tap_dv = WS(e->dvis) + (size_t)k * e->B * Hd;
-  g.C = WS(e->du); g.c_ld = Hd;
-  set_sk(e, st, g);
-  static const bool thin_off = getenv("MMVQA_NO_TAP_THIN") != nullptr;
-  if (!thin_off && e->prec == MMVQA_PREC_F32 && t.C <= 32 && k_tap_thin_ok(t.M, Hd, t.C, t.HW))   // EfficientNet stem tap: recompute in registers (tapthin.hip)
-  {
+  const float* dv = WS(e->dvis) + (size_t)k * e->B * Hd;
+  if (tap_is_thin(e, t)) {
     TRY(prof_begin(e, st, PROF_MATRIX, 2.0 * (double)t.M * Hd * t.C, HB_TAP_THIN_BWD, 4.0 * (double)t.M * (t.C + Hd)));
     TRY(k_tap_thin_bwd(st, fmap, bn_in ? WS(bn_in->scale) : nullptr, bn_in ? WS(bn_in->shift) : nullptr,
-                       PRM(t.w), g.tap_dv, WS(e->du), t.M, Hd, t.C, t.HW, tap_act(e)));
+                       PRM(t.w), dv, WS(e->du), t.M, Hd, t.C, t.HW, tap_act(e)));
     TRY(prof_end(e, st));
-  } else
+  } else {
+    GemmParams g = tap_desc(e, st, t, fmap, bn_in, EPI_TAP_BWD);
+    g.tap_dv = dv;
+    g.C = WS(e->du);
     RUN(PROF_IGEMM, 2.0 * (double)g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_FWD, 0, 0, st));
+  }
   if (!data_only) {
   // dW_tap[Hd][C] += du^T fmap
   GemmParams w = gp_linear_geom();
@@ -851,24 +896,27 @@ static int lag_us(const char* name) {
 // and, on the 14x14 / 7x7 layers, fills well under one workgroup per CU; the weight-gradient GEMMs and
 // the tap backward only feed the optimizer, so they run on a second HIP stream and fill the idle CUs.
 // Ordering is by events: fork() makes the side stream wait for everything enqueued so far on the main
-// stream, mark() returns an event for the side work enqueued so far, need() makes the main stream wait
+// stream, mark() hands out an event for the side work enqueued so far, need() makes the main stream wait
 // for such an event before it overwrites a buffer the side work reads.
 struct SideCtx {
   mmvqa_engine* e;
   hipStream_t st, sd;
   bool on;
+  // the side streams carry work with slack (weight gradients, taps, downsample branches): lowest priority, so that the
+  // dependency chain on the caller's stream is dispatched first whenever both have kernels ready.  A stream that cannot
+  // be made is no ordering loss: its work goes where it went without it.
+  static bool make_stream(hipStream_t* s, bool low_prio) {
+    int least = 0, greatest = 0;
+    const hipError_t r = low_prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest
+                             ? hipStreamCreateWithPriority(s, hipStreamNonBlocking, least)
+                             : hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+    if (r != hipSuccess) *s = nullptr;
+    return r == hipSuccess;
+  }
   SideCtx(mmvqa_engine* e_, hipStream_t st_, bool allow = true) : e(e_), st(st_) {
     on = allow && e->use_side && !e->tuner.tuning;   // (the per-launch profiler records its events on the launching stream)
-    if (on && !e->side) {
-      // the side stream carries work with slack (weight gradients, taps, downsample branches): lowest priority, so
-      // that the dependency chain on the caller's stream is dispatched first whenever both have kernels ready
-      int least = 0, greatest = 0;
-      static const bool prio_off = getenv("MMVQA_SIDE_PRIO_OFF") != nullptr;   // A/B switch
-      if (!prio_off && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-        on = hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, least) == hipSuccess;
-      else
-        on = hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking) == hipSuccess;
-    }
+    static const bool prio_off = getenv("MMVQA_SIDE_PRIO_OFF") != nullptr;   // A/B switch (this stream only)
+    if (on && !e->side) on = make_stream(&e->side, !prio_off);
     sd = on ? e->side : st;
   }
   // third stream for the tap backward: four long launch groups (2.4 ms per config-2 step) that are needed only when the
@@ -880,62 +928,49 @@ struct SideCtx {
   hipStream_t tap_stream() {
     static const bool want = getenv("MMVQA_TAP_STREAM_OFF") == nullptr;
     if (!on || !want) return sd;
-    if (!e->side2) {
-      int least = 0, greatest = 0;
-      bool ok;
-      if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest)
-        ok = hipStreamCreateWithPriority(&e->side2, hipStreamNonBlocking, least) == hipSuccess;
-      else
-        ok = hipStreamCreateWithFlags(&e->side2, hipStreamNonBlocking) == hipSuccess;
-      if (!ok) { e->side2 = nullptr; return sd; }
-    }
+    if (!e->side2 && !make_stream(&e->side2, true)) return sd;
     return e->side2;
   }
-  void fork_to(hipStream_t s) {   // s starts behind everything queued on the caller's stream so far
-    if (!on || s == st) return;
-    hipEvent_t ev = next_event();
-    if (!ev) return;
-    (void)hipEventRecord(ev, st);
-    lag(st, false);
-    (void)hipStreamWaitEvent(s, ev, 0);
-    lag(s, true);
+  // Every edge returns a status: a HIP call that fails ends the step with an error instead of dropping the ordering.
+  int fork_to(hipStream_t s) {   // s starts behind everything queued on the caller's stream so far
+    if (!on || s == st) return MMVQA_OK;
+    hipEvent_t ev;
+    TRY(next_event(&ev));
+    HIP_CHECK_RET(hipEventRecord(ev, st));
+    TRY(lag(st, false));
+    HIP_CHECK_RET(hipStreamWaitEvent(s, ev, 0));
+    return lag(s, true);
   }
-  static void lag(hipStream_t s, bool side) {   // (test-only, see lag_us)
+  int fork() { return fork_to(sd); }
+  static int lag(hipStream_t s, bool side) {   // (test-only, see lag_us)
     static const int side_us = lag_us("MMVQA_SIDE_LAG_US"), main_us = lag_us("MMVQA_MAIN_LAG_US");
     const int us = side ? side_us : main_us;
-    if (us > 0) (void)k_spin(s, us);
+    return us > 0 ? k_spin(s, us) : MMVQA_OK;
   }
-  hipEvent_t mark_on(hipStream_t s) {
-    if (!on) return nullptr;
-    hipEvent_t ev = next_event();
-    if (ev) (void)hipEventRecord(ev, s);
-    return ev;
+  int mark_on(hipStream_t s, hipEvent_t* ev) {   // *ev: the work queued on s so far (null without a side stream)
+    *ev = nullptr;
+    if (!on) return MMVQA_OK;
+    TRY(next_event(ev));
+    HIP_CHECK_RET(hipEventRecord(*ev, s));
+    return MMVQA_OK;
   }
-  hipEvent_t next_event() {
+  int mark(hipEvent_t* ev) { return mark_on(sd, ev); }
+  int next_event(hipEvent_t* ev) {
     if (e->ev_next == e->ev_pool.size()) {
-      hipEvent_t ev;
-      if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) return nullptr;
-      e->ev_pool.push_back(ev);
+      HIP_CHECK_RET(hipEventCreateWithFlags(ev, hipEventDisableTiming));
+      e->ev_pool.push_back(*ev);
     }
-    return e->ev_pool[e->ev_next++];
+    *ev = e->ev_pool[e->ev_next++];
+    return MMVQA_OK;
   }
-  void fork() {
-    if (!on) return;
-    hipEvent_t ev = next_event();
-    if (!ev) return;
-    (void)hipEventRecord(ev, st);
-    lag(st, false);
-    (void)hipStreamWaitEvent(sd, ev, 0);
-    lag(sd, true);
+  int need(hipEvent_t ev) {
+    if (on && ev) HIP_CHECK_RET(hipStreamWaitEvent(st, ev, 0));
+    return MMVQA_OK;
   }
-  hipEvent_t mark() {
-    if (!on) return nullptr;
-    hipEvent_t ev = next_event();
-    if (ev) (void)hipEventRecord(ev, sd);
-    return ev;
-  }
-  void need(hipEvent_t ev) {
-    if (on && ev) (void)hipStreamWaitEvent(st, ev, 0);
+  int join() {   // the caller's stream waits for everything queued on the side stream so far
+    hipEvent_t ev;
+    TRY(mark(&ev));
+    return need(ev);
   }
 };
 
@@ -953,31 +988,34 @@ struct SideReads {
     on = sc.on && !off && !data_only;
   }
   float* bias_grad(float* g) const { return data_only ? nullptr : g; }
-  void read(const void* p) {
-    hipEvent_t ev = sc.mark();
-    for (auto& kv : rd) if (kv.first == p) { kv.second = ev; return; }
+  int read(const void* p) {
+    hipEvent_t ev;
+    TRY(sc.mark(&ev));
+    for (auto& kv : rd) if (kv.first == p) { kv.second = ev; return MMVQA_OK; }
     rd.emplace_back(p, ev);
+    return MMVQA_OK;
   }
-  void write(const void* p) {
-    for (auto& kv : rd) if (kv.first == p && kv.second) { sc.need(kv.second); kv.second = nullptr; }
+  int write(const void* p) {
+    for (auto& kv : rd) if (kv.first == p && kv.second) { TRY(sc.need(kv.second)); kv.second = nullptr; }
+    return MMVQA_OK;
   }
-  void join() { if (on) sc.need(sc.mark()); }
+  int join() { return on ? sc.join() : MMVQA_OK; }
 };
 // dW += dy^T x (+ bias gradient) beside the chain: starts behind everything queued on the caller's stream so far
 static int lin_wgrad_side(mmvqa_engine* e, SideReads& sr, hipStream_t st, const float* dy, int dy_ld, const float* x, int x_ld, long M,
                           const LinRef& L, bool bias_from_colsum) {
   if (sr.data_only) return MMVQA_OK;
   if (!sr.on) return lin_wgrad(e, st, dy, dy_ld, x, x_ld, M, L, bias_from_colsum);
-  sr.sc.fork();
+  TRY(sr.sc.fork());
   TRY(lin_wgrad(e, sr.sc.sd, dy, dy_ld, x, x_ld, M, L, bias_from_colsum));
-  sr.read(dy);
-  return MMVQA_OK;
+  return sr.read(dy);
 }
 
-static void notify(mmvqa_engine* e, SideCtx& sc, long long lo, long long hi) {
-  if (!e->grad_cb || hi <= lo) return;
-  sc.need(sc.mark());   // weight gradients of the range may still be queued on the side stream
+static int notify(mmvqa_engine* e, SideCtx& sc, long long lo, long long hi) {
+  if (!e->grad_cb || hi <= lo) return MMVQA_OK;
+  TRY(sc.join());   // weight gradients of the range may still be queued on the side stream
   e->grad_cb(e->grad_cb_user, lo, hi);
+  return MMVQA_OK;
 }
 
 // --------------------------------------------------------------------------- ResNet forward / backward
@@ -988,15 +1026,7 @@ static int resnet_forward(mmvqa_engine* e, hipStream_t st) {
     HIP_CHECK_RET(hipMemsetAsync(stat_ptr(e, 0), 0, e->statzone_floats / 2 * sizeof(float), st));
   HIP_CHECK_RET(hipMemsetAsync(WS(e->vis), 0, (size_t)5 * B * d.hidden * sizeof(float), st));
   {  // stem 7x7/2 on the NCHW image
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.M = B * e->SH * e->SW; g.N = w; g.K = 147;
-    g.A = e->img; g.g_nchw = 1;
-    g.g_SH = e->IH; g.g_SW = e->IW; g.g_Cs = 3; g.g_OH = e->SH; g.g_OW = e->SW;
-    g.g_KH = g.g_KW = 7; g.g_stride = 2; g.g_pad = 3;
-    g.B = PRM(e->stem_conv.w); g.b_ld = 147;
-    g.C = WS(e->z0); g.c_ld = w;
-    if (e->training) g.stat1 = stat_ptr(e, e->stem_bn.stat_f);
+    const GemmParams g = stem_desc(e, KIND_FWD);
     RUN(PROF_IGEMM, 2.0 * (double)g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_FWD, 1, 0, st));
     TRY(bn_coef_fwd(e, st, e->stem_bn));
   }
@@ -1012,7 +1042,7 @@ static int resnet_forward(mmvqa_engine* e, hipStream_t st) {
   const float* pend_x = nullptr;
   const BNRef* pend_bn = nullptr;
   if (tap_first) {
-    sc.fork();
+    TRY(sc.fork());
     TRY(tap_fwd(e, sc.sd, 4, WS(e->z0), &e->stem_bn));
   } else {
     pend_tap = 4; pend_x = WS(e->z0); pend_bn = &e->stem_bn;
@@ -1026,27 +1056,27 @@ static int resnet_forward(mmvqa_engine* e, hipStream_t st) {
     BlockRef& b = e->blocks[i];
     hipEvent_t ev_ds = nullptr;
     if (b.has_ds) {
-      sc.fork();
-      TRY(conv_fwd(e, sc.sd, b.cd, x, nullptr, B, b.H, b.W, b.OH, b.OW, WS(b.zd), b.bd));
-      ev_ds = sc.mark();
+      TRY(sc.fork());
+      TRY(conv_fwd(e, sc.sd, b.cd, x, {}, B, b.H, b.W, b.OH, b.OW, WS(b.zd), b.bd));
+      TRY(sc.mark(&ev_ds));
     }
     if (pend_tap >= 0) {   // the tap on the previous layer's output (or the stem's), behind this block's downsample branch
-      if (!b.has_ds) sc.fork();
+      if (!b.has_ds) TRY(sc.fork());
       TRY(tap_fwd(e, sc.sd, pend_tap, pend_x, pend_bn));
       pend_tap = -1;
     }
-    TRY(conv_fwd(e, st, b.c1, x, nullptr, B, b.H, b.W, b.H, b.W, WS(b.z1), b.b1));
-    TRY(conv_fwd(e, st, b.c2, WS(b.z1), &b.b1, B, b.H, b.W, b.OH, b.OW, WS(b.z2), b.b2));
-    TRY(conv_fwd(e, st, b.c3, WS(b.z2), &b.b2, B, b.OH, b.OW, b.OH, b.OW, WS(b.z3), b.b3));
+    TRY(conv_fwd(e, st, b.c1, x, {}, B, b.H, b.W, b.H, b.W, WS(b.z1), b.b1));
+    TRY(conv_fwd(e, st, b.c2, WS(b.z1), {&b.b1, PRO_AFFINE_RELU}, B, b.H, b.W, b.OH, b.OW, WS(b.z2), b.b2));
+    TRY(conv_fwd(e, st, b.c3, WS(b.z2), {&b.b2, PRO_AFFINE_RELU}, B, b.OH, b.OW, b.OH, b.OW, WS(b.z3), b.b3));
     const long rows = (long)B * b.OH * b.OW;
     if (folding(e)) {
       mmvqa_bn_fold f3, fd;
       set_fold_fwd(e, f3, b.b3);
-      if (b.has_ds) { sc.need(ev_ds); set_fold_fwd(e, fd, b.bd); }
+      if (b.has_ds) { TRY(sc.need(ev_ds)); set_fold_fwd(e, fd, b.bd); }
       RUNB(HB_BN_ADD_RELU, 12.0 * rows * b.c3.Cout, k_bn_add_relu_fold(st, WS(b.z3), &f3, b.has_ds ? WS(b.zd) : x, b.has_ds ? &fd : nullptr,
                                             WS(b.out), rows, b.c3.Cout));
     } else if (b.has_ds) {
-      sc.need(ev_ds);
+      TRY(sc.need(ev_ds));
       RUNB(HB_BN_ADD_RELU, 12.0 * rows * b.c3.Cout, k_bn_add_relu(st, WS(b.z3), WS(b.b3.scale), WS(b.b3.shift), WS(b.zd), WS(b.bd.scale),
                                        WS(b.bd.shift), WS(b.out), rows, b.c3.Cout));
     } else {
@@ -1056,7 +1086,7 @@ static int resnet_forward(mmvqa_engine* e, hipStream_t st) {
     x = WS(b.out);
     if ((int)i == e->layer_end[layer]) {
       if (tap_first) {
-        sc.fork();
+        TRY(sc.fork());
         TRY(tap_fwd(e, sc.sd, 3 - layer, x, nullptr));
       } else {
         pend_tap = 3 - layer; pend_x = x; pend_bn = nullptr;
@@ -1065,10 +1095,10 @@ static int resnet_forward(mmvqa_engine* e, hipStream_t st) {
     }
   }
   if (pend_tap >= 0) {   // the tap on the last layer's output
-    sc.fork();
+    TRY(sc.fork());
     TRY(tap_fwd(e, sc.sd, pend_tap, pend_x, pend_bn));
   }
-  sc.need(sc.mark());   // join: the embedding reads the visual tokens
+  TRY(sc.join());   // join: the embedding reads the visual tokens
   return MMVQA_OK;
 }
 
@@ -1092,14 +1122,14 @@ static int resnet_backward(mmvqa_engine* e, hipStream_t st) {
   // their layer: side stream (they share the `du` scratch with the tap above, hence the fork after it)
   hipEvent_t ev_tap[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
   hipStream_t ts = sc.tap_stream();
-  sc.fork_to(ts);
+  TRY(sc.fork_to(ts));
   for (int k = 1; k <= 3; ++k) {
     const BlockRef& blk = e->blocks[e->layer_end[3 - k]];
     TRY(tap_bwd(e, ts, k, WS(blk.out), nullptr, WS(e->tapgrad[k]), EpiOpt()));
-    ev_tap[k] = sc.mark_on(ts);
+    TRY(sc.mark_on(ts, &ev_tap[k]));
   }
   TRY(tap_bwd(e, ts, 4, WS(e->z0), &e->stem_bn, WS(e->tapgrad[4]), EpiOpt()));
-  ev_tap[4] = sc.mark_on(ts);
+  TRY(sc.mark_on(ts, &ev_tap[4]));
   hipEvent_t ev_g1 = nullptr, ev_g2 = nullptr, ev_prevG = nullptr;   // side readers of g1buf / g2buf / previous G
   // gradients in [enc_lo, end) were announced by the caller; the tap weights sit in [taps[0].w, enc_lo) (fc below them).
   // Their gradients come from the tap stream, which notify() does not join: that range is announced after the stem,
@@ -1118,33 +1148,33 @@ static int resnet_backward(mmvqa_engine* e, hipStream_t st) {
     hipEvent_t evG = nullptr;   // side readers of this block's G
     // conv3 / bn3
     if (!folding(e)) TRY(bn_coef_bwd(e, st, b.b3));
-    sc.fork();
-    TRY(conv_wgrad(e, sd, b.c3, G, WS(b.z3), b.b3, WS(b.z2), &b.b2, B, b.OH, b.OW, b.OH, b.OW));
-    evG = sc.mark();
+    TRY(sc.fork());
+    TRY(conv_wgrad(e, sd, b.c3, G, WS(b.z3), b.b3, WS(b.z2), {&b.b2, PRO_AFFINE_RELU}, B, b.OH, b.OW, b.OH, b.OW));
+    TRY(sc.mark(&evG));
     {
       EpiOpt o;
       o.Mk = WS(b.z2); o.mk_ld = b.c2.Cout; o.mk_s = WS(b.b2.scale); o.mk_b = WS(b.b2.shift);
       o.st1 = &b.b2; o.Z1 = WS(b.z2);
-      sc.need(ev_g2);
+      TRY(sc.need(ev_g2));
       TRY(conv_dgrad(e, st, b.c3, G, WS(b.z3), b.b3, B, b.OH, b.OW, b.OH, b.OW, WS(e->g2buf), o));
     }
     // conv2 / bn2
     if (!folding(e)) TRY(bn_coef_bwd(e, st, b.b2));
-    sc.fork();
-    TRY(conv_wgrad(e, sd, b.c2, WS(e->g2buf), WS(b.z2), b.b2, WS(b.z1), &b.b1, B, b.H, b.W, b.OH, b.OW));
-    ev_g2 = sc.mark();
+    TRY(sc.fork());
+    TRY(conv_wgrad(e, sd, b.c2, WS(e->g2buf), WS(b.z2), b.b2, WS(b.z1), {&b.b1, PRO_AFFINE_RELU}, B, b.H, b.W, b.OH, b.OW));
+    TRY(sc.mark(&ev_g2));
     {
       EpiOpt o;
       o.Mk = WS(b.z1); o.mk_ld = b.c1.Cout; o.mk_s = WS(b.b1.scale); o.mk_b = WS(b.b1.shift);
       o.st1 = &b.b1; o.Z1 = WS(b.z1);
-      sc.need(ev_g1);
+      TRY(sc.need(ev_g1));
       TRY(conv_dgrad(e, st, b.c2, WS(e->g2buf), WS(b.z2), b.b2, B, b.H, b.W, b.OH, b.OW, WS(e->g1buf), o));
     }
     // conv1 / bn1
     if (!folding(e)) TRY(bn_coef_bwd(e, st, b.b1));
-    sc.fork();
-    TRY(conv_wgrad(e, sd, b.c1, WS(e->g1buf), WS(b.z1), b.b1, x, nullptr, B, b.H, b.W, b.H, b.W));
-    ev_g1 = sc.mark();
+    TRY(sc.fork());
+    TRY(conv_wgrad(e, sd, b.c1, WS(e->g1buf), WS(b.z1), b.b1, x, {}, B, b.H, b.W, b.H, b.W));
+    TRY(sc.mark(&ev_g1));
     // gradient wrt the block input: conv1 path + identity/downsample path (+ tap side gradient)
     EpiOpt o;
     if (i > 0) {
@@ -1155,98 +1185,45 @@ static int resnet_backward(mmvqa_engine* e, hipStream_t st) {
     }
     if (b.has_ds) {
       if (!folding(e)) TRY(bn_coef_bwd(e, st, b.bd));
-      sc.fork();
-      TRY(conv_wgrad(e, sd, b.cd, G, WS(b.zd), b.bd, x, nullptr, B, b.H, b.W, b.OH, b.OW));
-      evG = sc.mark();
+      TRY(sc.fork());
+      TRY(conv_wgrad(e, sd, b.cd, G, WS(b.zd), b.bd, x, {}, B, b.H, b.W, b.OH, b.OW));
+      TRY(sc.mark(&evG));
       EpiOpt od;
       od.R = extra; od.r_ld = b.cd.Cin;
-      sc.need(ev_extra);
+      TRY(sc.need(ev_extra));
       TRY(conv_dgrad(e, st, b.cd, G, WS(b.zd), b.bd, B, b.H, b.W, b.OH, b.OW, WS(e->dstmp), od));
       o.R = WS(e->dstmp); o.r_ld = b.c1.Cin;
     } else {
       if (extra) return mmvqa_set_error(MMVQA_ERR_STATE, "resnet_backward: tap gradient without downsample");
       o.R = G; o.r_ld = b.c1.Cin;
     }
-    sc.need(ev_prevG);   // the buffer written next was the G of the block before: its side readers must be done
+    TRY(sc.need(ev_prevG));   // the buffer written next was the G of the block before: its side readers must be done
     TRY(conv_dgrad(e, st, b.c1, WS(e->g1buf), WS(b.z1), b.b1, B, b.H, b.W, b.H, b.W, Gprev, o));
     ev_prevG = evG;
     cur ^= 1;
     // announce finished gradient ranges every ~12 blocks and at layer starts (large, few all-reduces)
     bool layer_start = false;
     for (int l = 0; l < 3; ++l) layer_start |= (i - 1 == e->layer_end[l]);
-    if (i > 0 && (layer_start || (nb - i) % 12 == 0)) { notify(e, sc, b.c1.w, hi_mark); hi_mark = b.c1.w; }
+    if (i > 0 && (layer_start || (nb - i) % 12 == 0)) { TRY(notify(e, sc, b.c1.w, hi_mark)); hi_mark = b.c1.w; }
   }
   // stem: max-pool backward + stem-tap gradient + ReLU mask + BN statistics, then the 7x7 weight gradient
   float* g0 = WS(e->gbuf[cur ^ 1]);
-  sc.need(ev_prevG);
-  sc.need(ev_tap[4]);
+  TRY(sc.need(ev_prevG));
+  TRY(sc.need(ev_tap[4]));
   RUNB(HB_MAXPOOL_BWD, 12.0 * B * e->SH * e->SW * w + 5.0 * B * e->PH * e->PW * w,
       k_maxpool_bwd(st, WS(e->gbuf[cur]), reinterpret_cast<unsigned char*>(WS(e->pool_idx)), WS(e->tapgrad[4]),
                     WS(e->z0), WS(e->stem_bn.scale), WS(e->stem_bn.shift), WS(e->stem_bn.mean),
                     WS(e->stem_bn.invstd), g0, stat_ptr(e, e->stem_bn.stat_b), B, e->SH, e->SW, w, e->PH, e->PW));
   TRY(bn_coef_bwd(e, st, e->stem_bn));
-  {
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.M = w; g.N = 147; g.K = B * e->SH * e->SW;
-    g.A = g0; g.A2 = WS(e->z0); g.a_ld = w; g.a_pro = PRO_DZ;
-    g.a_c0 = WS(e->stem_bn.P); g.a_c1 = WS(e->stem_bn.Q); g.a_c2 = WS(e->stem_bn.R);
-    g.B = e->img; g.g_nchw = 1;
-    g.g_SH = e->IH; g.g_SW = e->IW; g.g_Cs = 3; g.g_OH = e->SH; g.g_OW = e->SW;
-    g.g_KH = g.g_KW = 7; g.g_stride = 2; g.g_pad = 3;
-    g.C = GRD(e->stem_conv.w); g.c_ld = 147; g.c_atomic = 1;
-    RUN(PROF_IGEMM, 2.0 * (double)g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_WGRAD, 1, 0, st));
-  }
-  sc.need(sc.mark());   // join: everything after the backward (all-reduce, Adam) sees the side stream's gradients
-  notify(e, sc, e->taps[0].w, e->enc_lo);   // tap weights: the caller's stream is behind ev_tap[4], the last tap launch
-  notify(e, sc, e->emb_hi, hi_mark);
+  const GemmParams g = stem_desc(e, KIND_WGRAD, g0);
+  RUN(PROF_IGEMM, 2.0 * (double)g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_WGRAD, 1, 0, st));
+  TRY(sc.join());   // join: everything after the backward (all-reduce, Adam) sees the side stream's gradients
+  TRY(notify(e, sc, e->taps[0].w, e->enc_lo));   // tap weights: the caller's stream is behind ev_tap[4], the last tap launch
+  TRY(notify(e, sc, e->emb_hi, hi_mark));
   return MMVQA_OK;
 }
 
 // --------------------------------------------------------------------------- EfficientNetV2 forward / backward
-// conv (1x1 / 3x3 SAME) whose input is silu(bn_in(x_raw)) [* squeeze-excite gate]; statistics of the output
-static int eff_conv_fwd(mmvqa_engine* e, hipStream_t st, const ConvRef& c, const float* x, const BNRef* bn_in,
-                        const float* gate, int N, int H, int W, int OH, int OW, float* z, BNRef& bn_out, bool coef = true) {
-  GemmParams g;
-  memset(&g, 0, sizeof(g));
-  g.M = N * OH * OW; g.N = c.Cout; g.K = c.KH * c.KH * c.Cin;
-  g.A = x; g.a_ld = c.Cin;
-  if (bn_in) {
-    g.a_pro = gate ? PRO_SILU_GATE : PRO_AFFINE_SILU;
-    g.a_c0 = WS(bn_in->scale); g.a_c1 = WS(bn_in->shift);
-    g.gate = gate; g.gate_hw = OH * OW;
-  }
-  g.g_SH = H; g.g_SW = W; g.g_Cs = c.Cin; g.g_OH = OH; g.g_OW = OW;
-  g.g_KH = g.g_KW = c.KH; g.g_stride = c.stride; g.g_pad = c.pad;
-  g.B = PRM(c.w); g.b_ld = g.K;
-  g.C = z; g.c_ld = c.Cout;
-  if (e->training) { g.stat1 = stat_ptr(e, bn_out.stat_f); g.stat_bwd = 0; }
-  set_sk(e, st, g);
-  RUN(PROF_IGEMM, 2.0 * g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_FWD, 0, 0, st));
-  return coef ? bn_coef_fwd(e, st, bn_out) : MMVQA_OK;   // (!coef: the consumer folds the coefficients itself)
-}
-
-static int eff_conv_wgrad(mmvqa_engine* e, hipStream_t st, const ConvRef& c, const float* G, const float* z,
-                          const BNRef& bn_out, const float* x, const BNRef* bn_in, const float* gate, int N, int H,
-                          int W, int OH, int OW) {
-  GemmParams g;
-  memset(&g, 0, sizeof(g));
-  g.M = c.Cout; g.N = c.KH * c.KH * c.Cin; g.K = N * OH * OW;
-  g.A = G; g.A2 = z; g.a_ld = c.Cout; g.a_pro = PRO_DZ;
-  g.a_c0 = WS(bn_out.P); g.a_c1 = WS(bn_out.Q); g.a_c2 = WS(bn_out.R);
-  g.B = x; g.b_ld = c.Cin;
-  if (bn_in) {
-    g.b_pro = gate ? PRO_SILU_GATE : PRO_AFFINE_SILU;
-    g.b_c0 = WS(bn_in->scale); g.b_c1 = WS(bn_in->shift);
-    g.gate = gate; g.gate_hw = OH * OW;
-  }
-  g.g_SH = H; g.g_SW = W; g.g_Cs = c.Cin; g.g_OH = OH; g.g_OW = OW;
-  g.g_KH = g.g_KW = c.KH; g.g_stride = c.stride; g.g_pad = c.pad;
-  g.C = GRD(c.w); g.c_ld = g.N; g.c_atomic = 1;
-  RUN(PROF_IGEMM, 2.0 * (double)g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_WGRAD, 0, 0, st));
-  return MMVQA_OK;
-}
-
 static int effnet_forward(mmvqa_engine* e, hipStream_t st) {
   const mmvqa_model_desc& d = e->d;
   const int B = e->B;
@@ -1269,17 +1246,9 @@ static int effnet_forward(mmvqa_engine* e, hipStream_t st) {
     return MMVQA_OK;
   };
   {  // conv_stem 3x3/2 SAME on the NCHW image
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.M = (int)M0; g.N = 24; g.K = 27;
-    g.A = e->img; g.g_nchw = 1;
-    g.g_SH = e->IH; g.g_SW = e->IW; g.g_Cs = 3; g.g_OH = e->SH; g.g_OW = e->SW;
-    g.g_KH = g.g_KW = 3; g.g_stride = 2; g.g_pad = e->stem_conv.pad;
-    g.B = PRM(e->stem_conv.w); g.b_ld = 27;
-    g.C = WS(e->z0); g.c_ld = 24;
-    if (e->training) g.stat1 = stat_ptr(e, e->stem_bn.stat_f);
+    const GemmParams g = stem_desc(e, KIND_FWD);
     RUN(PROF_IGEMM, 2.0 * (double)g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_FWD, 1, 0, st));
-    TRY(block_end(e->stem_bn, WS(e->z0), ACT_SILU, nullptr, WS(e->eff_a0), M0, 24, false));
+    TRY(block_end(e->stem_bn, WS(e->z0), ACT_SILU, nullptr, WS(e->eff_a0), M0, g.N, false));
   }
   const float* x = WS(e->eff_a0);
   SideCtx sc(e, st);
@@ -1287,16 +1256,16 @@ static int effnet_forward(mmvqa_engine* e, hipStream_t st) {
     const long Mout = (long)B * b.OH * b.OW;
     const float* idn = b.skip ? x : nullptr;
     if (b.type == 0) {
-      TRY(eff_conv_fwd(e, st, b.c_a, x, nullptr, nullptr, B, b.H, b.W, b.OH, b.OW, WS(b.za), b.b_a, false));
+      TRY(conv_fwd(e, st, b.c_a, x, {}, B, b.H, b.W, b.OH, b.OW, WS(b.za), b.b_a, false));
       TRY(block_end(b.b_a, WS(b.za), ACT_SILU, idn, WS(b.out), Mout, b.cout, false));
     } else if (b.type == 1) {
-      TRY(eff_conv_fwd(e, st, b.c_a, x, nullptr, nullptr, B, b.H, b.W, b.OH, b.OW, WS(b.za), b.b_a));
-      TRY(eff_conv_fwd(e, st, b.c_p, WS(b.za), &b.b_a, nullptr, B, b.OH, b.OW, b.OH, b.OW, WS(b.zp), b.b_p, false));
+      TRY(conv_fwd(e, st, b.c_a, x, {}, B, b.H, b.W, b.OH, b.OW, WS(b.za), b.b_a));
+      TRY(conv_fwd(e, st, b.c_p, WS(b.za), {&b.b_a, PRO_AFFINE_SILU}, B, b.OH, b.OW, b.OH, b.OW, WS(b.zp), b.b_p, false));
       TRY(block_end(b.b_p, WS(b.zp), ACT_NONE, idn, WS(b.out), Mout, b.cout, false));
     } else {
       mmvqa_bn_fold fa, fdw;
       if (fold) { set_fold_fwd(e, fa, b.b_a); set_fold_fwd(e, fdw, b.b_dw); }
-      TRY(eff_conv_fwd(e, st, b.c_a, x, nullptr, nullptr, B, b.H, b.W, b.H, b.W, WS(b.za), b.b_a, !fold));
+      TRY(conv_fwd(e, st, b.c_a, x, {}, B, b.H, b.W, b.H, b.W, WS(b.za), b.b_a, !fold));
       RUNB(HB_DWCONV_FWD, 4.0 * ((double)B * b.H * b.W + (double)Mout) * b.mid, k_dwconv_fwd(st, WS(b.za), WS(b.b_a.scale), WS(b.b_a.shift), PRM(b.dw_w), WS(b.zdw),
                                       e->training ? stat_ptr(e, b.b_dw.stat_f) : nullptr, B, b.H, b.W, b.mid, b.OH, b.OW,
                                       b.stride, b.pad, fold ? &fa : nullptr));
@@ -1308,14 +1277,14 @@ static int effnet_forward(mmvqa_engine* e, hipStream_t st) {
                                       B, b.rd, b.mid));
       RUN(PROF_MATRIX, 2.0 * B * b.mid * b.rd, k_skinny_fwd(st, WS(b.r), b.rd, PRM(b.se_e.w), PRM(b.se_e.b), ACT_SIGMOID, WS(b.gpre),
                                       WS(b.gate), B, b.mid, b.rd));
-      TRY(eff_conv_fwd(e, st, b.c_p, WS(b.zdw), &b.b_dw, WS(b.gate), B, b.OH, b.OW, b.OH, b.OW, WS(b.zp), b.b_p, false));
+      TRY(conv_fwd(e, st, b.c_p, WS(b.zdw), {&b.b_dw, PRO_SILU_GATE, WS(b.gate)}, B, b.OH, b.OW, b.OH, b.OW, WS(b.zp), b.b_p, false));
       TRY(block_end(b.b_p, WS(b.zp), ACT_NONE, idn, WS(b.out), Mout, b.cout, false));
     }
     x = WS(b.out);
     // the taps feed only the encoder: side stream, beside the chain of (mostly sub-chip-sized) launches
-    if (b.feature >= 0) { sc.fork(); TRY(tap_fwd(e, sc.sd, b.feature, x, nullptr)); }
+    if (b.feature >= 0) { TRY(sc.fork()); TRY(tap_fwd(e, sc.sd, b.feature, x, nullptr)); }
   }
-  sc.need(sc.mark());   // join: the embedding reads the visual tokens
+  TRY(sc.join());   // join: the embedding reads the visual tokens
   return MMVQA_OK;
 }
 
@@ -1353,11 +1322,11 @@ static int effnet_backward(mmvqa_engine* e, hipStream_t st) {
   }
   // the other taps produce side gradients that are needed when the chain reaches their block (they share the `du`
   // scratch with the tap above, hence the fork after it)
-  scx.fork();
+  TRY(scx.fork());
   for (auto& b : e->eff)
     if (b.feature >= 0 && b.feature < 4) {
       TRY(tap_bwd(e, sd, b.feature, WS(b.out), nullptr, WS(e->tapgrad[b.feature]), EpiOpt()));
-      ev_tap[b.feature] = scx.mark();
+      TRY(scx.mark(&ev_tap[b.feature]));
     }
   // (a stream of their own for these taps, as the ResNet path has, measured neutral here: 22.74 / 22.76 / 22.84 vs 22.67 / 22.75 / 22.72 ms)
   for (int i = nb - 1; i >= 0; --i) {
@@ -1374,17 +1343,17 @@ static int effnet_backward(mmvqa_engine* e, hipStream_t st) {
     const float* dz_first = nullptr;   // gradient tensor feeding the block's first convolution
     if (b.type == 0) {
       // out = silu(bn(za)) + x
-      scx.need(ev_gA[pi]);
+      TRY(scx.need(ev_gA[pi]));
       RUNB(HB_ACT_BWD_STATS, 12.0 * Mout * b.cout, k_act_bwd_stats(st, G, nullptr, nullptr, WS(b.za), WS(b.b_a.scale), WS(b.b_a.shift),
                                          WS(b.b_a.mean), WS(b.b_a.invstd), ACT_SILU, gA, stat_ptr(e, b.b_a.stat_b), Mout,
                                          b.OH * b.OW, b.cout));
       dz_first = gA;
     } else if (b.type == 1) {
       TRY(bn_coef_bwd(e, st, b.b_p));
-      scx.fork();
-      TRY(eff_conv_wgrad(e, sd, b.c_p, G, WS(b.zp), b.b_p, WS(b.za), &b.b_a, nullptr, B, b.OH, b.OW, b.OH, b.OW));
-      ev_G[cur] = scx.mark();
-      scx.need(ev_gA[pi]);
+      TRY(scx.fork());
+      TRY(conv_wgrad(e, sd, b.c_p, G, WS(b.zp), b.b_p, WS(b.za), {&b.b_a, PRO_AFFINE_SILU}, B, b.OH, b.OW, b.OH, b.OW));
+      TRY(scx.mark(&ev_G[cur]));
+      TRY(scx.need(ev_gA[pi]));
       EpiOpt o;
       o.Mk = WS(b.za); o.mk_ld = b.mid; o.mk_s = WS(b.b_a.scale); o.mk_b = WS(b.b_a.shift); o.mk_mode = 1;
       o.st1 = &b.b_a; o.Z1 = WS(b.za);
@@ -1392,10 +1361,10 @@ static int effnet_backward(mmvqa_engine* e, hipStream_t st) {
       dz_first = gA;
     } else {
       TRY(bn_coef_bwd(e, st, b.b_p));
-      scx.fork();
-      TRY(eff_conv_wgrad(e, sd, b.c_p, G, WS(b.zp), b.b_p, WS(b.zdw), &b.b_dw, WS(b.gate), B, b.OH, b.OW, b.OH, b.OW));
-      ev_G[cur] = scx.mark();
-      scx.need(ev_gA[pi]);
+      TRY(scx.fork());
+      TRY(conv_wgrad(e, sd, b.c_p, G, WS(b.zp), b.b_p, WS(b.zdw), {&b.b_dw, PRO_SILU_GATE, WS(b.gate)}, B, b.OH, b.OW, b.OH, b.OW));
+      TRY(scx.mark(&ev_G[cur]));
+      TRY(scx.need(ev_gA[pi]));
       TRY(conv_dgrad(e, st, b.c_p, G, WS(b.zp), b.b_p, B, b.OH, b.OW, b.OH, b.OW, gA, EpiOpt()));   // t = d(a2*gate)
       // squeeze-excite backward
       float* dgate = WS(e->eff_se[0]); float* dpool = WS(e->eff_se[3]);
@@ -1405,21 +1374,18 @@ static int effnet_backward(mmvqa_engine* e, hipStream_t st) {
                                      GRD(b.se_e.w), GRD(b.se_e.b), GRD(b.se_r.w), GRD(b.se_r.b), dpool,
                                      WS(e->eff_separt), 1, B, b.mid, b.rd));
       // du2 = (t*gate + dpool/HW) * silu'(bn2(zdw)); BN2 sums
-      scx.need(ev_gB[pi]);
+      TRY(scx.need(ev_gB[pi]));
       RUNB(HB_ACT_BWD_STATS, 12.0 * Mout * b.mid, k_act_bwd_stats(st, gA, WS(b.gate), dpool, WS(b.zdw), WS(b.b_dw.scale), WS(b.b_dw.shift),
                                          WS(b.b_dw.mean), WS(b.b_dw.invstd), ACT_SILU, gB, stat_ptr(e, b.b_dw.stat_b), Mout,
                                          b.OH * b.OW, b.mid));
       mmvqa_bn_fold fdw_w, fdw_d;
       if (fold) { set_fold_bwd(e, fdw_w, b.b_dw, false); set_fold_bwd(e, fdw_d, b.b_dw, true); }
       else TRY(bn_coef_bwd(e, st, b.b_dw));
-      scx.fork();
-      {
-        hipStream_t st = sd;   // (RUNB times / launches on `st`)
-        RUNB(HB_DWCONV_BWD_WEIGHT, 4.0 * (2.0 * Mout + (double)Min) * b.mid, k_dwconv_bwd_weight(st, gB, WS(b.zdw), WS(b.b_dw.P), WS(b.b_dw.Q), WS(b.b_dw.R), WS(b.za),
-                                             WS(b.b_a.scale), WS(b.b_a.shift), GRD(b.dw_w), B, b.H, b.W, b.mid, b.OH, b.OW,
-                                             b.stride, b.pad, fold ? &fdw_w : nullptr));
-      }
-      ev_gB[pi] = scx.mark();
+      TRY(scx.fork());
+      RUNB_ON(sd, HB_DWCONV_BWD_WEIGHT, 4.0 * (2.0 * Mout + (double)Min) * b.mid, k_dwconv_bwd_weight(sd, gB, WS(b.zdw), WS(b.b_dw.P), WS(b.b_dw.Q), WS(b.b_dw.R), WS(b.za),
+                                           WS(b.b_a.scale), WS(b.b_a.shift), GRD(b.dw_w), B, b.H, b.W, b.mid, b.OH, b.OW,
+                                           b.stride, b.pad, fold ? &fdw_w : nullptr));
+      TRY(scx.mark(&ev_gB[pi]));
       RUNB(HB_DWCONV_BWD_DATA, 4.0 * (2.0 * Mout + 2.0 * (double)Min) * b.mid, k_dwconv_bwd_data(st, gB, WS(b.zdw), WS(b.b_dw.P), WS(b.b_dw.Q), WS(b.b_dw.R), PRM(b.dw_w),
                                            WS(b.za), WS(b.b_a.scale), WS(b.b_a.shift), WS(b.b_a.mean), WS(b.b_a.invstd), gA,
                                            stat_ptr(e, b.b_a.stat_b), B, b.H, b.W, b.mid, b.OH, b.OW, b.stride, b.pad, fold ? &fdw_d : nullptr));
@@ -1428,41 +1394,32 @@ static int effnet_backward(mmvqa_engine* e, hipStream_t st) {
     // first convolution of the block: weight gradient, then the gradient wrt the block input
     TRY(bn_coef_bwd(e, st, b.b_a));
     const int fo_h = b.type == 2 ? b.H : b.OH, fo_w = b.type == 2 ? b.W : b.OW;   // its output resolution
-    scx.fork();
-    TRY(eff_conv_wgrad(e, sd, b.c_a, dz_first, WS(b.za), b.b_a, x, nullptr, nullptr, B, b.H, b.W, fo_h, fo_w));
-    ev_gA[pi] = scx.mark();
+    TRY(scx.fork());
+    TRY(conv_wgrad(e, sd, b.c_a, dz_first, WS(b.za), b.b_a, x, {}, B, b.H, b.W, fo_h, fo_w));
+    TRY(scx.mark(&ev_gA[pi]));
     EpiOpt o;
     producer_opts(i - 1, o);
     if (b.skip) { o.R = G; o.r_ld = b.cin; }
-    else if (extra) { o.R = extra; o.r_ld = b.cin; scx.need(ev_tap[e->eff[i - 1].feature]); }
-    scx.need(ev_G[cur ^ 1]);   // the buffer written next was the G of the block before: its side reader must be done
+    else if (extra) { o.R = extra; o.r_ld = b.cin; TRY(scx.need(ev_tap[e->eff[i - 1].feature])); }
+    TRY(scx.need(ev_G[cur ^ 1]));   // the buffer written next was the G of the block before: its side reader must be done
     TRY(conv_dgrad(e, st, b.c_a, dz_first, WS(b.za), b.b_a, B, b.H, b.W, fo_h, fo_w, Gprev, o));
     (void)Min;
     cur ^= 1;
-    if (i > 0 && (nb - i) % 12 == 0) { notify(e, scx, b.c_a.w, hi_mark); hi_mark = b.c_a.w; }
+    if (i > 0 && (nb - i) % 12 == 0) { TRY(notify(e, scx, b.c_a.w, hi_mark)); hi_mark = b.c_a.w; }
   }
   // stem: du0 = G(a0) * silu'(bn1(z0)); BN sums; 3x3 weight gradient on the NCHW image
   float* g0 = WS(e->gbuf[cur ^ 1]);
   const long M0 = (long)B * e->SH * e->SW;
-  scx.need(ev_G[cur ^ 1]);
-  RUNB(HB_ACT_BWD_STATS, 12.0 * M0 * 24, k_act_bwd_stats(st, WS(e->gbuf[cur]), nullptr, nullptr, WS(e->z0), WS(e->stem_bn.scale),
+  const int C0 = e->stem_conv.Cout;
+  TRY(scx.need(ev_G[cur ^ 1]));
+  RUNB(HB_ACT_BWD_STATS, 12.0 * M0 * C0, k_act_bwd_stats(st, WS(e->gbuf[cur]), nullptr, nullptr, WS(e->z0), WS(e->stem_bn.scale),
                                      WS(e->stem_bn.shift), WS(e->stem_bn.mean), WS(e->stem_bn.invstd), ACT_SILU, g0,
-                                     stat_ptr(e, e->stem_bn.stat_b), M0, e->SH * e->SW, 24));
+                                     stat_ptr(e, e->stem_bn.stat_b), M0, e->SH * e->SW, C0));
   TRY(bn_coef_bwd(e, st, e->stem_bn));
-  {
-    GemmParams g;
-    memset(&g, 0, sizeof(g));
-    g.M = 24; g.N = 27; g.K = (int)M0;
-    g.A = g0; g.A2 = WS(e->z0); g.a_ld = 24; g.a_pro = PRO_DZ;
-    g.a_c0 = WS(e->stem_bn.P); g.a_c1 = WS(e->stem_bn.Q); g.a_c2 = WS(e->stem_bn.R);
-    g.B = e->img; g.g_nchw = 1;
-    g.g_SH = e->IH; g.g_SW = e->IW; g.g_Cs = 3; g.g_OH = e->SH; g.g_OW = e->SW;
-    g.g_KH = g.g_KW = 3; g.g_stride = 2; g.g_pad = e->stem_conv.pad;
-    g.C = GRD(e->stem_conv.w); g.c_ld = 27; g.c_atomic = 1;
-    RUN(PROF_IGEMM, 2.0 * (double)g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_WGRAD, 1, 0, st));
-  }
-  scx.need(scx.mark());   // join: everything after the backward (all-reduce, Adam) sees the side stream's gradients
-  notify(e, scx, e->emb_hi, hi_mark);
+  const GemmParams g = stem_desc(e, KIND_WGRAD, g0);
+  RUN(PROF_IGEMM, 2.0 * (double)g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_WGRAD, 1, 0, st));
+  TRY(scx.join());   // join: everything after the backward (all-reduce, Adam) sees the side stream's gradients
+  TRY(notify(e, scx, e->emb_hi, hi_mark));
   return MMVQA_OK;
 }
 
@@ -1475,6 +1432,45 @@ static int attn_call(mmvqa_engine* e, hipStream_t st, AttnParams& a, int head_di
   REG(REG_ATTN);
   const double fl = (bwd ? 10.0 : 4.0) * (double)e->B * a.heads * e->T * e->T * head_dim;
   RUN(PROF_ATTN, fl, mmvqa_launch_attention(a, head_dim, bwd, st));
+  return MMVQA_OK;
+}
+
+// The attention descriptors of the two encoders as the forward fills them; the backward adds only its d* pointers.
+static AttnParams bert_attn_desc(mmvqa_engine* e, const BertLayerRef& L, int layer, float p) {
+  const int H = e->d.hidden, hd = H / e->d.heads;
+  AttnParams a;
+  memset(&a, 0, sizeof(a));
+  a.q = WS(L.qkvo); a.k = a.q + H; a.v = a.q + 2 * H;
+  a.row_stride = 3 * H; a.head_stride = hd;
+  a.out = WS(L.ctx); a.out_row_stride = H; a.out_head_stride = hd;
+  a.mask = e->mask; a.mask_on_query = 0; a.probs = WS(L.probs);
+  a.B = e->B; a.T = e->T; a.heads = e->d.heads; a.sqrt_d = sqrtf((float)hd);
+  a.drop_p = p; a.seed = site_seed(e, layer, 0);
+  return a;
+}
+static AttnParams rf_attn_desc(mmvqa_engine* e, const RFLayerRef& L, int layer) {
+  const int H = e->d.hidden, es = H / 8;
+  AttnParams a;
+  memset(&a, 0, sizeof(a));
+  a.k = WS(L.kqvo); a.q = a.k + es; a.v = a.k + 2 * es;
+  a.row_stride = 8 * 3 * es; a.head_stride = 3 * es;
+  a.out = WS(L.res); a.out_row_stride = H; a.out_head_stride = es;
+  a.mask = e->mask; a.mask_on_query = 1;
+  a.prev_in = layer > 0 ? WS(e->rf[layer - 1].prev) : nullptr;
+  a.prev_out = WS(L.prev); a.probs = WS(L.probs);
+  a.B = e->B; a.T = e->T; a.heads = 8; a.sqrt_d = sqrtf((float)es);
+  return a;
+}
+
+// dropout on a gradient [B*T, hidden] on its way into a linear: *out = g itself where nothing is dropped, else a masked copy in t_b
+static int drop_grad(mmvqa_engine* e, hipStream_t st, SideReads& sr, const float* g, float p, uint32_t seed, const float** out) {
+  *out = g;
+  if (p > 0.f) {
+    const long n = (long)e->B * e->T * e->d.hidden;
+    TRY(sr.write(WS(e->t_b)));
+    RUNB(HB_DROPOUT_COPY, 8.0 * n, k_dropout_copy(st, g, WS(e->t_b), n, p, seed));
+    *out = WS(e->t_b);
+  }
   return MMVQA_OK;
 }
 
@@ -1500,14 +1496,7 @@ static int bert_forward(mmvqa_engine* e, hipStream_t st, const float* x_in, cons
                          H, d.heads, p, site_seed(e, i, 0)));
     } else {
     { REG(REG_QKV); TRY(lin_fwd(e, st, WS(L.xn1), H, M, L.qkv, WS(L.qkvo), 3 * H, ACT_NONE, nullptr, 0.f, 0, nullptr, 0)); }
-    AttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.q = WS(L.qkvo); a.k = a.q + H; a.v = a.q + 2 * H;
-    a.row_stride = 3 * H; a.head_stride = H / d.heads;
-    a.out = WS(L.ctx); a.out_row_stride = H; a.out_head_stride = H / d.heads;
-    a.mask = e->mask; a.mask_on_query = 0; a.probs = WS(L.probs);
-    a.B = e->B; a.T = e->T; a.heads = d.heads; a.sqrt_d = sqrtf((float)(H / d.heads));
-    a.drop_p = p; a.seed = site_seed(e, i, 0);
+    AttnParams a = bert_attn_desc(e, L, i, p);
     TRY(attn_call(e, st, a, H / d.heads, 0));
     }
     TRY(lin_fwd(e, st, WS(L.ctx), H, M, L.proj, WS(L.y), H, ACT_NONE, nullptr, p, site_seed(e, i, 1), x, H));
@@ -1532,50 +1521,35 @@ static int bert_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, Sid
     BertLayerRef& L = e->bert[i];
     const float* x = i == 0 ? x_in : WS(e->bert[i - 1].z);
     // FFN branch: z = y + drop(fc2(gelu(fc1(norm1(y)))))
-    const float* dzd = dz;
-    if (p > 0.f) {
-      sr.write(WS(e->t_b));
-      RUNB(HB_DROPOUT_COPY, 8.0 * M * H, k_dropout_copy(st, dz, WS(e->t_b), M * H, p, site_seed(e, i, 2)));
-      dzd = WS(e->t_b);
-    }
+    const float* dzd;
+    TRY(drop_grad(e, st, sr, dz, p, site_seed(e, i, 2), &dzd));
     TRY(lin_wgrad_side(e, sr, st, dzd, H, WS(L.h1), 4 * H, M, L.fc2, true));
-    sr.write(WS(e->t_big));
+    TRY(sr.write(WS(e->t_big)));
     TRY(lin_dgrad(e, st, dzd, H, M, L.fc2, WS(e->t_big), 4 * H, ACT_GELU, WS(L.pre1), 4 * H, sr.bias_grad(GRD(L.fc1.b)), nullptr, 0));
     TRY(lin_wgrad_side(e, sr, st, WS(e->t_big), 4 * H, WS(L.xn2), H, M, L.fc1, false));
-    sr.write(WS(e->t_c));
+    TRY(sr.write(WS(e->t_c)));
     TRY(lin_dgrad(e, st, WS(e->t_big), 4 * H, M, L.fc1, WS(e->t_c), H, 0, nullptr, 0, nullptr, nullptr, 0));
     // dy = LN'(dxn2) + dz
-    sr.write(WS(e->t_d));
+    TRY(sr.write(WS(e->t_d)));
     TRY(ln_bwd(e, st, WS(e->t_c), WS(L.y), e->norm1, WS(L.mean2), WS(L.rstd2), dz, WS(e->t_d), M, sr.data_only));
     float* dy = WS(e->t_d);
     // attention branch: y = x + drop(proj(attn(norm1(x))))
-    const float* dyd = dy;
-    if (p > 0.f) {
-      sr.write(WS(e->t_b));
-      RUNB(HB_DROPOUT_COPY, 8.0 * M * H, k_dropout_copy(st, dy, WS(e->t_b), M * H, p, site_seed(e, i, 1)));
-      dyd = WS(e->t_b);
-    }
+    const float* dyd;
+    TRY(drop_grad(e, st, sr, dy, p, site_seed(e, i, 1), &dyd));
     TRY(lin_wgrad_side(e, sr, st, dyd, H, WS(L.ctx), H, M, L.proj, true));
-    sr.write(WS(e->t_c));
+    TRY(sr.write(WS(e->t_c)));
     TRY(lin_dgrad(e, st, dyd, H, M, L.proj, WS(e->t_c), H, 0, nullptr, 0, nullptr, nullptr, 0));  // dctx
-    AttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.q = WS(L.qkvo); a.k = a.q + H; a.v = a.q + 2 * H;
-    a.row_stride = 3 * H; a.head_stride = H / d.heads;
-    a.out_row_stride = H; a.out_head_stride = H / d.heads;
-    a.mask = e->mask; a.mask_on_query = 0; a.probs = WS(L.probs);
-    a.B = e->B; a.T = e->T; a.heads = d.heads; a.sqrt_d = sqrtf((float)(H / d.heads));
-    a.drop_p = p; a.seed = site_seed(e, i, 0);
+    AttnParams a = bert_attn_desc(e, L, i, p);
     a.dout = WS(e->t_c);
     float* dqkv = WS(e->t_big);
     a.dq = dqkv; a.dk = dqkv + H; a.dv = dqkv + 2 * H;
-    sr.write(dqkv);
+    TRY(sr.write(dqkv));
     TRY(attn_call(e, st, a, H / d.heads, 1));
     { REG(REG_QKV);
       TRY(lin_wgrad_side(e, sr, st, dqkv, 3 * H, WS(L.xn1), H, M, L.qkv, true));
-      sr.write(WS(e->t_c));
+      TRY(sr.write(WS(e->t_c)));
       TRY(lin_dgrad(e, st, dqkv, 3 * H, M, L.qkv, WS(e->t_c), H, 0, nullptr, 0, nullptr, nullptr, 0)); }  // dxn1
-    sr.write(dz);
+    TRY(sr.write(dz));
     TRY(ln_bwd(e, st, WS(e->t_c), x, e->norm1, WS(L.mean1), WS(L.rstd1), dy, dz, M, sr.data_only));
   }
   return MMVQA_OK;
@@ -1592,15 +1566,7 @@ static int rf_forward(mmvqa_engine* e, hipStream_t st, const float* x_in, const 
   for (int i = 0; i < d.n_layers; ++i) {
     RFLayerRef& L = e->rf[i];
     { REG(REG_QKV); TRY(lin_fwd(e, st, x, es, M * 8, L.kqv, WS(L.kqvo), 3 * es, ACT_NONE, nullptr, 0.f, 0, nullptr, 0)); }
-    AttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.k = WS(L.kqvo); a.q = a.k + es; a.v = a.k + 2 * es;
-    a.row_stride = 8 * 3 * es; a.head_stride = 3 * es;
-    a.out = WS(L.res); a.out_row_stride = H; a.out_head_stride = es;
-    a.mask = e->mask; a.mask_on_query = 1;
-    a.prev_in = i > 0 ? WS(e->rf[i - 1].prev) : nullptr;
-    a.prev_out = WS(L.prev); a.probs = WS(L.probs);
-    a.B = e->B; a.T = e->T; a.heads = 8; a.sqrt_d = sqrtf((float)es);
+    AttnParams a = rf_attn_desc(e, L, i);
     TRY(attn_call(e, st, a, es, 0));
     // s1 = x + drop(proj(res)); x1 = ln1(s1)
     TRY(lin_fwd(e, st, WS(L.res), H, M, L.proj, WS(L.s1), H, ACT_NONE, nullptr, p, site_seed(e, i, 1), x, H));
@@ -1625,51 +1591,37 @@ static int rf_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, SideR
     RFLayerRef& L = e->rf[i];
     const float* x = i == 0 ? x_in : WS(e->rf[i - 1].x2);
     // x2 = ln2(s2), s2 = x1 + drop(ff2(serf(ff0(x1))))
-    sr.write(WS(e->t_d));
+    TRY(sr.write(WS(e->t_d)));
     TRY(ln_bwd(e, st, dx2, WS(L.s2), L.ln2, WS(L.mean2), WS(L.rstd2), nullptr, WS(e->t_d), M, sr.data_only));
     float* ds2 = WS(e->t_d);
-    const float* dff = ds2;
-    if (p > 0.f) {
-      sr.write(WS(e->t_b));
-      RUNB(HB_DROPOUT_COPY, 8.0 * M * H, k_dropout_copy(st, ds2, WS(e->t_b), M * H, p, site_seed(e, i, 2)));
-      dff = WS(e->t_b);
-    }
+    const float* dff;
+    TRY(drop_grad(e, st, sr, ds2, p, site_seed(e, i, 2), &dff));
     TRY(lin_wgrad_side(e, sr, st, dff, H, WS(L.hact), 4 * H, M, L.ff2, true));
-    sr.write(WS(e->t_big));
+    TRY(sr.write(WS(e->t_big)));
     TRY(lin_dgrad(e, st, dff, H, M, L.ff2, WS(e->t_big), 4 * H, ACT_SERF, WS(L.pre), 4 * H, sr.bias_grad(GRD(L.ff0.b)), nullptr, 0));
     TRY(lin_wgrad_side(e, sr, st, WS(e->t_big), 4 * H, WS(L.x1), H, M, L.ff0, false));
-    sr.write(WS(e->t_c));
+    TRY(sr.write(WS(e->t_c)));
     TRY(lin_dgrad(e, st, WS(e->t_big), 4 * H, M, L.ff0, WS(e->t_c), H, 0, nullptr, 0, nullptr, ds2, H));  // dx1 total
     // x1 = ln1(s1), s1 = x + drop(proj(res))
-    sr.write(WS(e->t_d));
+    TRY(sr.write(WS(e->t_d)));
     TRY(ln_bwd(e, st, WS(e->t_c), WS(L.s1), L.ln1, WS(L.mean1), WS(L.rstd1), nullptr, WS(e->t_d), M, sr.data_only));
     float* ds1 = WS(e->t_d);
-    const float* dr = ds1;
-    if (p > 0.f) {
-      sr.write(WS(e->t_b));
-      RUNB(HB_DROPOUT_COPY, 8.0 * M * H, k_dropout_copy(st, ds1, WS(e->t_b), M * H, p, site_seed(e, i, 1)));
-      dr = WS(e->t_b);
-    }
+    const float* dr;
+    TRY(drop_grad(e, st, sr, ds1, p, site_seed(e, i, 1), &dr));
     TRY(lin_wgrad_side(e, sr, st, dr, H, WS(L.res), H, M, L.proj, false));
-    sr.write(WS(e->t_c));
+    TRY(sr.write(WS(e->t_c)));
     TRY(lin_dgrad(e, st, dr, H, M, L.proj, WS(e->t_c), H, 0, nullptr, 0, nullptr, nullptr, 0));  // dres
-    AttnParams a;
-    memset(&a, 0, sizeof(a));
-    a.k = WS(L.kqvo); a.q = a.k + es; a.v = a.k + 2 * es;
-    a.row_stride = 8 * 3 * es; a.head_stride = 3 * es;
-    a.out_row_stride = H; a.out_head_stride = es;
-    a.mask = e->mask; a.mask_on_query = 1; a.probs = WS(L.probs);
-    a.B = e->B; a.T = e->T; a.heads = 8; a.sqrt_d = sqrtf((float)es);
+    AttnParams a = rf_attn_desc(e, L, i);
     a.dout = WS(e->t_c);
     float* dkqv = WS(e->t_big);
     a.dk = dkqv; a.dq = dkqv + es; a.dv = dkqv + 2 * es;
     a.dprev_in = (i < d.n_layers - 1) ? WS(e->t_dprev[(i + 1) & 1]) : nullptr;
     a.dprev_out = i > 0 ? WS(e->t_dprev[i & 1]) : nullptr;
-    sr.write(dkqv);
+    TRY(sr.write(dkqv));
     TRY(attn_call(e, st, a, es, 1));
     { REG(REG_QKV);
       TRY(lin_wgrad_side(e, sr, st, dkqv, 3 * es, x, es, M * 8, L.kqv, false));
-      sr.write(dx2);
+      TRY(sr.write(dx2));
       TRY(lin_dgrad(e, st, dkqv, 3 * es, M * 8, L.kqv, dx2, es, 0, nullptr, 0, nullptr, ds1, es)); }  // dx total
   }
   return MMVQA_OK;
@@ -1824,7 +1776,7 @@ static int fb_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, SideR
       TRY(lin_wgrad_side(e, sr, st, WS(e->fb_dmem), 1024, WS(e->fb_agg), H, Mmem, e->fb_kv, false));
     }
   }
-  sr.write(WS(e->t_a));
+  TRY(sr.write(WS(e->t_a)));
   RUN(PROF_OTHER, 0, k_fb_reorder(st, ghid, WS(e->t_a), B, T, H, 0));
   return MMVQA_OK;
 }
@@ -1869,16 +1821,15 @@ static int heads_backward(mmvqa_engine* e, hipStream_t st, const float* h, const
   const long HM = d.head_kind == 1 ? e->B : M;
   const float* hin = d.head_kind == 1 ? WS(e->hd_pool) : h;
   if (!sr.data_only) {  // classifier[2]: logits = c1 W^T + b  (beside the data gradient of the same layer: both read dlogits, nobody writes it)
-    hipStream_t st_main = st;
-    if (sr.on) sr.sc.fork();
-    hipStream_t st = sr.on ? sr.sc.sd : st_main;
+    if (sr.on) TRY(sr.sc.fork());
+    hipStream_t wst = sr.on ? sr.sc.sd : st;
     GemmParams g = gp_linear_geom();
     g.M = d.n_classes; g.N = H; g.K = (int)HM;
     g.A = dlogits; g.a_ld = dl_ld;
     g.B = WS(e->hd_c1); g.b_ld = H; g.g_Cs = H;
     g.C = GRD(e->cls2.w); g.c_ld = H; g.c_atomic = 1;
-    RUN(PROF_IGEMM, 2.0 * HM * d.n_classes * H, mmvqa_launch_igemm(g, KIND_WGRAD, 0, 0, st));
-    RUN(PROF_OTHER, 0, k_colsum(st, dlogits, dl_ld, (int)HM, d.n_classes, GRD(e->cls2.b)));
+    RUN_ON(wst, PROF_IGEMM, 2.0 * HM * d.n_classes * H, mmvqa_launch_igemm(g, KIND_WGRAD, 0, 0, wst));
+    RUN_ON(wst, PROF_OTHER, 0, k_colsum(wst, dlogits, dl_ld, (int)HM, d.n_classes, GRD(e->cls2.b)));
   }
   TRY(lin_dgrad(e, st, dlogits, dl_ld, HM, e->cls2, WS(e->t_b), H, 0, nullptr, 0, nullptr, nullptr, 0));  // dc1
   TRY(ln_bwd(e, st, WS(e->t_b), WS(e->hd_c0), e->cls_ln, WS(e->hd_mean), WS(e->hd_rstd), nullptr, WS(e->t_c), HM, sr.data_only));
@@ -1887,14 +1838,14 @@ static int heads_backward(mmvqa_engine* e, hipStream_t st, const float* h, const
   TRY(lin_wgrad_side(e, sr, st, WS(e->t_b), H, hin, H, HM, e->fc1, false));
   float* dh = WS(e->t_a);
   if (d.head_kind == 1) {
-    sr.write(WS(e->t_c));
+    TRY(sr.write(WS(e->t_c)));
     TRY(lin_dgrad(e, st, WS(e->t_b), H, HM, e->fc1, WS(e->t_c), H, 0, nullptr, 0, nullptr, nullptr, 0));
     RUN(PROF_OTHER, 0, k_meanpool_bwd(st, WS(e->t_c), e->mask, dh, e->B, e->T, H, 0));
   } else {
     TRY(lin_dgrad(e, st, WS(e->t_b), H, HM, e->fc1, dh, H, 0, nullptr, 0, nullptr, nullptr, 0));
   }
   if (d.supcon && dfeat) {
-    sr.write(WS(e->t_b)); sr.write(WS(e->t_c));
+    TRY(sr.write(WS(e->t_b))); TRY(sr.write(WS(e->t_c)));
     float* df = WS(e->t_b);  // [B][feat_dim]
     RUN(PROF_OTHER, 0, k_l2norm_bwd(st, dfeat, WS(e->sc_y), WS(e->sc_nrm), df, e->B, d.feat_dim));
     TRY(lin_wgrad(e, st, df, d.feat_dim, WS(e->sc_a), H, e->B, e->head2, true));
@@ -1933,11 +1884,23 @@ static int prepare_workspace(mmvqa_engine* e, hipStream_t st) {
   return MMVQA_OK;
 }
 
-// every implicit GEMM launched inside a forward / backward takes the engine's operand precision
-struct PrecScope {
-  explicit PrecScope(int prec) { mmvqa_set_igemm_precision(prec); }
-  ~PrecScope() { mmvqa_set_igemm_precision(MMVQA_PREC_F32); }
+// One entry point's launches: every implicit GEMM inside takes the engine's tuner and the given operand precision, and the
+// event pool is handed out from its start again
+struct StepScope {
+  StepScope(mmvqa_engine* e, int prec) { mmvqa_set_tuner(&e->tuner); mmvqa_set_igemm_precision(prec); e->ev_next = 0; }
+  ~StepScope() { mmvqa_set_igemm_precision(MMVQA_PREC_F32); mmvqa_set_tuner(nullptr); }
 };
+
+static int encoder_forward(mmvqa_engine* e, hipStream_t st, const float** h) {
+  if (e->d.encoder == 0) return bert_forward(e, st, WS(e->emb_out), h);
+  if (e->d.encoder == 2) return fb_forward(e, st, WS(e->emb_out), h);
+  return rf_forward(e, st, WS(e->emb_out), h);
+}
+static int encoder_backward(mmvqa_engine* e, hipStream_t st, SideReads& sr) {
+  if (e->d.encoder == 0) return bert_backward(e, st, WS(e->emb_out), sr);
+  if (e->d.encoder == 2) return fb_backward(e, st, WS(e->emb_out), sr);
+  return rf_backward(e, st, WS(e->emb_out), sr);
+}
 
 int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long long* ids, const long long* seg,
                    const long long* mask, float* logits, int logits_ld, float* feat, int training, uint32_t seed) {
@@ -1953,9 +1916,7 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
   e->training = training; e->seed = seed;
   if (e->prec != MMVQA_PREC_F32 && d.cnn != 0)
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward: f16 operand mode covers the ResNet encoders only");
-  struct TunerScope { TunerScope(IgemmTuner* t) { mmvqa_set_tuner(t); } ~TunerScope() { mmvqa_set_tuner(nullptr); } } ts(&e->tuner);
-  PrecScope ps(e->prec);
-  e->ev_next = 0;
+  StepScope scope(e, e->prec);
   if (d.cnn == 1) TRY(effnet_forward(e, st)); else TRY(resnet_forward(e, st));
   const float pe = training ? d.p_emb_drop : 0.f;
   e->prof_reg = REG_EMBED;
@@ -1965,9 +1926,7 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
                   d.hidden, d.num_vis, 1e-12f, pe, site_seed(e, 100, 0)));
   e->prof_reg = REG_BACKBONE;
   const float* h = nullptr;
-  if (d.encoder == 0) TRY(bert_forward(e, st, WS(e->emb_out), &h));
-  else if (d.encoder == 2) TRY(fb_forward(e, st, WS(e->emb_out), &h));
-  else TRY(rf_forward(e, st, WS(e->emb_out), &h));
+  TRY(encoder_forward(e, st, &h));
   e->enc_out_final = (size_t)(h - e->ws);
   if (d.head_kind == 2) {   // models/mmbert.py:159-161: logits = h; fc1 / classifier / head are not run
     return copy_rows(st, logits, (size_t)logits_ld, h, (size_t)d.hidden, (size_t)e->B * e->T, (size_t)d.hidden);
@@ -1980,9 +1939,7 @@ int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int d
   const mmvqa_model_desc& d = e->d;
   if (e->prec != MMVQA_PREC_F32 && d.cnn != 0)
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward: f16 operand mode covers the ResNet encoders only");
-  struct TunerScope { TunerScope(IgemmTuner* t) { mmvqa_set_tuner(t); } ~TunerScope() { mmvqa_set_tuner(nullptr); } } ts(&e->tuner);
-  PrecScope ps(e->prec);
-  e->ev_next = 0;
+  StepScope scope(e, e->prec);
   const float* h = WS(e->enc_out_final);
   SideCtx sc_enc(e, st);
   SideReads sr(sc_enc);
@@ -1995,11 +1952,9 @@ int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int d
   } else {
     TRY(heads_backward(e, st, h, dlogits, dl_ld, dfeat, sr));
   }
-  if (d.encoder == 0) TRY(bert_backward(e, st, WS(e->emb_out), sr));
-  else if (d.encoder == 2) TRY(fb_backward(e, st, WS(e->emb_out), sr));
-  else TRY(rf_backward(e, st, WS(e->emb_out), sr));
+  TRY(encoder_backward(e, st, sr));
   if (e->grad_cb) {
-    sr.join();   // the weight gradients of the range may still be queued on the side stream
+    TRY(sr.join());   // the weight gradients of the range may still be queued on the side stream
     e->grad_cb(e->grad_cb_user, e->enc_lo, e->n_params);   // heads + encoder gradients are final
   }
   const float pe = e->training ? d.p_emb_drop : 0.f;
@@ -2049,15 +2004,11 @@ int engine_backward_feature(mmvqa_engine* e, hipStream_t st, const float* dlogit
   if (!dlogits || !dA) return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward_feature: null pointer");
   if (dl_ld < d.n_classes || (dl_ld & 3))
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward_feature: dlogits_ld=%d must be >= n_classes and %%4==0", dl_ld);
-  struct TunerScope { TunerScope(IgemmTuner* t) { mmvqa_set_tuner(t); } ~TunerScope() { mmvqa_set_tuner(nullptr); } } ts(&e->tuner);
-  PrecScope ps(MMVQA_PREC_F32);
-  e->ev_next = 0;
+  StepScope scope(e, MMVQA_PREC_F32);
   SideCtx sc(e, st, false);
   SideReads sr(sc, true);
   TRY(heads_backward(e, st, WS(e->enc_out_final), dlogits, dl_ld, nullptr, sr));
-  if (d.encoder == 0) TRY(bert_backward(e, st, WS(e->emb_out), sr));
-  else if (d.encoder == 2) TRY(fb_backward(e, st, WS(e->emb_out), sr));
-  else TRY(rf_backward(e, st, WS(e->emb_out), sr));
+  TRY(encoder_backward(e, st, sr));
   size_t off = 0; int h = 0, w = 0, C = 0;
   const int k = feature_tap(e, &off, &h, &w, &C);
   // the visual tokens overwrite rows 0..4 after the embedding LayerNorm: dvis[k][b] is row k of sample b, copied
@@ -2090,12 +2041,6 @@ int engine_create(const mmvqa_model_desc* desc, mmvqa_engine** out) {
   if (d.head_kind == 2) e->d.supcon = 0;   // models/mmbert.py:159-161 returns h alone, whatever args.supcon says
   if (getenv("MMVQA_NO_SIDE_STREAM")) e->use_side = 0;   // A/B switch: everything on the caller's stream
   if (getenv("MMVQA_NO_BN_FOLD")) e->bn_fold = 0;        // A/B switch: separate BatchNorm coefficient launches everywhere
-  memset(e->prof_launch, 0, sizeof(e->prof_launch));
-  memset(e->prof_ms, 0, sizeof(e->prof_ms));
-  memset(e->prof_flops, 0, sizeof(e->prof_flops));
-  memset(e->reg_launch, 0, sizeof(e->reg_launch));
-  memset(e->reg_ms, 0, sizeof(e->reg_ms));
-  memset(e->reg_flops, 0, sizeof(e->reg_flops));
   int r = build_tables(e);
   if (r != MMVQA_OK) { delete e; return r; }
   *out = e;

@@ -191,11 +191,11 @@ struct mmvqa_engine {
   int prof_reg = REG_BACKBONE;
   int prof_tag = HB_NONE;   // tag of the launches that name none themselves (set around a block that is timed as a whole)
   struct ProfRec { hipEvent_t a, b; int cls, reg; double flops; int tag; double bytes; };
-  long long tag_launch[HB_N];
-  double tag_ms[HB_N], tag_bytes[HB_N];
+  long long tag_launch[HB_N] = {};
+  double tag_ms[HB_N] = {}, tag_bytes[HB_N] = {};
   std::vector<ProfRec> prof;
-  long long prof_launch[PROF_NCLS];
-  double prof_ms[PROF_NCLS], prof_flops[PROF_NCLS];
-  long long reg_launch[REG_N][PROF_NCLS];
-  double reg_ms[REG_N][PROF_NCLS], reg_flops[REG_N][PROF_NCLS];
+  long long prof_launch[PROF_NCLS] = {};
+  double prof_ms[PROF_NCLS] = {}, prof_flops[PROF_NCLS] = {};
+  long long reg_launch[REG_N][PROF_NCLS] = {};
+  double reg_ms[REG_N][PROF_NCLS] = {}, reg_flops[REG_N][PROF_NCLS] = {};
 };
