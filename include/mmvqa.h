@@ -248,6 +248,16 @@ typedef struct mmvqa_model_desc {
                          * (n_classes changes when classifier[2] is replaced, these do not) */
 } mmvqa_model_desc;
 
+/* Geometry of the forward-only BERT teacher (HF BertModel without the pooler; mm-vqa_amd/csrc/teacher.cpp):
+ * hidden % 64 == 0 and heads == hidden / 64 (the attention kernel has head dimension 64), hidden <= 1024, inter % 4 == 0,
+ * absolute position embeddings, erf GELU, LayerNorm eps (HF: 1e-12). */
+typedef struct mmvqa_bert_desc {
+  int layers, hidden, heads, inter, vocab, max_pos, type_vocab;
+  float eps;
+} mmvqa_bert_desc;
+
+typedef struct mmvqa_bert mmvqa_bert;
+
 /* gradient-ready notification of mmvqa_engine_set_grad_callback: grads[lo, hi) (float offsets) are final */
 typedef void (*mmvqa_grad_cb)(void* user, long long lo, long long hi);
 
@@ -260,11 +270,25 @@ size_t mmvqa_sizeof_gemm_desc(void);
 size_t mmvqa_sizeof_attn_desc(void);
 size_t mmvqa_sizeof_model_desc(void);
 size_t mmvqa_sizeof_fb_attn_desc(void);
+size_t mmvqa_sizeof_bert_desc(void);
 
 /* ---- op level (each is what one torch op of the reference's hot path lowers to) ------------ */
 /* kind: MMVQA_KIND_*; nchw: 1 only for the 7x7 stem (NCHW image source); tile: 0 auto */
 int mmvqa_igemm(const mmvqa_gemm_desc* d, int kind, int nchw, int tile, mmvqa_stream_t s);
 int mmvqa_attention(const mmvqa_attn_desc* d, int head_dim, int backward, mmvqa_stream_t s);
+/* Forward-only attention with per-sample key lengths, head dimension 64, 1 <= len[b] <= T <= 512, fp32 (bertattn.hip):
+ *   out[b][i][h][:] = softmax_j(q_i . k_j * scale ; j < len[b]) . v_j
+ * Row b*T + i of q / k / v starts at q + (b*T + i)*row_stride + h*head_stride (so the three may sit inside one fused
+ * [B*T][3*hidden] buffer), of out at out + (b*T + i)*out_row_stride + h*out_head_stride; len is int32 [B] on the device.
+ * No dropout, nothing saved, no score tensor in memory; online softmax over ceil(len[b] / 32) key tiles, bit-equal from
+ * launch to launch.  Keys j >= len[b] have probability exactly 0 and are never read; query rows i >= len[b] are computed
+ * like any other row, over the valid keys.  A len[b] outside [1, T] makes that sample's output rows NaN and reads nothing.
+ * Refused on the host with MMVQA_ERR_ARG before any HIP call: a null pointer, B, T or heads < 1, T > 512, B or heads >
+ * 65535, a row stride below 64, strides that are not multiples of 4.  q / k bases that are not 16-byte aligned are read
+ * one element at a time. */
+int mmvqa_attention_len_fwd(mmvqa_stream_t s, const float* q, const float* k, const float* v, int row_stride,
+                            int head_stride, float* out, int out_row_stride, int out_head_stride, const int* len, int B,
+                            int T, int heads, float scale);
 /* BertLayer forward, projection and attention in ONE launch (models/transformer.py:19-30: proj_q / proj_k / proj_v,
  * split heads, scores / sqrt(d) - 10000 (1 - mask), softmax, dropout, @ v, merge heads) for T <= 32 and head dimension 64
  * (hidden = 64 * heads): xn [B*T, hidden] -> qkv [B*T, 3*hidden] (q | k | v, kept for the backward pass),
@@ -599,6 +623,26 @@ int mmvqa_engine_profile_read_region(mmvqa_engine* e, int region, int cls, long 
  * 2 / 3 maxpool fwd / bwd, 4 / 5 layernorm fwd / bwd, 6 dropout_copy, 7 bn_act_add, 8 / 9 / 10 dwconv fwd / bwd_data /
  * bwd_weight, 11 se_pool, 12 se_dgate, 13 act_bwd_stats, 14 / 15 tap_thin fwd / bwd */
 int mmvqa_engine_profile_read_hbm(mmvqa_engine* e, int kernel, long long* launches, double* ms, double* bytes);
+
+/* ---- BERT teacher: a frozen, forward-only HF BertModel (no pooler) on the device ------------------------------
+ * The teacher of --task distillation (pretrain/roco_utils.py:112-132: last_hidden_state of every caption) and of the
+ * cosine SupCon mask (models/SupConLoss/supcon_utils.py:140-159: mean hidden state of caption and translation).
+ * Tensor table: HF names without the "bert." prefix, embeddings.word_embeddings.weight ...
+ * encoder.layer.{i}.output.LayerNorm.bias, shapes as torch has them, offsets in floats into ONE parameter buffer; query /
+ * key / value weights (then biases) of a layer lie back to back, so the projection is one product.
+ * plan(B, T) -> workspace bytes (0 on error; T <= min(512, max_pos)); bind borrows the parameter buffer and the
+ * workspace (both 16-byte aligned); forward enqueues on the given stream only, without synchronising or allocating:
+ * ids int64 [B][T] (0 beyond a sample's length), len int32 [B] as in mmvqa_attention_len_fwd, token type 0, out
+ * [B*T][hidden] fp32 = last_hidden_state including the padded rows.  ids outside the vocabulary are not checked. */
+int mmvqa_bert_create(const mmvqa_bert_desc* desc, mmvqa_bert** out);
+void mmvqa_bert_destroy(mmvqa_bert* e);
+int mmvqa_bert_num_tensors(const mmvqa_bert* e);
+long long mmvqa_bert_param_floats(const mmvqa_bert* e);
+int mmvqa_bert_tensor_info(const mmvqa_bert* e, int i, char* name, int name_cap, int* ndim, long long shape[2],
+                           long long* offset);
+size_t mmvqa_bert_plan(mmvqa_bert* e, int B, int T);
+int mmvqa_bert_bind(mmvqa_bert* e, const float* params, void* workspace, size_t workspace_bytes);
+int mmvqa_bert_forward(mmvqa_bert* e, mmvqa_stream_t s, const long long* ids, const int* len, int B, int T, float* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Device input pipeline: the torchvision/PIL transforms of pretrain/roco_train.py:98-112 and

@@ -121,6 +121,14 @@ class ModelDesc(C.Structure):
     ]
 
 
+class BertDesc(C.Structure):
+    """mirror of mmvqa_bert_desc"""
+    _fields_ = [
+        ("layers", C.c_int), ("hidden", C.c_int), ("heads", C.c_int), ("inter", C.c_int), ("vocab", C.c_int),
+        ("max_pos", C.c_int), ("type_vocab", C.c_int), ("eps", C.c_float),
+    ]
+
+
 # every symbol include/mmvqa.h declares, with (restype, argtypes); checked by tests/test_abi.py
 _i, _f, _d, _l, _ll, _u32, _sz = C.c_int, C.c_float, C.c_double, C.c_long, C.c_longlong, C.c_uint32, C.c_size_t
 _P = c_ptr
@@ -131,8 +139,10 @@ SIGNATURES = {
     "mmvqa_sizeof_attn_desc": (_sz, []),
     "mmvqa_sizeof_model_desc": (_sz, []),
     "mmvqa_sizeof_fb_attn_desc": (_sz, []),
+    "mmvqa_sizeof_bert_desc": (_sz, []),
     "mmvqa_igemm": (_i, [C.POINTER(GemmDesc), _i, _i, _i, _P]),
     "mmvqa_attention": (_i, [C.POINTER(AttnDesc), _i, _i, _P]),
+    "mmvqa_attention_len_fwd": (_i, [_P, _P, _P, _P, _i, _i, _P, _i, _i, _P, _i, _i, _i, _f]),
     "mmvqa_qkv_attention_fwd": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _i, _i, _i, _i, _f, _u32]),
     "mmvqa_fb_attention": (_i, [C.POINTER(FbAttnDesc), _i, _P]),
     "mmvqa_fb_aggregate_fwd": (_i, [_P, _P, _ll, _i, _P, _P, _l, _i]),
@@ -199,6 +209,14 @@ SIGNATURES = {
     "mmvqa_aug_train_fused_fits": (_i, [_i]),
     "mmvqa_low_priority_stream": (_i, [C.POINTER(_P), C.POINTER(_i)]),
     "mmvqa_stream_priority": (_i, [_P, C.POINTER(_i)]),
+    "mmvqa_bert_create": (_i, [C.POINTER(BertDesc), C.POINTER(_P)]),
+    "mmvqa_bert_destroy": (None, [_P]),
+    "mmvqa_bert_num_tensors": (_i, [_P]),
+    "mmvqa_bert_param_floats": (_ll, [_P]),
+    "mmvqa_bert_tensor_info": (_i, [_P, _i, C.c_char_p, _i, C.POINTER(_i), C.POINTER(_ll * 2), C.POINTER(_ll)]),
+    "mmvqa_bert_plan": (_sz, [_P, _i, _i]),
+    "mmvqa_bert_bind": (_i, [_P, _P, _P, _sz]),
+    "mmvqa_bert_forward": (_i, [_P, _P, _P, _P, _i, _i, _P]),
     "mmvqa_engine_create": (_i, [C.POINTER(ModelDesc), C.POINTER(_P)]),
     "mmvqa_engine_destroy": (None, [_P]),
     "mmvqa_engine_num_tensors": (_i, [_P]),
@@ -246,7 +264,7 @@ def lib():
         fn = getattr(L, name)  # AttributeError if the library does not export a declared symbol
         fn.restype = res
         fn.argtypes = args
-    for nm, st in (("gemm", GemmDesc), ("attn", AttnDesc), ("model", ModelDesc), ("fb_attn", FbAttnDesc), ("resample_job", ResampleJob),
+    for nm, st in (("gemm", GemmDesc), ("attn", AttnDesc), ("model", ModelDesc), ("fb_attn", FbAttnDesc), ("bert", BertDesc), ("resample_job", ResampleJob),
                    ("aug_record", AugRecord)):
         if nm in ("resample_job", "aug_record"):
             got = getattr(L, f"mmvqa_sizeof_{nm}")()

@@ -67,6 +67,12 @@ int mmvqa_qkv_attention_fwd(mmvqa_stream_t s, const float* xn, const float* W, c
   if (B <= 0 || drop_p < 0.f || drop_p >= 1.f) return mmvqa_set_error(MMVQA_ERR_ARG, "qkv_attention_fwd: B=%d drop_p=%g", B, (double)drop_p);
   return k_qkv_attn_fwd(ST(s), xn, W, bias, mask, qkv, probs, ctx, B, T, hidden, heads, drop_p, seed);
 }
+int mmvqa_attention_len_fwd(mmvqa_stream_t s, const float* q, const float* k, const float* v, int row_stride,
+                            int head_stride, float* out, int out_row_stride, int out_head_stride, const int* len, int B,
+                            int T, int heads, float scale) {
+  return k_attention_len_fwd(ST(s), q, k, v, row_stride, head_stride, out, out_row_stride, out_head_stride, len, B, T, heads,
+                             scale);
+}
 int mmvqa_fb_attention(const mmvqa_fb_attn_desc* d, int backward, mmvqa_stream_t s) {
   if (!d) return mmvqa_set_error(MMVQA_ERR_ARG, "fb_attention: null descriptor");
   return k_fb_attention(ST(s), *d, backward ? 1 : 0);

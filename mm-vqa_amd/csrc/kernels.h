@@ -87,6 +87,10 @@ int k_soft_ce(hipStream_t st, const float* logits, int ld, const long long* targ
 int k_distill_mse(hipStream_t st, const float* h, int ld, const void* table, int table_f16, long long table_rows,
                   const long long* start, const int* count, int first, int B, int T, int H, float* row_sq, float* loss,
                   float* dh, int dld, float gscale);
+// bertattn.hip: forward-only attention with per-sample key lengths (the BERT teacher), head dimension 64, T <= 512
+int k_attention_len_fwd(hipStream_t st, const float* q, const float* k, const float* v, int row_stride, int head_stride,
+                        float* out, int out_row_stride, int out_head_stride, const int* len, int B, int T, int heads,
+                        float scale);
 // fbattn.hip: the Feedback Transformer's window attention, hidden aggregation, GEGLU and row permutation
 int k_fb_attention(hipStream_t st, const mmvqa_fb_attn_desc& p, int bwd);
 int k_fb_aggregate_fwd(hipStream_t st, const float* hid, long long hstride, int nh, const float* lw, float* agg, long rows, int H);

@@ -285,6 +285,30 @@ class CaptionEmbeddings:
         return out
 
 
+def distill_layout(piece_ids, T, num_vis, cls_id, sep_id):
+    """the teacher's piece ids of one caption (without CLS / SEP) in encode_text's distillation layout
+    (roco_utils.py:162-199) -> (ids, seg, mask) lists of T"""
+    part2 = [int(i) for i in piece_ids[:max(T - (num_vis + 3), 0)]]                   # :174-175
+    tokens = [cls_id] + [0] * num_vis + [sep_id] + part2 + [sep_id]                   # :178
+    seg = [0] * (num_vis + 2) + [1] * (len(part2) + 1)                                # :181
+    n_pad = T - len(tokens)
+    if n_pad < 0:
+        raise ValueError(f"TeacherStates: T={T} has no room for [CLS], {num_vis} visual tokens and two [SEP]")
+    return tokens + [0] * n_pad, seg + [0] * n_pad, [1] * len(tokens) + [0] * n_pad
+
+
+def teacher_row(tokenizer, text_, max_token_length):
+    """what the teacher is fed for one text, as HF's tokenizer(text, truncation=True) with model_max_length =
+    --max_token_length gives it: [CLS] + the first max_token_length - 2 pieces + [SEP] -> int64 [1 + max_token_length]:
+    the length (CLS and SEP included), then the ids, zero-padded.  The shape is the same for every text."""
+    L = int(max_token_length)
+    if L < 2:
+        raise ValueError(f"max_token_length = {L} has no room for [CLS] and [SEP]")
+    pieces = tokenizer.convert_tokens_to_ids(tokenizer.tokenize(text_))[:L - 2]
+    ids = [tokenizer.cls_token_id] + pieces + [tokenizer.sep_token_id]
+    return torch.tensor([len(ids)] + ids + [0] * (L - len(ids)), dtype=torch.int64)
+
+
 class TeacherStates:
     """The teacher's per-token states of every caption of a ROCO table, for the distillation task
     (pretrain/roco_utils.py:112-132: last_hidden_state[1:len-1] of the teacher on the caption, CLS and SEP dropped).
@@ -393,13 +417,7 @@ class TeacherStates:
     def encode(self, row, T, num_vis=5):
         """one caption in encode_text's distillation layout (roco_utils.py:162-199) -> (ids, seg, mask) lists of T"""
         lo, hi = int(self.offsets[row]), int(self.offsets[row + 1])
-        part2 = self.ids[lo:hi][:max(T - (num_vis + 3), 0)].tolist()                     # :174-175
-        tokens = [self.cls_id] + [0] * num_vis + [self.sep_id] + part2 + [self.sep_id]   # :178
-        seg = [0] * (num_vis + 2) + [1] * (len(part2) + 1)                                # :181
-        n_pad = T - len(tokens)
-        if n_pad < 0:
-            raise ValueError(f"TeacherStates: T={T} has no room for [CLS], {num_vis} visual tokens and two [SEP]")
-        return tokens + [0] * n_pad, seg + [0] * n_pad, [1] * len(tokens) + [0] * n_pad
+        return distill_layout(self.ids[lo:hi], T, num_vis, self.cls_id, self.sep_id)
 
     def batch(self, rows, T, num_vis=5):
         """-> host (ids, seg, mask) int64 [B, T], start int64 [B] (first row of each caption in `states`) and count
@@ -494,6 +512,45 @@ class DistillDataset(torch.utils.data.Dataset):
         return decode(self.rows[idx][0]), ids[0], seg[0], mask[0], torch.tensor([int(start[0]), int(count[0])]), idx
 
 
+def collate_teacher(items):
+    """collate for OnlineDistillDataset: the same dict plus teacher_T, the batch's longest teacher input (a host
+    scalar: the step sizes the teacher's launches from it without reading the device)"""
+    out = collate(items)
+    out["teacher_T"] = out["target"][:, 0].max()
+    return out
+
+
+class OnlineDistillDataset(torch.utils.data.Dataset):
+    """item (epoch, index) -> (uint8 [H, W, 3], ids, seg, mask, teacher row) of the distillation task with the teacher
+    run on the device (teacher.BertTeacher): the caption is tokenised here, in the worker, with the TEACHER's WordPiece;
+    the student's ids / seg / mask are encode_text's distillation layout of those same piece ids
+    (roco_utils.py:174-186; the student is fed the tokens the teacher saw), and in the target's place travels
+    teacher_row's int64 [1 + max_token_length]: length, then [CLS] pieces [SEP].  A batch's fifth tensor is int64
+    [B, 1 + max_token_length] -- one shape for every batch -- and the host batch carries teacher_T, its longest length."""
+
+    collate = staticmethod(collate_teacher)
+
+    def __init__(self, rows, tokenizer, num_vis=5, max_position_embeddings=75, max_token_length=512):
+        self.rows, self.tok = list(rows), tokenizer
+        self.num_vis, self.T, self.L = num_vis, max_position_embeddings, int(max_token_length)
+        if self.L < 2:
+            raise ValueError(f"OnlineDistillDataset: max_token_length = {self.L} has no room for [CLS] and [SEP]")
+
+    def __len__(self):
+        return len(self.rows)
+
+    def encode(self, idx):
+        """(ids, seg, mask int64 [T], teacher row int64 [1 + L])"""
+        row = teacher_row(self.tok, self.rows[idx][1], self.L)
+        n = int(row[0])
+        ids, seg, mask = distill_layout(row[2:n].tolist(), self.T, self.num_vis, self.tok.cls_token_id, self.tok.sep_token_id)
+        return tuple(torch.tensor(v, dtype=torch.int64) for v in (ids, seg, mask)) + (row,)
+
+    def __getitem__(self, key):
+        _epoch, idx = key
+        return (decode(self.rows[idx][0]),) + self.encode(idx) + (idx,)
+
+
 def category_ids(rows):
     """{category name: id}: id i is the i-th distinct category of `rows` (data.vqa_tables rows, row[3]) in row order,
     the numbering of vqamed2019/utils.py:228-229 over the train table"""
@@ -573,6 +630,17 @@ def collate_supcon_cols(items):
     return out
 
 
+def collate_supcon_teacher(items):
+    """collate_supcon for items that end with the teacher rows of caption and drawn translation
+    (RocoSupConDataset(teacher_tokenizer=...)): the same dict plus teacher int64 [2n, 1 + L] (captions, then translations:
+    the order of `list(doc1) + list(doc2)`, supcon_utils.py:141) and teacher_T, the longest of the 2n lengths"""
+    out = collate_supcon([it[:8] for it in items])
+    t = torch.stack([it[8] for it in items])                        # [n, 2, 1 + L]
+    out["teacher"] = torch.cat([t[:, 0], t[:, 1]]).contiguous()
+    out["teacher_T"] = out["teacher"][:, 0].max()
+    return out
+
+
 class RocoSupConDataset(torch.utils.data.Dataset):
     """item (epoch, index) -> (uint8 [H, W, 3], ids, aug_ids, seg, mask, tgt, aug_tgt, index) as supcon_utils.py:218-232
     returns it (the image untransformed: both views are made on the device).  One rng, sample_rng(seed, epoch,
@@ -580,17 +648,25 @@ class RocoSupConDataset(torch.utils.data.Dataset):
     column (get_translation), then the translation's masking.  The translation's seg / mask are not kept: the
     reference uses the caption's for both halves (process_tensors).
     report_aug_col=True (the Jaccard mask needs to know which translation was drawn): the item gains a ninth element,
-    the drawn column as 1..3 (= CSV column - 2, the WordSets column), and batches are packed by collate_supcon_cols."""
+    the drawn column as 1..3 (= CSV column - 2, the WordSets column), and batches are packed by collate_supcon_cols.
+    teacher_tokenizer (the cosine mask of the BERT teacher; not with report_aug_col): the ninth element is int64
+    [2, 1 + max_token_length], teacher_row of the caption and of the translation drawn, tokenised with the teacher's
+    WordPiece; batches are packed by collate_supcon_teacher."""
 
     collate = staticmethod(collate_supcon)     # HostLoader packs its batches with it
 
     def __init__(self, rows, tokenizer, keywords, num_vis=5, max_position_embeddings=75, mlm_prob=0.15, seed=0,
-                 report_aug_col=False):
+                 report_aug_col=False, teacher_tokenizer=None, max_token_length=512):
         self.rows, self.tok, self.kw = list(rows), tokenizer, frozenset(keywords)
         self.num_vis, self.T, self.mlm_prob, self.seed = num_vis, max_position_embeddings, mlm_prob, seed
         self.report_aug_col = bool(report_aug_col)
+        self.teacher_tok, self.L = teacher_tokenizer, int(max_token_length)
+        if self.report_aug_col and teacher_tokenizer is not None:
+            raise ValueError("RocoSupConDataset: report_aug_col and teacher_tokenizer are the ninth element of different masks' items")
         if self.report_aug_col:
             self.collate = collate_supcon_cols
+        if teacher_tokenizer is not None:
+            self.collate = collate_supcon_teacher
 
     def __len__(self):
         return len(self.rows)
@@ -613,6 +689,10 @@ class RocoSupConDataset(torch.utils.data.Dataset):
         epoch, idx = key
         enc, col = self.encode_col(epoch, idx)
         item = (decode(self.rows[idx][0]),) + enc + (idx,)
+        if self.teacher_tok is not None:
+            _path, caption, trans = self.rows[idx]
+            return item + (torch.stack([teacher_row(self.teacher_tok, caption, self.L),
+                                        teacher_row(self.teacher_tok, trans[col - 1], self.L)]),)
         return item + (col,) if self.report_aug_col else item
 
 
@@ -742,10 +822,16 @@ class DeviceFeeder:
     category=True (VQA with label smoothing by category; the host batches must carry `category`, i.e. come from a
     VqaDataset(categories=...)): the batch is a 6-tuple whose last element is category, an int64 device tensor [B] of
     category ids.  It lives in the slot and is copied on the feeder's stream like the rest: same ready event, same reuse
-    rule.  The log entry gains `category`.  Not together with pairs."""
+    rule.  The log entry gains `category`.  Not together with pairs.
+
+    teacher=True (SupCon with the BERT teacher's cosine mask; the host batches must carry `teacher`, i.e. come from a
+    RocoSupConDataset(teacher_tokenizer=...)): the batch is a 6-tuple whose last element is the int64 device tensor
+    [2n, 1 + L] of teacher rows (data.teacher_row: length, ids), in the slot like the rest.  Not together with pairs or
+    category.  Whenever a host batch carries `teacher_T` (this one, or OnlineDistillDataset's, whose teacher rows are the
+    batch's fifth tensor) the log entry gains `teacher_T`, the batch's longest teacher input as a host integer."""
 
     def __init__(self, host: HostLoader, device, train=True, depth=2, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5),
-                 fused=True, pairs=False, category=False):
+                 fused=True, pairs=False, category=False, teacher=False):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("DeviceFeeder runs on the GPU only (no CPU fallback)")
@@ -753,9 +839,9 @@ class DeviceFeeder:
             raise ValueError("depth must be >= 1")
         self.host, self.dev, self.depth, self.fused = host, device, int(depth), fused
         self.views = getattr(host, "views", 1)
-        self.pairs, self.category = bool(pairs), bool(category)
-        if self.pairs and self.category:
-            raise ValueError("DeviceFeeder: pairs and category are the sixth element of different loops' batches")
+        self.pairs, self.category, self.teacher = bool(pairs), bool(category), bool(teacher)
+        if self.pairs + self.category + self.teacher > 1:
+            raise ValueError("DeviceFeeder: pairs, category and teacher are the sixth element of different loops' batches")
         aug = host.aug or {}
         self.aug = DeviceAugment(size=host.size, train=train, mean=mean, std=std, device=device, **aug)
         self.stream, self.priority = low_priority_stream(device)
@@ -841,6 +927,16 @@ class DeviceFeeder:
                 cat = buf["category"][:B]
                 cat.copy_(batch["category"], non_blocking=True)
                 out.append(cat)
+            if self.teacher:
+                if "teacher" not in batch:
+                    raise ValueError("DeviceFeeder(teacher=True): the host batches carry no `teacher` "
+                                     "(RocoSupConDataset(teacher_tokenizer=...) reports it)")
+                tr = batch["teacher"]
+                if buf.get("teacher") is None or buf["teacher"].shape[0] < tr.shape[0] or buf["teacher"].shape[1] != tr.shape[1]:
+                    buf["teacher"] = torch.empty(max(tr.shape[0], NI), tr.shape[1], dtype=torch.int64, device=self.dev)
+                td = buf["teacher"][:tr.shape[0]]
+                td.copy_(tr, non_blocking=True)
+                out.append(td)
             slot.ready = torch.cuda.Event()
             slot.ready.record(s)
         entry = dict(meta, index=batch["index"].tolist(), params=params, shapes=batch["shapes"].tolist())
@@ -848,6 +944,8 @@ class DeviceFeeder:
             entry["aug_col"] = batch["aug_col"].tolist()
         if self.category:
             entry["category"] = batch["category"].tolist()
+        if "teacher_T" in batch:
+            entry["teacher_T"] = int(batch["teacher_T"])
         self._queue.append((slot, tuple(out), entry))
         return True
 

@@ -251,6 +251,19 @@ def global_supcon_views(feat, n):
     return torch.cat([parts[:, 0].reshape(w * n, 1, -1), parts[:, 1].reshape(w * n, 1, -1)], 1).contiguous()
 
 
+def global_supcon_means(means, n):
+    """means fp32 [2n, D] of this rank (captions 0..n-1, the translations drawn n..2n-1) -> [2 world n, D] over the
+    global batch: all captions rank-major, then all translations rank-major -- the sample order global_supcon_views gives
+    the features.  One all-gather on the current stream (no host synchronisation, no gradient: the mask has none)."""
+    if world() == 1:
+        return means
+    mine = means.contiguous()
+    out = [torch.empty_like(mine) for _ in range(world())]
+    dist.all_gather(out, mine)
+    g = torch.stack(out).view(world(), 2, n, -1)
+    return torch.cat([g[:, 0].reshape(world() * n, -1), g[:, 1].reshape(world() * n, -1)]).contiguous()
+
+
 def global_supcon_pairs(rows, cols):
     """(rows, cols) int32 [n] of this rank -- the (table row, translation column) of each sample -> the same for the
     global batch, [world*n] each, rank-major: the sample order global_supcon_views gives the features.  One all-gather

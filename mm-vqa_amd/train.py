@@ -4,7 +4,8 @@ which never ship to the GPU box (SURVEY.md 8(b) "Callers the build must supply")
   mlm      pretrain/roco_train.py:155-197 + pretrain/roco_utils.py:207-372 (train_one_epoch / validate)
   supcon   pretrain/roco_supcon_train.py:137,168-202 + models/SupConLoss/supcon_utils.py:253-379
   distill  the same two files with --task distillation: the headless model against the teacher's per-token states
-           (roco_utils.py:112-132, 230-238), which are read from --teacher_states instead of running the teacher
+           (roco_utils.py:112-132, 230-238), read from --teacher_states, or computed per batch by the BERT teacher on the
+           device (--teacher_weights, teacher.BertTeacher)
   vqa      vqamed2019/train.py:125-296 + vqamed2019/utils.py:625-767
   eval     vqamed2019/eval.py:99-180 + vqamed2019/utils.py:769-843 (test-set run: metrics, <model>_preds.csv, <model>_res.txt)
   gradcam  vqamed2019/grad_cam2.py:99-188 over the test split (one overlay PNG per row + gradcam_index.csv)
@@ -25,6 +26,8 @@ torch.distributed (RCCL).
     python -m mmvqa_amd.train distill --run_name r --emb_vocab 28996 --epochs 2 --steps_per_epoch 20
     python -m mmvqa_amd.train distill --data_dir roco-dataset/data --emb_vocab 28996 --bert_weights clinicalbert.pt \\
                                       --teacher_states roco_train_teacher.npz --val_teacher_states roco_val_teacher.npz
+    python -m mmvqa_amd.train distill --data_dir roco-dataset/data --emb_vocab 28996 --bert_weights clinicalbert.pt \\
+                                      --teacher_weights clinicalbert.pt --teacher_vocab_file clinicalbert_vocab.txt
     python -m mmvqa_amd.train vqa    --run_name r --loss ASLSingleLabel --batch_size 64
     python -m mmvqa_amd.train vqa    --run_name r --smoothing 0.1 --batch_size 64
     python -m mmvqa_amd.train eval   --model_dir save/MLM/r.pt --num_classes 1552 --batch_size 16
@@ -33,6 +36,8 @@ torch.distributed (RCCL).
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --supcon_mask jaccard
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --supcon_mask embeddings \\
                                      --caption_embeddings roco_train_embeddings.npz
+    python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --supcon_mask cosine \\
+                                     --teacher_weights clinicalbert.pt --teacher_vocab_file clinicalbert_vocab.txt
 """
 from __future__ import annotations
 
@@ -49,7 +54,8 @@ from . import (CategorySmoothing, FusedAdam, LabelSmoothing, Model, asl_loss, ch
                evaluate, jaccard_mask, mlm_loss, split_feat, supcon_loss, synth)
 from . import data as D
 from .amp import GradScaler
-from .ddp import GradReducer, comm_info, global_supcon_pairs, global_supcon_views, sync_replicas
+from .ddp import GradReducer, comm_info, global_supcon_means, global_supcon_pairs, global_supcon_views, sync_replicas
+from .teacher import BertTeacher, cosine_mask_from_means
 
 
 def common_args(p):
@@ -100,18 +106,33 @@ def common_args(p):
     p.add_argument("--feeder_depth", type=int, default=2, help="device batches prepared ahead of the step")
 
 
-def feeder(args, ctx, dataset, train, aug=None, batch_size=None, views=1, pairs=False, category=False):
+def feeder(args, ctx, dataset, train, aug=None, batch_size=None, views=1, pairs=False, category=False, teacher=False):
     """DeviceFeeder over one split (shuffled and augmented for training, file order and val transforms otherwise)"""
     host = D.HostLoader(dataset, batch_size or args.batch_size, shuffle=train, seed=args.seed, rank=ctx.rank,
                         world=ctx.world, num_workers=args.num_workers, aug=aug if train else None, size=args.image_size,
                         views=views)
-    return D.DeviceFeeder(host, ctx.dev, train=train, depth=args.feeder_depth, pairs=pairs, category=category)
+    return D.DeviceFeeder(host, ctx.dev, train=train, depth=args.feeder_depth, pairs=pairs, category=category, teacher=teacher)
 
 
 def tokenizer(args):
     if not args.vocab_file:
         raise ValueError("--data_dir needs --vocab_file (a local WordPiece vocab.txt; nothing is downloaded)")
     return D.text.BertWordPiece(args.vocab_file)
+
+
+def teacher_tokenizer(args):
+    """the teacher's own WordPiece (--teacher_vocab_file), cased unless --teacher_lower_case: the clinical checkpoints
+    the reference names are cased"""
+    return D.text.BertWordPiece(args.teacher_vocab_file, do_lower_case=bool(args.teacher_lower_case))
+
+
+def load_teacher(args, ctx):
+    """the frozen BERT teacher of --teacher_weights on the step's device"""
+    teacher = BertTeacher.from_state_dict(args.teacher_weights).to(ctx.dev)
+    if args.max_token_length > min(512, teacher.max_pos):
+        raise ValueError(f"--max_token_length {args.max_token_length} is more than the teacher takes "
+                         f"(min(512, its {teacher.max_pos} positions))")
+    return teacher
 
 
 def roco_feeders(args, ctx):
@@ -127,21 +148,26 @@ def roco_supcon_feeders(args, ctx, pairs):
     drop_last=False), the plain ROCO validation split at the full --batch_size.  With --supcon_mask jaccard or
     embeddings the train batches carry each sample's (row, translation column) and the third value is what the mask is
     built from, on the device: the table's word sets, or its caption embeddings read from --caption_embeddings and
-    normalised (else None)."""
+    normalised (else None).  With --supcon_mask cosine the workers tokenise caption and drawn translation with the
+    teacher's WordPiece, the train batches carry those ids and the third value is the BERT teacher."""
     tok, kw = tokenizer(args), D.load_keywords(args.data_dir)
     table = D.roco_supcon_table(args.data_dir)
     kind = getattr(args, "supcon_mask", "none")
-    masked = kind != "none"
-    words = None
+    masked = kind in ("jaccard", "embeddings")
+    words, ttok = None, None
     if kind == "jaccard":
         words = D.WordSets.from_table(table).to(ctx.dev)
     elif kind == "embeddings":
         words = D.CaptionEmbeddings.from_file(args.caption_embeddings, table).to(ctx.dev)
+    elif kind == "cosine":
+        words, ttok = load_teacher(args, ctx), teacher_tokenizer(args)
     tr = D.RocoSupConDataset(table, tok, kw, args.num_vis, args.max_position_embeddings, args.mlm_prob, args.seed,
-                             report_aug_col=masked)
+                             report_aug_col=masked, teacher_tokenizer=ttok,
+                             max_token_length=getattr(args, "max_token_length", 512))
     va = D.RocoDataset(D.roco_table(args.data_dir, "validation"), tok, kw, args.num_vis, args.max_position_embeddings,
                        args.mlm_prob, args.seed)
-    return feeder(args, ctx, tr, True, D.ROCO_AUG, batch_size=pairs, views=2, pairs=masked), feeder(args, ctx, va, False), words
+    return (feeder(args, ctx, tr, True, D.ROCO_AUG, batch_size=pairs, views=2, pairs=masked, teacher=ttok is not None),
+            feeder(args, ctx, va, False), words)
 
 
 def epoch_batches(fd, epoch, synthetic):
@@ -314,7 +340,26 @@ def process_tensors(img, caption_token, aug_tokens, segment_ids, attention_mask,
             cat(attention_mask, attention_mask), cat(target, aug_targets))
 
 
-def supcon_step(model, opt, red, world, batch, words=None):
+def teacher_inputs(rows, teacher_T=None):
+    """teacher rows int64 [B, 1 + L] (data.teacher_row) -> (ids int64 [B, Tp] contiguous, lens int32 [B], Tp): the
+    batch cut at its longest length Tp -- teacher_T, the feeder's host-side figure (log entry `teacher_T`), or, without
+    one, a read of the device"""
+    Tp = int(rows[:, 0].max()) if teacher_T is None else int(teacher_T)
+    return rows[:, 1:1 + Tp].contiguous(), rows[:, 0].to(torch.int32), Tp
+
+
+def teacher_cosine_mask(teacher, rows, teacher_T=None):
+    """SimilarityCalculator.bert_embedd (supcon_utils.py:140-159) on the device from the 2n teacher rows (captions, then
+    the translations drawn): the mean hidden state over ALL positions of the batch padded to its longest text, unit
+    rows (eps 1e-8), caption i against translation j, unit diagonal -> [n, n].  Under data parallelism each rank pads
+    to its own longest text (the reference's per-process semantics), the mean vectors are gathered in the sample order
+    of global_supcon_views and every rank builds the global [world n, world n] mask."""
+    ids, lens, _ = teacher_inputs(rows, teacher_T)
+    means = global_supcon_means(teacher.sentence_means(ids, lens), rows.shape[0] // 2)
+    return cosine_mask_from_means(means)
+
+
+def supcon_step(model, opt, red, world, batch, words=None, teacher_T=None):
     """models/SupConLoss/supcon_utils.py:270-294: MLM loss over both views + SupCon(split_feat(feat)) (called without
     a mask => SimCLR, :287); under DDP the views of all ranks are gathered first.  Returns (loss, pred, stats).
     With `words` (--supcon_mask jaccard: the table's WordSets on the device) the batch is the feeder's 6-tuple and the
@@ -323,7 +368,9 @@ def supcon_step(model, opt, red, world, batch, words=None):
     (--supcon_mask embeddings) the mask is the cosine of the two texts' sentence embeddings instead, as
     sentence_trans(caption, aug) gives it (:162-168).  Under DDP the (row, column) pairs of all
     ranks are gathered and every rank builds the global mask, in the sample order of the gathered features; gather and
-    mask launch go on the step's stream."""
+    mask launch go on the step's stream.  When `words` is a teacher.BertTeacher (--supcon_mask cosine) the batch's sixth
+    element holds the teacher's ids of caption and translation and the mask is teacher_cosine_mask's; teacher_T is the
+    feeder's host-side longest length."""
     img, ids, seg, mask, tgt = batch[:5]
     opt.zero_grad()
     logits, feat = model(img, ids, seg, mask)
@@ -332,6 +379,8 @@ def supcon_step(model, opt, red, world, batch, words=None):
     feat = global_supcon_views(feat, bsz)          # = split_feat(feat, bsz) on one rank; global negatives under DDP
     if words is None:
         loss = loss_mlm + supcon_loss(feat)        # 2N*world rows: the tiled kernel has no size cap
+    elif isinstance(words, BertTeacher):
+        loss = loss_mlm + supcon_loss(feat, mask=teacher_cosine_mask(words, batch[5], teacher_T))
     else:
         rows, cols = global_supcon_pairs(*batch[5])
         build_mask = embedding_mask if isinstance(words, D.CaptionEmbeddings) else jaccard_mask
@@ -443,6 +492,47 @@ def distill_feeders(args, ctx):
     return out[0][0], out[1][0], out[0][1], out[1][1]
 
 
+def online_distill_feeders(args, ctx):
+    """(train feeder, validation feeder, teacher, teacher): the same tree with the teacher run per batch.  The workers
+    tokenise with the teacher's WordPiece (data.OnlineDistillDataset); the fifth tensor of a batch is int64
+    [B, 1 + --max_token_length] = (length, the teacher's input ids)."""
+    teacher, tok = load_teacher(args, ctx), teacher_tokenizer(args)
+    if teacher.hidden != args.hidden_size:
+        raise ValueError(f"{args.teacher_weights}: the teacher's states are {teacher.hidden} wide, --hidden_size is {args.hidden_size}")
+    if len(tok.vocab) > args.emb_vocab:
+        raise ValueError(f"{args.teacher_vocab_file}: {len(tok.vocab)} tokens, the student's embedding table has "
+                         f"{args.emb_vocab} rows (--emb_vocab must be the teacher's vocabulary size)")
+    if len(tok.vocab) > teacher.vocab:
+        raise ValueError(f"{args.teacher_vocab_file}: {len(tok.vocab)} tokens, the teacher's embedding table has {teacher.vocab} rows")
+    fds = []
+    for split in ("train", "validation"):
+        ds = D.OnlineDistillDataset(D.roco_table(args.data_dir, split), tok, args.num_vis, args.max_position_embeddings,
+                                    args.max_token_length)
+        fds.append(feeder(args, ctx, ds, split == "train", D.ROCO_AUG))
+    return fds[0], fds[1], teacher, teacher
+
+
+def online_distill_targets(teacher, rows, teacher_T=None):
+    """run the teacher on a batch's rows [B, 1 + L] -> (table [B * Tp, hidden], start int64 [B], count int32 [B]) in the
+    form distill_loss reads: sample b's caption states are rows b * Tp + 1 .. of the teacher's output (CLS dropped),
+    len - 2 of them (SEP dropped too) -- roco_utils.py:127-129"""
+    ids, lens, Tp = teacher_inputs(rows, teacher_T)
+    states = teacher(ids, lens)
+    B = ids.shape[0]
+    start = torch.arange(B, dtype=torch.int64, device=ids.device) * Tp + 1
+    return states.view(B * Tp, teacher.hidden), start, lens - 2
+
+
+def synthetic_teacher_rows(batch, num_vis=5):
+    """teacher rows [B, 1 + L] for a synthetic distillation batch (synth.distill_batch): the teacher sees [CLS], the
+    caption ids the student was given and [SEP], all of which the student's row already holds; L = T - num_vis - 1"""
+    ids, count = batch[1], batch[5]
+    first = num_vis + 2
+    n_max = ids.shape[1] - first - 1
+    lens = count.to(torch.int64).clamp(max=n_max) + 2
+    return torch.cat([lens[:, None], ids[:, :1], ids[:, first:]], 1).contiguous()
+
+
 def distill_targets(batch):
     """(start int64 [B], count int32 [B]) of a batch: its last two tensors, or the columns of a fed batch's [B, 2]"""
     if len(batch) == 6:
@@ -450,14 +540,20 @@ def distill_targets(batch):
     return batch[4][:, 0].contiguous(), batch[4][:, 1].to(torch.int32)
 
 
-def distill_step(model, opt, red, world, batch, teacher, scaler=None, num_vis=5):
+def distill_step(model, opt, red, world, batch, teacher, scaler=None, num_vis=5, teacher_T=None):
     """pretrain/roco_utils.py:214-247 with task 'distillation' (:230-231, 237-238): zero_grad -> forward (the model
     returns h) -> nn.MSELoss against the teacher's states -> backward -> (gradient all-reduce) -> Adam.  batch =
     (img, ids, seg, mask, start, count) or (img, ids, seg, mask, [B, 2] of both); teacher = the resident table of
     states.  Returns the loss.  With a scaler (--mixed_precision, :224-245): autocast forward, the loss in fp32, scaled
-    backward, scaler.step after the all-reduce, scaler.update."""
+    backward, scaler.step after the all-reduce, scaler.update.
+    When `teacher` is a teacher.BertTeacher the batch's fifth tensor holds the teacher's input rows [B, 1 + L]
+    (data.OnlineDistillDataset) and the table is the teacher's output for this batch, computed first
+    (online_distill_targets); teacher_T is the feeder's host-side longest length.  The loss call is the same."""
     img, ids, seg, mask = batch[:4]
-    start, count = distill_targets(batch)
+    if isinstance(teacher, BertTeacher):
+        teacher, start, count = online_distill_targets(teacher, batch[4], teacher_T)
+    else:
+        start, count = distill_targets(batch)
     opt.zero_grad()
     with torch.autocast("cuda", dtype=torch.float16) if scaler is not None else contextlib.nullcontext():
         loss = distill_loss(model(img, ids, seg, mask), teacher, start, count, num_vis)
@@ -470,8 +566,12 @@ def distill_batches(args, ctx, fd, teacher, epoch, seeds):
     seed, each with a table of its own"""
     if fd is not None:
         return ((b, teacher) for b in epoch_batches(fd, epoch, None))
-    return (synth.distill_batch(args.batch_size, args.max_position_embeddings, args.image_size, args.emb_vocab,
-                                args.hidden_size, seed=sd, device=ctx.dev, num_vis=args.num_vis) for sd in seeds)
+    syn = (synth.distill_batch(args.batch_size, args.max_position_embeddings, args.image_size, args.emb_vocab,
+                               args.hidden_size, seed=sd, device=ctx.dev, num_vis=args.num_vis) for sd in seeds)
+    if teacher is None:
+        return syn
+    # --teacher_layers: the seeded random teacher over the synthetic caption ids instead of the batch's random table
+    return ((b[:4] + (synthetic_teacher_rows(b, args.num_vis),), teacher) for b, _table in syn)
 
 
 def run_distill(args):
@@ -479,12 +579,24 @@ def run_distill(args):
     args.dataset, args.task = "roco", "distillation"
     model, opt, sched, red = build(args, ctx)
     scaler = GradScaler() if args.mixed_precision else None
-    tr_fd, va_fd, tr_teacher, va_teacher = distill_feeders(args, ctx) if args.data_dir else (None,) * 4
+    tr_fd, va_fd, tr_teacher, va_teacher = (None,) * 4
+    if args.data_dir:
+        tr_fd, va_fd, tr_teacher, va_teacher = (online_distill_feeders if args.teacher_weights else distill_feeders)(args, ctx)
+    elif args.teacher_layers:
+        tr_teacher = va_teacher = BertTeacher.random(args.teacher_layers, args.hidden_size, 4 * args.hidden_size, args.emb_vocab,
+                                                     max(args.max_position_embeddings, 2), seed=args.seed).to(ctx.dev)
+
+    def longest(fd, pair):       # the fed batch's longest teacher input, from the feeder's host-side log; synthetic: all of L
+        return fd.log[-1]["teacher_T"] if fd is not None else pair[0][4].shape[1] - 1
 
     def step(pair):                                               # per-step host sync, as roco_utils.py:267
-        return float(distill_step(model, opt, red, ctx.world, *pair, scaler=scaler, num_vis=args.num_vis).detach()), 0, 0
+        tT = longest(tr_fd, pair) if isinstance(pair[1], BertTeacher) else None
+        return float(distill_step(model, opt, red, ctx.world, *pair, scaler=scaler, num_vis=args.num_vis, teacher_T=tT).detach()), 0, 0
 
     def val_value(pair):    # roco_utils.py:292-372 with task 'distillation': no accuracy (total_acc is None)
+        if isinstance(pair[1], BertTeacher):
+            table, start, count = online_distill_targets(pair[1], pair[0][4], longest(va_fd, pair))
+            return float(distill_loss(model(*pair[0][:4]), table, start, count, args.num_vis)), 0, 0
         return float(distill_loss(model(*pair[0][:4]), pair[1], *distill_targets(pair[0]), args.num_vis)), 0, 0
 
     return pretrain(
@@ -511,7 +623,8 @@ def run_supcon(args):
             yield process_tensors((a[0], b[0]), a[1], b[1], a[2], a[3], a[4], b[4])
 
     def step(batch):
-        loss, _, stats = supcon_step(model, opt, red, ctx.world, batch, words=words)
+        tT = tr_fd.log[-1]["teacher_T"] if isinstance(words, BertTeacher) else None   # the feeder's host-side longest length
+        loss, _, stats = supcon_step(model, opt, red, ctx.world, batch, words=words, teacher_T=tT)
         # fed: the MLM accuracy train_one_epoch returns (supcon_utils.py:296-318); synthetic: `stats` stays on the device
         return (float(loss.detach()), *(stats.tolist()[1:] if tr_fd is not None else (0, 0)))
 
@@ -731,15 +844,31 @@ def parse_args(argv=None):
                                 "CLS / SEP), states [total, hidden_size]; no teacher is run here")
             p.add_argument("--val_teacher_states", type=str, default=None, metavar="FILE",
                            help="the same for the validation split")
+            p.add_argument("--teacher_layers", type=int, default=0, metavar="N",
+                           help="without --data_dir: run a seeded random BERT teacher of N layers (--hidden_size wide) over "
+                                "the synthetic caption ids instead of a random table of states")
+        if mode in ("distill", "supcon"):
+            p.add_argument("--teacher_weights", type=str, default=None, metavar="FILE",
+                           help="with --data_dir: a local HF BertModel state dict (.bin / .pt / .safetensors), e.g. "
+                                "ClinicalBERT: the teacher is run on the GPU per batch (distill: instead of "
+                                "--teacher_states; supcon: --supcon_mask cosine)")
+            p.add_argument("--teacher_vocab_file", type=str, default=None, metavar="FILE",
+                           help="the teacher's WordPiece vocab.txt (with --teacher_weights)")
+            p.add_argument("--max_token_length", type=int, default=512,
+                           help="the teacher's inputs are truncated to this many tokens, [CLS] and [SEP] included")
+            p.add_argument("--teacher_lower_case", action="store_true", default=False,
+                           help="lower-case and strip accents before the teacher's WordPiece (default: cased)")
         if mode == "supcon":
             p.add_argument("--con_task", type=str, default="supcon", choices=["simclr", "supcon"])
             p.add_argument("--similarity", type=str, default="sentence_transformers")      # accepted, not read
-            p.add_argument("--supcon_mask", type=str, default="none", choices=["none", "jaccard", "embeddings"],
+            p.add_argument("--supcon_mask", type=str, default="none", choices=["none", "jaccard", "embeddings", "cosine"],
                            help="positives of the SupCon loss: none = the other view only (SimCLR, what the reference's "
                                 "loop runs); jaccard = caption / back-translation word overlap weights every pair "
                                 "(SimilarityCalculator.jaccard); embeddings = the cosine of the two texts' sentence "
-                                "embeddings (SimilarityCalculator.sentence_trans) from --caption_embeddings.  Either "
-                                "mask is built on the GPU per batch and needs --data_dir")
+                                "embeddings (SimilarityCalculator.sentence_trans) from --caption_embeddings; cosine = "
+                                "the cosine of the BERT teacher's mean hidden states of the two texts "
+                                "(SimilarityCalculator.bert_embedd), the teacher of --teacher_weights run per batch.  "
+                                "Every mask is built on the GPU per batch and needs --data_dir")
             p.add_argument("--caption_embeddings", type=str, default=None, metavar="FILE",
                            help="with --supcon_mask embeddings: an .npz of precomputed sentence embeddings, names [R] "
                                 "(image file names) and emb [R, 4, D] (caption and the three translations); no "
@@ -781,9 +910,29 @@ def parse_args(argv=None):
             p.error("--supcon_mask embeddings needs --caption_embeddings FILE (the precomputed sentence embeddings)")
         if args.supcon_mask != "embeddings" and args.caption_embeddings:
             p.error(f"--caption_embeddings is read by --supcon_mask embeddings only, not by --supcon_mask {args.supcon_mask}")
+        tgiven = [o for o in ("teacher_weights", "teacher_vocab_file") if getattr(args, o)]
+        if args.supcon_mask == "cosine" and len(tgiven) != 2:
+            # (worded as argparse words a refused value: without the teacher's files `cosine` is not a choice)
+            p.error("argument --supcon_mask: invalid choice: 'cosine' needs --teacher_weights FILE and --teacher_vocab_file FILE "
+                    "(the BERT teacher and its WordPiece)")
+        if args.supcon_mask != "cosine" and tgiven:
+            p.error(f"--{tgiven[0]} is read by --supcon_mask cosine only, not by --supcon_mask {args.supcon_mask}")
+    if mode in ("distill", "supcon") and args.max_token_length < 2:
+        p.error(f"--max_token_length {args.max_token_length} has no room for [CLS] and [SEP]")
     if mode == "distill":
         given = [o for o in ("teacher_states", "val_teacher_states") if getattr(args, o)]
-        if args.data_dir and len(given) != 2:
+        tgiven = [o for o in ("teacher_weights", "teacher_vocab_file") if getattr(args, o)]
+        if tgiven and given:
+            p.error(f"--{tgiven[0]} (the teacher run on the GPU) and --{given[0]} (its precomputed states) exclude each other")
+        if tgiven and not args.data_dir:
+            p.error(f"--{tgiven[0]} is read with --data_dir only (synthetic batches: --teacher_layers N runs a random teacher)")
+        if tgiven and len(tgiven) != 2:
+            p.error("distill with the teacher on the GPU needs both --teacher_weights FILE and --teacher_vocab_file FILE")
+        if args.teacher_layers and args.data_dir:
+            p.error("--teacher_layers is for synthetic batches: with --data_dir the teacher comes from --teacher_weights")
+        if args.teacher_layers < 0 or (args.teacher_layers and args.hidden_size % 64):
+            p.error("--teacher_layers needs N >= 1 and a --hidden_size that is a multiple of 64")
+        if args.data_dir and not tgiven and len(given) != 2:
             p.error("distill with --data_dir needs --teacher_states FILE and --val_teacher_states FILE (the teacher's "
                     "precomputed states of both splits)")
         if not args.data_dir and given:
