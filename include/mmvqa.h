@@ -407,6 +407,23 @@ int mmvqa_jaccard_mask(mmvqa_stream_t s, const int* offsets, const int* ids, con
 int mmvqa_normalize_rows(mmvqa_stream_t s, float* x, long long rows, int D, float eps);
 int mmvqa_cosine_mask(mmvqa_stream_t s, const float* table, const int* rowsA, const int* colsA, const int* rowsB,
                       const int* colsB, float* mask, int n, int D, int table_rows);
+/* BERTScore F1 mask of a batch (SimilarityCalculator.bert_score, supcon_utils.py:170-182, restated: the library's
+ * greedy_cos_idf with idf = False, one candidate against one reference, bertscore.hip).  xa / xb are the token states of
+ * the n candidates / n references, [n][T][D] fp32 each, rows ALREADY of unit length (mmvqa_normalize_rows); text i has
+ * lenA[i] / lenB[i] positions, [CLS] first and [SEP] last.  For i != j, with S[t][u] = <xa[i][t], xb[j][u]> over ALL
+ * positions t < lenA[i], u < lenB[j] (the specials are match targets):
+ *   P = mean over t in 1..lenA[i]-2 of max_u S[t][u]      R = mean over u in 1..lenB[j]-2 of max_t S[t][u]
+ *   F = 2 P R / (P + R), a NaN F becomes 0; an empty text (len == 2) gives P = R = F = 0;
+ *   mask[i][j] = baseline == 0 ? F : (F - baseline) / (1 - baseline)
+ * prec / rec ([n][n] each, both or neither) receive P and R, not rescaled.  mask[i][i] = prec[i][i] = rec[i][i] = 1, not
+ * computed.  The score tiles are 32 x 32 products on v_mfma_f32_32x32x2_f32 (a k-ordered fmaf chain); no [n][n][T][T]
+ * tensor exists anywhere; no atomics: the same inputs give the same bits on every launch.  Positions >= len are never
+ * read, 32-row tiles wholly past a length are not visited.  A len outside [2, T] gives NaN in the row (lenA) or column
+ * (lenB) it touches and reads nothing for it; the diagonal stays 1.  Refused on the host with MMVQA_ERR_ARG before any HIP
+ * call: a null xa / xb / lenA / lenB / mask, exactly one of prec / rec null, n < 1, n > 65535, T < 2, T > 512, D < 64,
+ * D % 64 != 0, D > 1024, xa or xb not 16-byte aligned.  All pointers are device pointers. */
+int mmvqa_bertscore_mask(mmvqa_stream_t s, const float* xa, const int* lenA, const float* xb, const int* lenB, float* mask,
+                         float* prec, float* rec, int n, int T, int D, float baseline);
 /* Soft-target cross entropy over logits [rows][C] (leading dimension ld), forward AND backward in one launch, plus a
  * one-workgroup launch for the mean; the criteria vqamed2019/train.py:164-174 selects with --smoothing:
  *   mode 0 (MMVQA_SOFT_CE_HARD)      nn.CrossEntropyLoss, the eval branch (vqamed2019/utils.py:1261-1264)
@@ -633,7 +650,10 @@ int mmvqa_engine_profile_read_hbm(mmvqa_engine* e, int kernel, long long* launch
  * plan(B, T) -> workspace bytes (0 on error; T <= min(512, max_pos)); bind borrows the parameter buffer and the
  * workspace (both 16-byte aligned); forward enqueues on the given stream only, without synchronising or allocating:
  * ids int64 [B][T] (0 beyond a sample's length), len int32 [B] as in mmvqa_attention_len_fwd, token type 0, out
- * [B*T][hidden] fp32 = last_hidden_state including the padded rows.  ids outside the vocabulary are not checked. */
+ * [B*T][hidden] fp32 = last_hidden_state including the padded rows.  ids outside the vocabulary are not checked.
+ * forward_layers is forward stopped after the first n_layers layers (1..layers): the last LayerNorm of layer n_layers
+ * writes out, which is HF's hidden_states[n_layers] (what BERTScore reads, supcon_utils.py:103-108); n_layers == layers is
+ * forward itself, bit for bit; an n_layers outside 1..layers is refused with MMVQA_ERR_ARG before any HIP call. */
 int mmvqa_bert_create(const mmvqa_bert_desc* desc, mmvqa_bert** out);
 void mmvqa_bert_destroy(mmvqa_bert* e);
 int mmvqa_bert_num_tensors(const mmvqa_bert* e);
@@ -643,6 +663,8 @@ int mmvqa_bert_tensor_info(const mmvqa_bert* e, int i, char* name, int name_cap,
 size_t mmvqa_bert_plan(mmvqa_bert* e, int B, int T);
 int mmvqa_bert_bind(mmvqa_bert* e, const float* params, void* workspace, size_t workspace_bytes);
 int mmvqa_bert_forward(mmvqa_bert* e, mmvqa_stream_t s, const long long* ids, const int* len, int B, int T, float* out);
+int mmvqa_bert_forward_layers(mmvqa_bert* e, mmvqa_stream_t s, const long long* ids, const int* len, int B, int T,
+                              int n_layers, float* out);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Device input pipeline: the torchvision/PIL transforms of pretrain/roco_train.py:98-112 and

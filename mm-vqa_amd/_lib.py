@@ -171,6 +171,7 @@ SIGNATURES = {
     "mmvqa_jaccard_mask": (_i, [_P] * 8 + [_i, _i]),
     "mmvqa_normalize_rows": (_i, [_P, _P, _ll, _i, _f]),
     "mmvqa_cosine_mask": (_i, [_P] * 7 + [_i, _i, _i]),
+    "mmvqa_bertscore_mask": (_i, [_P] * 8 + [_i, _i, _i, _f]),
     "mmvqa_soft_ce_loss": (_i, [_P, _P, _i, _P, _P, _P, _i, _i, _i, _d, _P, _P, _P, _i, _i, _i, _f]),
     "mmvqa_distill_mse": (_i, [_P, _P, _i, _P, _i, _ll, _P, _P, _i, _i, _i, _i, _P, _P, _P, _i, _f]),
     "mmvqa_dwconv_fwd": (_i, [_P, _P, _P, _P, _P, _P, _P] + [_i] * 8),
@@ -217,6 +218,7 @@ SIGNATURES = {
     "mmvqa_bert_plan": (_sz, [_P, _i, _i]),
     "mmvqa_bert_bind": (_i, [_P, _P, _P, _sz]),
     "mmvqa_bert_forward": (_i, [_P, _P, _P, _P, _i, _i, _P]),
+    "mmvqa_bert_forward_layers": (_i, [_P, _P, _P, _P, _i, _i, _i, _P]),
     "mmvqa_engine_create": (_i, [C.POINTER(ModelDesc), C.POINTER(_P)]),
     "mmvqa_engine_destroy": (None, [_P]),
     "mmvqa_engine_num_tensors": (_i, [_P]),

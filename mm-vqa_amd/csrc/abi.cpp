@@ -196,6 +196,10 @@ int mmvqa_cosine_mask(mmvqa_stream_t s, const float* table, const int* rowsA, co
                       const int* colsB, float* mask, int n, int D, int table_rows) {
   return k_cosine_mask(ST(s), table, rowsA, colsA, rowsB, colsB, mask, n, D, table_rows);
 }
+int mmvqa_bertscore_mask(mmvqa_stream_t s, const float* xa, const int* lenA, const float* xb, const int* lenB, float* mask,
+                         float* prec, float* rec, int n, int T, int D, float baseline) {
+  return k_bertscore_mask(ST(s), xa, lenA, xb, lenB, mask, prec, rec, n, T, D, baseline);
+}
 int mmvqa_soft_ce_loss(mmvqa_stream_t s, const float* logits, int ld, const long long* target, const long long* category,
                        const float* table, int table_ld, int n_cat, int mode, double smoothing, float* row_loss,
                        float* loss, float* dlogits, int dld, int rows, int C, float gscale) {

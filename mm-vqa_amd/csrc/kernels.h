@@ -91,6 +91,9 @@ int k_distill_mse(hipStream_t st, const float* h, int ld, const void* table, int
 int k_attention_len_fwd(hipStream_t st, const float* q, const float* k, const float* v, int row_stride, int head_stride,
                         float* out, int out_row_stride, int out_head_stride, const int* len, int B, int T, int heads,
                         float scale);
+// bertscore.hip: BERTScore P / R / F1 of every (candidate, reference) pair of a batch from unit-length token states
+int k_bertscore_mask(hipStream_t st, const float* xa, const int* lenA, const float* xb, const int* lenB, float* mask,
+                     float* prec, float* rec, int n, int T, int D, float baseline);
 // fbattn.hip: the Feedback Transformer's window attention, hidden aggregation, GEGLU and row permutation
 int k_fb_attention(hipStream_t st, const mmvqa_fb_attn_desc& p, int bwd);
 int k_fb_aggregate_fwd(hipStream_t st, const float* hid, long long hstride, int nh, const float* lw, float* agg, long rows, int H);

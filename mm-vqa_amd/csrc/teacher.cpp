@@ -8,7 +8,9 @@
 //                mmvqa_layernorm_fwd  y = LN(t + x)
 //                mmvqa_igemm      f = gelu(y Wi^T + b)
 //                mmvqa_igemm      t = f Wd^T + b
-//                mmvqa_layernorm_fwd  x = LN(t + y)       the last layer writes the caller's buffer
+//                mmvqa_layernorm_fwd  x = LN(t + y)       the last layer run writes the caller's buffer
+// mmvqa_bert_forward_layers stops after the first n_layers layers (HF's hidden_states[n_layers], what BERTScore reads,
+// supcon_utils.py:103-108); mmvqa_bert_forward is the same function with n_layers = layers.
 // Everything is enqueued on the caller's stream; nothing synchronises, allocates or tunes.  Weights and workspace are
 // borrowed device buffers.
 #include <cstdio>
@@ -193,12 +195,17 @@ int mmvqa_bert_bind(mmvqa_bert* e, const float* params, void* workspace, size_t 
   return MMVQA_OK;
 }
 
-int mmvqa_bert_forward(mmvqa_bert* e, mmvqa_stream_t s, const long long* ids, const int* len, int B, int T, float* out) {
-  if (!e || !ids || !len || !out) return mmvqa_set_error(MMVQA_ERR_ARG, "bert_forward: null pointer");
-  if (!e->bound) return mmvqa_set_error(MMVQA_ERR_STATE, "bert_forward: plan and bind first");
+// the embeddings and the first n_layers layers; the last LayerNorm of layer n_layers writes `out` (HF's hidden_states[n_layers])
+static int bert_run(mmvqa_bert* e, mmvqa_stream_t s, const long long* ids, const int* len, int B, int T, int n_layers,
+                    float* out, const char* who) {
+  if (!e || !ids || !len || !out) return mmvqa_set_error(MMVQA_ERR_ARG, "%s: null pointer", who);
+  if (n_layers < 1 || n_layers > (int)e->layers.size())
+    return mmvqa_set_error(MMVQA_ERR_ARG, "%s: n_layers=%d outside 1..%d (the encoder's depth)", who, n_layers,
+                           (int)e->layers.size());
+  if (!e->bound) return mmvqa_set_error(MMVQA_ERR_STATE, "%s: plan and bind first", who);
   if (B != e->B || T != e->T)
-    return mmvqa_set_error(MMVQA_ERR_ARG, "bert_forward: B=%d T=%d differ from the planned B=%d T=%d", B, T, e->B, e->T);
-  if ((uintptr_t)out & 15) return mmvqa_set_error(MMVQA_ERR_ARG, "bert_forward: out must be 16-byte aligned");
+    return mmvqa_set_error(MMVQA_ERR_ARG, "%s: B=%d T=%d differ from the planned B=%d T=%d", who, B, T, e->B, e->T);
+  if ((uintptr_t)out & 15) return mmvqa_set_error(MMVQA_ERR_ARG, "%s: out must be 16-byte aligned", who);
   hipStream_t st = reinterpret_cast<hipStream_t>(s);
   const int M = B * T, H = e->d.hidden, I = e->d.inter, heads = e->d.heads;
   const float* P = e->params;
@@ -216,7 +223,6 @@ int mmvqa_bert_forward(mmvqa_bert* e, mmvqa_stream_t s, const long long* ids, co
   HIP_CHECK_RET(hipMemsetAsync(seg, 0, (size_t)M * sizeof(long long), st));
   TRY(mmvqa_embed_fwd(s, ids, seg, P + e->word, P + e->pos, P + e->type, P + e->emb_g, P + e->emb_b, nullptr, x, nullptr,
                       nullptr, B, T, H, 0, e->d.eps, 0.f, 0u));
-  const int n_layers = (int)e->layers.size();
   for (int i = 0; i < n_layers; ++i) {
     const BertLayerRef& L = e->layers[i];
     TRY(bert_linear(st, x, M, H, P + L.wqkv, P + L.bqkv, 3 * H, MMVQA_ACT_NONE, qkv));
@@ -229,6 +235,15 @@ int mmvqa_bert_forward(mmvqa_bert* e, mmvqa_stream_t s, const long long* ids, co
                             e->d.eps));
   }
   return MMVQA_OK;
+}
+
+int mmvqa_bert_forward(mmvqa_bert* e, mmvqa_stream_t s, const long long* ids, const int* len, int B, int T, float* out) {
+  return bert_run(e, s, ids, len, B, T, e ? (int)e->layers.size() : 1, out, "bert_forward");
+}
+
+int mmvqa_bert_forward_layers(mmvqa_bert* e, mmvqa_stream_t s, const long long* ids, const int* len, int B, int T,
+                              int n_layers, float* out) {
+  return bert_run(e, s, ids, len, B, T, n_layers, out, "bert_forward_layers");
 }
 
 }  // extern "C"

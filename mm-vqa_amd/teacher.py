@@ -4,6 +4,9 @@ Two of the reference's recipes run a stock HF BertModel (`args.clinicalbert`) be
   --task distillation   pretrain/roco_utils.py:112-132: the target of a caption is last_hidden_state[1:len-1]
   --similarity cosine   models/SupConLoss/supcon_utils.py:92-97, 140-159: the positive mask is the cosine of the mean
                         hidden state of caption and translation, the mean taken over ALL padded positions
+and a third scores the token states of an inner layer (BERTScorer, supcon_utils.py:103-108, 170-182):
+  --similarity bert_score   the positive mask is the BERTScore F1 of caption against translation: forward(layer=N) and
+                        bertscore_mask below (csrc/bertscore.hip), the library's greedy matching restated
 
 BertTeacher is that model, forward only: post-LN layers, absolute positions, erf GELU, no pooler, token type 0.  Its
 weights are one flat fp32 buffer; it has no parameters (nothing for an optimiser), its state_dict() is empty (the
@@ -160,15 +163,23 @@ class BertTeacher(torch.nn.Module):
         self._bound = key
 
     @torch.no_grad()
-    def forward(self, ids, lens):
+    def forward(self, ids, lens, layer=None):
         """last_hidden_state [B, T, hidden] of ids int64 [B, T] with per-sample lengths lens int32 [B] (1 <= len <= T;
         positions from len on are padding: never attended to, but their own rows are computed, as HF computes them).
-        Runs on the current stream; nothing is synchronised.  ids outside the vocabulary are not checked."""
+        With layer = N (1..layers) the encoder stops after its first N layers: HF's hidden_states[N], which is what
+        BERTScore reads; None runs all layers.  Runs on the current stream; nothing is synchronised.  ids outside the
+        vocabulary are not checked."""
         B, T = self._check(ids, lens)
+        if layer is not None and not 1 <= int(layer) <= self.layers:
+            raise ValueError(f"BertTeacher: layer = {layer} is outside 1..{self.layers} (the checkpoint's depth)")
         self._plan(B, T)
         ids, lens = ids.contiguous(), lens.contiguous()
         out = torch.empty(B, T, self.hidden, dtype=torch.float32, device=self.flat.device)
-        L.check(L.lib().mmvqa_bert_forward(self._handle, L.stream_ptr(), L.ptr(ids), L.ptr(lens), B, T, L.ptr(out)))
+        if layer is None:
+            L.check(L.lib().mmvqa_bert_forward(self._handle, L.stream_ptr(), L.ptr(ids), L.ptr(lens), B, T, L.ptr(out)))
+        else:
+            L.check(L.lib().mmvqa_bert_forward_layers(self._handle, L.stream_ptr(), L.ptr(ids), L.ptr(lens), B, T, int(layer),
+                                                      L.ptr(out)))
         return out
 
     @torch.no_grad()
@@ -223,3 +234,51 @@ def cosine_mask_from_means(means, n=None):
     L.check(lib.mmvqa_cosine_mask(L.stream_ptr(), L.ptr(table), L.ptr(ra), L.ptr(ca), L.ptr(rb), L.ptr(cb), L.ptr(mask), n, D,
                                   rows))
     return mask
+
+
+BERTSCORE_EPS = 1e-12      # the library divides by the plain norm; BERT states are far from zero
+
+
+def normalize_states_(x):
+    """rows of fp32 [..., D] to unit length in place (x / max(|x|, 1e-12), mmvqa_normalize_rows); current stream"""
+    if x.dtype != torch.float32 or not x.is_cuda or not x.is_contiguous():
+        raise ValueError("normalize_states_: a contiguous fp32 GPU tensor is expected")
+    D = x.shape[-1]
+    L.check(L.lib().mmvqa_normalize_rows(L.stream_ptr(), L.ptr(x), x.numel() // D, D, BERTSCORE_EPS))
+    return x
+
+
+def bertscore_mask_unit(xa, lenA, xb, lenB, baseline=0.0, return_pr=False):
+    """mmvqa_bertscore_mask on states whose rows are already of unit length (see bertscore_mask)"""
+    if xa.dim() != 3 or xb.shape != xa.shape or xa.dtype != torch.float32 or xb.dtype != torch.float32:
+        raise ValueError("bertscore_mask: `xa` and `xb` must be fp32 [n, T, D] tensors of one shape")
+    if not xa.is_cuda or xb.device != xa.device:
+        raise L.MMVQAError("bertscore_mask: GPU tensors only (no CPU fallback)")
+    n, T, D = xa.shape
+    for ln in (lenA, lenB):
+        if not torch.is_tensor(ln) or ln.dtype != torch.int32 or tuple(ln.shape) != (n,) or ln.device != xa.device:
+            raise ValueError(f"bertscore_mask: the lengths must be int32 [{n}] tensors on the states' device")
+    xa, xb, lenA, lenB = xa.contiguous(), xb.contiguous(), lenA.contiguous(), lenB.contiguous()
+    mask = torch.empty(n, n, dtype=torch.float32, device=xa.device)
+    pr = torch.empty(2, n, n, dtype=torch.float32, device=xa.device) if return_pr else None
+    L.check(L.lib().mmvqa_bertscore_mask(L.stream_ptr(), L.ptr(xa), L.ptr(lenA), L.ptr(xb), L.ptr(lenB), L.ptr(mask),
+                                         L.ptr(pr[0]) if return_pr else None, L.ptr(pr[1]) if return_pr else None, n, T, D,
+                                         float(baseline)))
+    return (mask, pr[0], pr[1]) if return_pr else mask
+
+
+def bertscore_mask(xa, lenA, xb, lenB, baseline=0.0, return_pr=False):
+    """the BERTScore F1 mask of SimilarityCalculator.bert_score (supcon_utils.py:170-182), the library's greedy matching
+    restated (idf off, one candidate against one reference): xa / xb fp32 [n, T, D] are the token states of the n
+    candidates / references (position 0 [CLS], position len - 1 [SEP]), lenA / lenB int32 [n].  Copies of the states are
+    brought to unit length (eps 1e-12); S = all cosines of text i against text j over positions < len, specials
+    included as match targets; P / R = the mean over the word pieces 1..len-2 of the row / column maxima; mask[i][j] =
+    2PR / (P + R) (NaN -> 0, an empty text -> 0), then (F - baseline) / (1 - baseline) when baseline != 0; unit diagonal.
+    -> mask [n, n] fp32, with return_pr also P and R (not rescaled).  Positions >= len are never read by the score
+    kernel.  Runs on the current stream; nothing is synchronised."""
+    if xa.dtype != torch.float32 or xb.dtype != torch.float32:
+        raise ValueError("bertscore_mask: `xa` and `xb` must be fp32 [n, T, D] tensors of one shape")
+    if not xa.is_cuda or not xb.is_cuda:
+        raise L.MMVQAError("bertscore_mask: GPU tensors only (no CPU fallback)")
+    return bertscore_mask_unit(normalize_states_(xa.contiguous().clone()), lenA, normalize_states_(xb.contiguous().clone()),
+                               lenB, baseline, return_pr)

@@ -38,6 +38,9 @@ torch.distributed (RCCL).
                                      --caption_embeddings roco_train_embeddings.npz
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --supcon_mask cosine \\
                                      --teacher_weights clinicalbert.pt --teacher_vocab_file clinicalbert_vocab.txt
+    python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --supcon_mask bert_score \\
+                                     --teacher_weights scibert.pt --teacher_vocab_file scibert_vocab.txt \\
+                                     --teacher_lower_case --bert_score_layer 8 --max_token_length 64
 """
 from __future__ import annotations
 
@@ -54,8 +57,10 @@ from . import (CategorySmoothing, FusedAdam, LabelSmoothing, Model, asl_loss, ch
                evaluate, jaccard_mask, mlm_loss, split_feat, supcon_loss, synth)
 from . import data as D
 from .amp import GradScaler
-from .ddp import GradReducer, comm_info, global_supcon_means, global_supcon_pairs, global_supcon_views, sync_replicas
-from .teacher import BertTeacher, cosine_mask_from_means
+from .ddp import (GradReducer, comm_info, global_supcon_means, global_supcon_pairs, global_supcon_states, global_supcon_views,
+                  sync_replicas)
+from .ddp import world as ddp_world
+from .teacher import BertTeacher, bertscore_mask_unit, cosine_mask_from_means, normalize_states_
 
 
 def common_args(p):
@@ -159,8 +164,11 @@ def roco_supcon_feeders(args, ctx, pairs):
         words = D.WordSets.from_table(table).to(ctx.dev)
     elif kind == "embeddings":
         words = D.CaptionEmbeddings.from_file(args.caption_embeddings, table).to(ctx.dev)
-    elif kind == "cosine":
+    elif kind in ("cosine", "bert_score"):
         words, ttok = load_teacher(args, ctx), teacher_tokenizer(args)
+        if kind == "bert_score" and not 1 <= args.bert_score_layer <= words.layers:
+            raise ValueError(f"--bert_score_layer {args.bert_score_layer} is outside 1..{words.layers}, the depth of "
+                             f"{args.teacher_weights}")
     tr = D.RocoSupConDataset(table, tok, kw, args.num_vis, args.max_position_embeddings, args.mlm_prob, args.seed,
                              report_aug_col=masked, teacher_tokenizer=ttok,
                              max_token_length=getattr(args, "max_token_length", 512))
@@ -359,7 +367,26 @@ def teacher_cosine_mask(teacher, rows, teacher_T=None):
     return cosine_mask_from_means(means)
 
 
-def supcon_step(model, opt, red, world, batch, words=None, teacher_T=None):
+def teacher_bertscore_mask(teacher, rows, layer, baseline, teacher_T=None):
+    """SimilarityCalculator.bert_score (supcon_utils.py:170-182) on the device from the 2n teacher rows (captions, then
+    the translations drawn): the teacher's hidden_states[layer] of every text, rows to unit length, and
+    teacher.bertscore_mask's F1 of caption i against translation j with a unit diagonal -> [n, n].  The reference scores
+    each pair alone; here the batch is padded to its longest text and no padded position enters a score, so the mask
+    does not depend on the padding.  Under data parallelism each rank's states are zero-padded to the rows' fixed width
+    (--max_token_length), gathered in the sample order of global_supcon_views (ddp.global_supcon_states) and every rank
+    builds the global [world n, world n] mask."""
+    ids, lens, Tp = teacher_inputs(rows, teacher_T)
+    states = normalize_states_(teacher(ids, lens, layer=layer))
+    n, width = rows.shape[0] // 2, rows.shape[1] - 1
+    if ddp_world() > 1 and Tp < width:
+        padded = states.new_zeros(2 * n, width, states.shape[2])
+        padded[:, :Tp] = states
+        states = padded
+    xa, la, xb, lb = global_supcon_states(states, lens, n)
+    return bertscore_mask_unit(xa, la, xb, lb, baseline)
+
+
+def supcon_step(model, opt, red, world, batch, words=None, teacher_T=None, bert_score=None):
     """models/SupConLoss/supcon_utils.py:270-294: MLM loss over both views + SupCon(split_feat(feat)) (called without
     a mask => SimCLR, :287); under DDP the views of all ranks are gathered first.  Returns (loss, pred, stats).
     With `words` (--supcon_mask jaccard: the table's WordSets on the device) the batch is the feeder's 6-tuple and the
@@ -370,7 +397,8 @@ def supcon_step(model, opt, red, world, batch, words=None, teacher_T=None):
     ranks are gathered and every rank builds the global mask, in the sample order of the gathered features; gather and
     mask launch go on the step's stream.  When `words` is a teacher.BertTeacher (--supcon_mask cosine) the batch's sixth
     element holds the teacher's ids of caption and translation and the mask is teacher_cosine_mask's; teacher_T is the
-    feeder's host-side longest length."""
+    feeder's host-side longest length.  With bert_score = (layer, baseline) beside the teacher (--supcon_mask bert_score)
+    the same ids give teacher_bertscore_mask's BERTScore F1 mask instead (:170-182)."""
     img, ids, seg, mask, tgt = batch[:5]
     opt.zero_grad()
     logits, feat = model(img, ids, seg, mask)
@@ -379,6 +407,8 @@ def supcon_step(model, opt, red, world, batch, words=None, teacher_T=None):
     feat = global_supcon_views(feat, bsz)          # = split_feat(feat, bsz) on one rank; global negatives under DDP
     if words is None:
         loss = loss_mlm + supcon_loss(feat)        # 2N*world rows: the tiled kernel has no size cap
+    elif isinstance(words, BertTeacher) and bert_score is not None:
+        loss = loss_mlm + supcon_loss(feat, mask=teacher_bertscore_mask(words, batch[5], bert_score[0], bert_score[1], teacher_T))
     elif isinstance(words, BertTeacher):
         loss = loss_mlm + supcon_loss(feat, mask=teacher_cosine_mask(words, batch[5], teacher_T))
     else:
@@ -616,6 +646,8 @@ def run_supcon(args):
         raise ValueError("--batch_size must be >= 2 (two views per sample)")
     # (fed batches come in process_tensors' layout: data.collate_supcon)
     tr_fd, va_fd, words = roco_supcon_feeders(args, ctx, n) if args.data_dir else (None, None, None)
+    bert_score = ((args.bert_score_layer, args.bert_score_baseline)
+                  if getattr(args, "supcon_mask", "none") == "bert_score" else None)
 
     def synthetic(epoch):
         for sd in train_seeds(args, ctx, epoch):
@@ -624,7 +656,7 @@ def run_supcon(args):
 
     def step(batch):
         tT = tr_fd.log[-1]["teacher_T"] if isinstance(words, BertTeacher) else None   # the feeder's host-side longest length
-        loss, _, stats = supcon_step(model, opt, red, ctx.world, batch, words=words, teacher_T=tT)
+        loss, _, stats = supcon_step(model, opt, red, ctx.world, batch, words=words, teacher_T=tT, bert_score=bert_score)
         # fed: the MLM accuracy train_one_epoch returns (supcon_utils.py:296-318); synthetic: `stats` stays on the device
         return (float(loss.detach()), *(stats.tolist()[1:] if tr_fd is not None else (0, 0)))
 
@@ -861,13 +893,24 @@ def parse_args(argv=None):
         if mode == "supcon":
             p.add_argument("--con_task", type=str, default="supcon", choices=["simclr", "supcon"])
             p.add_argument("--similarity", type=str, default="sentence_transformers")      # accepted, not read
-            p.add_argument("--supcon_mask", type=str, default="none", choices=["none", "jaccard", "embeddings", "cosine"],
+            p.add_argument("--bert_score", type=str, default=None, choices=["bert", "scibert"])   # accepted; `bert` is refused below
+            p.add_argument("--bert_score_layer", type=int, default=None, metavar="N",
+                           help="with --supcon_mask bert_score: the teacher's hidden layer whose output is scored, "
+                                "hidden_states[N] with N in 1..the checkpoint's depth (default 8, the library's choice "
+                                "for allenai/scibert_scivocab_uncased)")
+            p.add_argument("--bert_score_baseline", type=float, default=None, metavar="B",
+                           help="with --supcon_mask bert_score: rescale F to (F - B) / (1 - B), the library's "
+                                "rescale_with_baseline (default 0: no rescaling)")
+            p.add_argument("--supcon_mask", type=str, default="none",
+                           choices=["none", "jaccard", "embeddings", "cosine", "bert_score"],
                            help="positives of the SupCon loss: none = the other view only (SimCLR, what the reference's "
                                 "loop runs); jaccard = caption / back-translation word overlap weights every pair "
                                 "(SimilarityCalculator.jaccard); embeddings = the cosine of the two texts' sentence "
                                 "embeddings (SimilarityCalculator.sentence_trans) from --caption_embeddings; cosine = "
                                 "the cosine of the BERT teacher's mean hidden states of the two texts "
-                                "(SimilarityCalculator.bert_embedd), the teacher of --teacher_weights run per batch.  "
+                                "(SimilarityCalculator.bert_embedd), the teacher of --teacher_weights run per batch; "
+                                "bert_score = the BERTScore F1 of the two texts (SimilarityCalculator.bert_score, the "
+                                "library's greedy matching restated) from the same teacher's --bert_score_layer.  "
                                 "Every mask is built on the GPU per batch and needs --data_dir")
             p.add_argument("--caption_embeddings", type=str, default=None, metavar="FILE",
                            help="with --supcon_mask embeddings: an .npz of precomputed sentence embeddings, names [R] "
@@ -915,8 +958,26 @@ def parse_args(argv=None):
             # (worded as argparse words a refused value: without the teacher's files `cosine` is not a choice)
             p.error("argument --supcon_mask: invalid choice: 'cosine' needs --teacher_weights FILE and --teacher_vocab_file FILE "
                     "(the BERT teacher and its WordPiece)")
-        if args.supcon_mask != "cosine" and tgiven:
-            p.error(f"--{tgiven[0]} is read by --supcon_mask cosine only, not by --supcon_mask {args.supcon_mask}")
+        if args.supcon_mask == "bert_score" and len(tgiven) != 2:
+            p.error("argument --supcon_mask: invalid choice: 'bert_score' needs --teacher_weights FILE and --teacher_vocab_file "
+                    "FILE (the BERT teacher whose hidden layer is scored, and its WordPiece)")
+        if args.supcon_mask not in ("cosine", "bert_score") and tgiven:
+            p.error(f"--{tgiven[0]} is read by --supcon_mask bert_score and --supcon_mask cosine only, not by --supcon_mask "
+                    f"{args.supcon_mask}")
+        if args.bert_score == "bert":
+            p.error("--bert_score bert is roberta-large with a baseline file (BERTScorer(lang='en', rescale_with_baseline=True)): "
+                    "neither its byte-level BPE nor the baseline file is built here; use --bert_score scibert with a local "
+                    "BERT checkpoint")
+        bgiven = [o for o in ("bert_score_layer", "bert_score_baseline") if getattr(args, o) is not None]
+        if args.supcon_mask != "bert_score" and bgiven:
+            p.error(f"--{bgiven[0]} is read by --supcon_mask bert_score only, not by --supcon_mask {args.supcon_mask}")
+        if args.supcon_mask == "bert_score":
+            args.bert_score_layer = 8 if args.bert_score_layer is None else args.bert_score_layer
+            args.bert_score_baseline = 0.0 if args.bert_score_baseline is None else args.bert_score_baseline
+            if args.bert_score_layer < 1:
+                p.error(f"--bert_score_layer {args.bert_score_layer} must be at least 1 (hidden_states[0] is the embeddings)")
+            if not args.bert_score_baseline < 1.0:
+                p.error(f"--bert_score_baseline {args.bert_score_baseline} must be below 1 (F is divided by 1 - B)")
     if mode in ("distill", "supcon") and args.max_token_length < 2:
         p.error(f"--max_token_length {args.max_token_length} has no room for [CLS] and [SEP]")
     if mode == "distill":
