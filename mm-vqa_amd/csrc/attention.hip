@@ -1,34 +1,27 @@
 // Fused self-attention for T <= 128 on the gfx950 fp32-input MFMA; no LDS, no score tensor in HBM
 // other than the probabilities kept for backward.
 //
-// One wave owns (batch b, head, 32-query tile).  Scores are produced TRANSPOSED
-// (S^T[j][i] = K_j . Q_i: keys on accumulator registers, queries on lanes) so that
-//  * softmax over keys is an in-register reduction plus one cross-half exchange, and
-//  * the probability tile is directly the A operand of the P.V MFMA (its k index = key sits on
-//    the registers/lane-half exactly as v_mfma_f32_32x32x2_f32 wants it; see
-//    cdna_hip_programming.md "An accumulator tile as the next MFMA's operand").
+// One wave owns (batch b, head, 32-query tile).  Scores are produced TRANSPOSED (S^T[j][i] = K_j . Q_i: keys on
+// accumulator registers, queries on lanes): the wave-tile idiom of wave_tile.h, which also defines the dropout stream.
 //
 // Covers both encoders of the reference:
 //   BertLayer  (models/transformer.py:19-30): S/sqrt(d) - 10000(1-mask[key]); softmax; dropout; .V
 //   RealFormer (models/realformer.py:30-45) : S/sqrt(d) + prev - 10000(1-mask[QUERY]); prev<-S; softmax; .V
 // fp32 op order follows the reference: (q.k)/sqrt(d), then +prev, then -10000*(1-m).
-#include "common.h"
+#include "wave_tile.h"
 
-template <int D2, int VW>
-__device__ __forceinline__ void load_half_row(const float* p, float (&r)[D2]) {
-  if constexpr (VW == 4) {
-#pragma unroll
-    for (int s = 0; s < D2; s += 4) {
-      f32x4 t = *reinterpret_cast<const f32x4*>(p + s);
-      r[s] = t[0]; r[s + 1] = t[1]; r[s + 2] = t[2]; r[s + 3] = t[3];
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < D2; ++s) r[s] = p[s];
-  }
+// Global operands of the forward kernel that its one-tile form (HOIST) prefetches and its other forms load at the point
+// of use: the address is written once, here, and both places call it.
+__device__ __forceinline__ float key_mask(const long long* mask, int b, int T, int j) { return (float)mask[b * T + j]; }
+// [b][query][key][head] of prev_in / prev_out
+__device__ __forceinline__ size_t prev_at(int b, int T, int query, int key, int heads, int head) {
+  return ((size_t)(b * T + query) * T + key) * heads + head;
 }
-
-__device__ __forceinline__ int erow(int e, int lh) { return (e & 3) + 8 * (e >> 2) + 4 * lh; }
+// element dd of row r of sample b of a [B*T][stride] operand (this head's columns from hoff); 0 outside
+template <int D>
+__device__ __forceinline__ float ld_elem(const float* x, int b, int T, int r, int dd, int stride, size_t hoff) {
+  return (r < T && dd < D) ? x[(size_t)(b * T + r) * stride + hoff + dd] : 0.f;
+}
 
 // --------------------------------------------------------------------------- forward
 template <int D, int NJ>
@@ -43,10 +36,7 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnParams p) {
 
   float qf[D2];
   if (qvalid) load_half_row<D2, VW>(p.q + (size_t)(b * T + qi) * p.row_stride + hb + lh * D2, qf);
-  else {
-#pragma unroll
-    for (int s = 0; s < D2; ++s) qf[s] = 0.f;
-  }
+  else zero_row(qf);
   const float qmask = (qvalid && p.mask_on_query) ? (float)p.mask[b * T + qi] : 1.f;
 
   // One 32-key tile (T <= 32, the bench's shape): every global load of the kernel is issued here, before the first
@@ -57,15 +47,12 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnParams p) {
   if constexpr (HOIST) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int j = erow(e, lh);
+      const int j = tile_row(e, lh);
       const bool ok = j < T && qvalid;
-      h_mk[e] = (ok && !p.mask_on_query) ? (float)p.mask[b * T + j] : 1.f;
-      h_pv[e] = (ok && p.prev_in) ? p.prev_in[((size_t)(b * T + qi) * T + j) * p.heads + head] : 0.f;
+      h_mk[e] = (ok && !p.mask_on_query) ? key_mask(p.mask, b, T, j) : 1.f;
+      h_pv[e] = (ok && p.prev_in) ? p.prev_in[prev_at(b, T, qi, j, p.heads, head)] : 0.f;
 #pragma unroll
-      for (int dt = 0; dt < ND; ++dt) {
-        const int dd = dt * 32 + li;
-        h_v[dt * 16 + e] = (j < T && dd < D) ? p.v[(size_t)(b * T + j) * p.row_stride + hb + dd] : 0.f;
-      }
+      for (int dt = 0; dt < ND; ++dt) h_v[dt * 16 + e] = ld_elem<D>(p.v, b, T, j, dt * 32 + li, p.row_stride, hb);
     }
   }
 
@@ -75,16 +62,8 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnParams p) {
     float kf[D2];
     const int kj = jt * 32 + li;
     if (kj < T) load_half_row<D2, VW>(p.k + (size_t)(b * T + kj) * p.row_stride + hb + lh * D2, kf);
-    else {
-#pragma unroll
-      for (int s = 0; s < D2; ++s) kf[s] = 0.f;
-    }
-    f32x16 a;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) a[e] = 0.f;
-#pragma unroll
-    for (int s = 0; s < D2; ++s) a = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s], qf[s], a, 0, 0, 0);
-    sc[jt] = a;
+    else zero_row(kf);
+    sc[jt] = tile_product<D2>(kf, qf);
   }
 
   // scale, residual, mask; row max
@@ -93,19 +72,13 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnParams p) {
   for (int jt = 0; jt < NJ; ++jt) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int j = jt * 32 + erow(e, lh);
+      const int j = jt * 32 + tile_row(e, lh);
       float s = -INFINITY;
       if (j < T && qvalid) {
         s = sc[jt][e] / p.sqrt_d;
-        const size_t po = ((size_t)(b * T + qi) * T + j) * p.heads + head;
-        float mval;
-        if constexpr (HOIST) {
-          if (p.prev_in) s = s + h_pv[e];
-          mval = p.mask_on_query ? qmask : h_mk[e];
-        } else {
-          if (p.prev_in) s = s + p.prev_in[po];
-          mval = p.mask_on_query ? qmask : (float)p.mask[b * T + j];
-        }
+        const size_t po = prev_at(b, T, qi, j, p.heads, head);
+        if (p.prev_in) s = s + (HOIST ? h_pv[e] : p.prev_in[po]);
+        const float mval = p.mask_on_query ? qmask : (HOIST ? h_mk[e] : key_mask(p.mask, b, T, j));
         s = s - 10000.0f * (1.0f - mval);
         if (p.prev_out) p.prev_out[po] = s;
       }
@@ -113,31 +86,16 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnParams p) {
       mx = fmaxf(mx, s);
     }
   }
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  float sum = 0.f;
+  const float inv = tile_softmax<NJ>(sc, mx, qvalid);
+  const AttnDrop drop(p.seed, p.drop_p);
 #pragma unroll
   for (int jt = 0; jt < NJ; ++jt) {
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      float ex = (sc[jt][e] == -INFINITY) ? 0.f : expf(sc[jt][e] - mx);
-      sc[jt][e] = ex;
-      sum += ex;
-    }
-  }
-  sum += __shfl_xor(sum, 32, 64);
-  const float inv = qvalid ? 1.0f / sum : 0.f;
-  const float ks = p.drop_p > 0.f ? 1.0f / (1.0f - p.drop_p) : 1.f;
-#pragma unroll
-  for (int jt = 0; jt < NJ; ++jt) {
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int j = jt * 32 + erow(e, lh);
+      const int j = jt * 32 + tile_row(e, lh);
       float pr = sc[jt][e] * inv;
       if (p.probs && j < T && qvalid) p.probs[((size_t)(b * p.heads + head) * T + j) * T + qi] = pr;
-      if (p.drop_p > 0.f) {
-        float u = rng_uniform(p.seed, (uint32_t)(((b * p.heads + head) * T + qi) * T + j));
-        pr = (u >= p.drop_p) ? pr * ks : 0.f;
-      }
+      if (drop.p > 0.f) pr = drop.keep(b * p.heads + head, T, qi, j) ? pr * drop.ks : 0.f;
       sc[jt][e] = pr;
     }
   }
@@ -145,24 +103,20 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnParams p) {
   // O[i][d] = sum_j P[i][j] V[j][d]: A = P^T accumulator (k = key on registers/half), B = V rows
 #pragma unroll
   for (int dt = 0; dt < ND; ++dt) {
-    f32x16 o;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) o[e] = 0.f;
+    f32x16 o = tile_zero();
     const int dd = dt * 32 + li;
 #pragma unroll
     for (int jt = 0; jt < NJ; ++jt) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int j = jt * 32 + erow(e, lh);
-        float vv;
-        if constexpr (HOIST) vv = h_v[dt * 16 + e];
-        else vv = (j < T && dd < D) ? p.v[(size_t)(b * T + j) * p.row_stride + hb + dd] : 0.f;
+        const int j = jt * 32 + tile_row(e, lh);
+        const float vv = HOIST ? h_v[dt * 16 + e] : ld_elem<D>(p.v, b, T, j, dd, p.row_stride, hb);
         o = __builtin_amdgcn_mfma_f32_32x32x2f32(sc[jt][e], vv, o, 0, 0, 0);
       }
     }
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int i = it * 32 + erow(e, lh);
+      const int i = it * 32 + tile_row(e, lh);
       if (i < T && dd < D)
         p.out[(size_t)(b * T + i) * p.out_row_stride + (size_t)head * p.out_head_stride + dd] = o[e];
     }
@@ -181,8 +135,9 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnParams p) {
   const int T = p.T;
   const size_t hb = (size_t)head * p.head_stride;
   const size_t ohb = (size_t)head * p.out_head_stride;
-  const float ks = p.drop_p > 0.f ? 1.0f / (1.0f - p.drop_p) : 1.f;
-  const size_t pbase = (size_t)(b * p.heads + head) * T * T;
+  const AttnDrop drop(p.seed, p.drop_p);
+  const int bh = b * p.heads + head;
+  const size_t pbase = (size_t)bh * T * T;
 
   float delta[NJ];  // delta[it] for query it*32+li
   // One 32 x 32 tile (T <= 32): every global load of both passes is issued here, before the first store (see the
@@ -194,7 +149,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnParams p) {
     const bool lv = li < T;   // this lane's query (pass A) / key (pass B) exists
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int r = erow(e, lh);   // the key of pass A, the query of pass B
+      const int r = tile_row(e, lh);   // the key of pass A, the query of pass B
       const bool ok = r < T && lv;
       h_pa[e] = ok ? p.probs[pbase + (size_t)r * T + li] : 0.f;
       h_pb[e] = ok ? p.probs[pbase + (size_t)li * T + r] : 0.f;
@@ -217,10 +172,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnParams p) {
     const bool qvalid = qi < T;
     float dof[D2];
     if (qvalid) load_half_row<D2, VW>(p.dout + (size_t)(b * T + qi) * p.out_row_stride + ohb + lh * D2, dof);
-    else {
-#pragma unroll
-      for (int s = 0; s < D2; ++s) dof[s] = 0.f;
-    }
+    else zero_row(dof);
     f32x16 ds[NJ];
     float dl = 0.f;
 #pragma unroll
@@ -228,28 +180,20 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnParams p) {
       float vf[D2];
       const int kj = jt * 32 + li;
       if (kj < T) load_half_row<D2, VW>(p.v + (size_t)(b * T + kj) * p.row_stride + hb + lh * D2, vf);
-      else {
+      else {   // written out, not zero_row(vf): with it attn_bwd_kernel<96, 2> compiled to other register counts
 #pragma unroll
         for (int s = 0; s < D2; ++s) vf[s] = 0.f;
       }
-      f32x16 a;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) a[e] = 0.f;
-#pragma unroll
-      for (int s = 0; s < D2; ++s) a = __builtin_amdgcn_mfma_f32_32x32x2f32(vf[s], dof[s], a, 0, 0, 0);
-      // a[e] = dP'[i=qi][j(e)]  (grad wrt post-dropout probabilities)
+      const f32x16 a = tile_product<D2>(vf, dof);   // a[e] = dP'[i=qi][j(e)]  (grad wrt post-dropout probabilities)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int j = jt * 32 + erow(e, lh);
+        const int j = jt * 32 + tile_row(e, lh);
         float pr = 0.f, dp = 0.f;
         if (j < T && qvalid) {
           if constexpr (HOIST) pr = h_pa[e];
           else pr = p.probs[pbase + (size_t)j * T + qi];
           dp = a[e];
-          if (p.drop_p > 0.f) {
-            float u = rng_uniform(p.seed, (uint32_t)(((b * p.heads + head) * T + qi) * T + j));
-            dp = (u >= p.drop_p) ? dp * ks : 0.f;
-          }
+          if (drop.p > 0.f) dp = drop.keep(bh, T, qi, j) ? dp * drop.ks : 0.f;
         }
         dl += dp * pr;
         ds[jt][e] = pr * dp;  // dS = P*dP - P*delta once delta is known (P is re-read: tiny, cache-resident)
@@ -260,14 +204,12 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnParams p) {
     // dS^T[j][i] = P*dP - P*delta (+ dprev) ; then dQ += dS . K / sqrt(d)
     f32x16 dq[ND];
 #pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) dq[dt][e] = 0.f;
+    for (int dt = 0; dt < ND; ++dt) dq[dt] = tile_zero();
 #pragma unroll
     for (int jt = 0; jt < NJ; ++jt) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int j = jt * 32 + erow(e, lh);
+        const int j = jt * 32 + tile_row(e, lh);
         float g = 0.f;
         if (j < T && qvalid) {
           float pr;
@@ -287,7 +229,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnParams p) {
         const int dd = dt * 32 + li;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int j = jt * 32 + erow(e, lh);
+          const int j = jt * 32 + tile_row(e, lh);
           float kv;
           if constexpr (HOIST) kv = h_k[dt * 16 + e];
           else kv = (j < T && dd < D) ? p.k[(size_t)(b * T + j) * p.row_stride + hb + dd] : 0.f;
@@ -300,7 +242,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnParams p) {
       const int dd = dt * 32 + li;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int i = it * 32 + erow(e, lh);
+        const int i = it * 32 + tile_row(e, lh);
         if (i < T && dd < D) p.dq[(size_t)(b * T + i) * p.row_stride + hb + dd] = dq[dt][e];
       }
     }
@@ -313,46 +255,33 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnParams p) {
     const bool kvalid = kj < T;
     float vf[D2];
     if (kvalid) load_half_row<D2, VW>(p.v + (size_t)(b * T + kj) * p.row_stride + hb + lh * D2, vf);
-    else {
-#pragma unroll
-      for (int s = 0; s < D2; ++s) vf[s] = 0.f;
-    }
+    else zero_row(vf);
     f32x16 dk[ND], dv[ND];
 #pragma unroll
-    for (int dt = 0; dt < ND; ++dt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) { dk[dt][e] = 0.f; dv[dt][e] = 0.f; }
+    for (int dt = 0; dt < ND; ++dt) { dk[dt] = tile_zero(); dv[dt] = tile_zero(); }
 #pragma unroll
     for (int it = 0; it < NJ; ++it) {
       float dof[D2];
       const int qi_l = it * 32 + li;
       if (qi_l < T) load_half_row<D2, VW>(p.dout + (size_t)(b * T + qi_l) * p.out_row_stride + ohb + lh * D2, dof);
-      else {
-#pragma unroll
-        for (int s = 0; s < D2; ++s) dof[s] = 0.f;
-      }
+      else zero_row(dof);
       // a[e] = dP'[i(e)][j=kj] = dO_i . V_j   (A = dO rows -> registers carry i, B = V rows -> lanes carry j)
-      f32x16 a;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) a[e] = 0.f;
-#pragma unroll
-      for (int s = 0; s < D2; ++s) a = __builtin_amdgcn_mfma_f32_32x32x2f32(dof[s], vf[s], a, 0, 0, 0);
+      const f32x16 a = tile_product<D2>(dof, vf);
       f32x16 pd, sd;  // P' (post-dropout) and dS, element e <-> query i(e), lane <-> key kj
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int i = it * 32 + erow(e, lh);
-        const float dli = __shfl(delta[it], erow(e, lh), 64);  // delta of query i lives in lane (i & 31)
+        const int i = it * 32 + tile_row(e, lh);
+        const float dli = __shfl(delta[it], tile_row(e, lh), 64);  // delta of query i lives in lane (i & 31)
         float pr = 0.f, prd = 0.f, g = 0.f;
         if (i < T && kvalid) {
           if constexpr (HOIST) pr = h_pb[e];
           else pr = p.probs[pbase + (size_t)kj * T + i];
           float dp = a[e];
           prd = pr;
-          if (p.drop_p > 0.f) {
-            float u = rng_uniform(p.seed, (uint32_t)(((b * p.heads + head) * T + i) * T + kj));
-            bool keep = u >= p.drop_p;
-            dp = keep ? dp * ks : 0.f;
-            prd = keep ? pr * ks : 0.f;
+          if (drop.p > 0.f) {
+            const bool keep = drop.keep(bh, T, i, kj);
+            dp = keep ? dp * drop.ks : 0.f;
+            prd = keep ? pr * drop.ks : 0.f;
           }
           g = pr * (dp - dli);
           if constexpr (HOIST) { if (p.dprev_in) g += h_db[e]; }
@@ -367,7 +296,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnParams p) {
         const int dd = dt * 32 + li;
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
-          const int i = it * 32 + erow(e, lh);
+          const int i = it * 32 + tile_row(e, lh);
           const bool ok = (i < T && dd < D);
           float qv, dov;
           if constexpr (HOIST) { qv = h_q[dt * 16 + e]; dov = h_do[dt * 16 + e]; }
@@ -388,7 +317,7 @@ __global__ __launch_bounds__(64) void attn_bwd_kernel(const AttnParams p) {
       const int dd = dt * 32 + li;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int j = jt * 32 + erow(e, lh);
+        const int j = jt * 32 + tile_row(e, lh);
         if (j < T && dd < D) {
           p.dk[(size_t)(b * T + j) * p.row_stride + hb + dd] = dk[dt][e];
           p.dv[(size_t)(b * T + j) * p.row_stride + hb + dd] = dv[dt][e];

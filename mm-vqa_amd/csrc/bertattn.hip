@@ -3,11 +3,11 @@
 // No dropout, nothing saved for a backward pass, no score tensor in HBM, no LDS, no atomics.
 //
 // One wave owns (batch b, head, 32-query tile), as attention.hip's forward does, and the scores are produced
-// TRANSPOSED (S^T[j][i] = K_j . Q_i: keys on accumulator registers, queries on lanes) so that the probability tile is
-// directly the A operand of the P.V product on v_mfma_f32_32x32x2_f32.  The key axis is a RUN-TIME loop over
-// ceil(len[b] / 32) tiles with an online softmax: running maximum m, running sum l and the two 32 x 32 output
-// accumulators rescaled by exp(m_old - m_new) per tile.  Each tile's order of operations is fixed, so the result is
-// bit-equal from launch to launch, and what a query computes does not depend on the lane or tile it sits in.
+// TRANSPOSED (the wave-tile idiom of wave_tile.h: keys on accumulator registers, queries on lanes) so that the
+// probability tile is directly the A operand of the P.V product on v_mfma_f32_32x32x2_f32.  The key axis is a RUN-TIME
+// loop over ceil(len[b] / 32) tiles with an online softmax: running maximum m, running sum l and the two 32 x 32
+// output accumulators rescaled by exp(m_old - m_new) per tile.  Each tile's order of operations is fixed, so the result
+// is bit-equal from launch to launch, and what a query computes does not depend on the lane or tile it sits in.
 //
 // Lengths: keys j >= len[b] are SELECTED out (probability exactly 0, the v row replaced by 0), never read, and tiles
 // that lie wholly past len[b] are not visited; an additive -10000 is not used.  Query rows i >= len[b] (i < T) are
@@ -15,6 +15,7 @@
 // and reads nothing (the convention of distill.hip).
 #include "common.h"
 #include "kernels.h"
+#include "wave_tile.h"
 
 #include <cstdint>
 
@@ -34,23 +35,6 @@ struct BertAttnParams {
 };
 
 template <int VW>
-__device__ __forceinline__ void ba_load_half(const float* __restrict__ p, float (&r)[BA_D2]) {
-  if constexpr (VW == 4) {
-#pragma unroll
-    for (int s = 0; s < BA_D2; s += 4) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(p + s);
-      r[s] = t[0]; r[s + 1] = t[1]; r[s + 2] = t[2]; r[s + 3] = t[3];
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < BA_D2; ++s) r[s] = p[s];
-  }
-}
-
-// row of accumulator register e in lane half lh of a 32 x 32 MFMA result
-__device__ __forceinline__ int ba_erow(int e, int lh) { return (e & 3) + 8 * (e >> 2) + 4 * lh; }
-
-template <int VW>
 __global__ __launch_bounds__(64) void attn_len_fwd_kernel(const BertAttnParams p) {
   const int lane = threadIdx.x, li = lane & 31, lh = lane >> 5;
   const int it = blockIdx.x, head = blockIdx.y, b = blockIdx.z;
@@ -63,7 +47,7 @@ __global__ __launch_bounds__(64) void attn_len_fwd_kernel(const BertAttnParams p
     const float nan = __int_as_float(0x7fc00000);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int i = it * 32 + ba_erow(e, lh);
+      const int i = it * 32 + tile_row(e, lh);
       if (i < T) { ob[(size_t)i * ors + li] = nan; ob[(size_t)i * ors + 32 + li] = nan; }
     }
     return;
@@ -77,15 +61,10 @@ __global__ __launch_bounds__(64) void attn_len_fwd_kernel(const BertAttnParams p
 
   const int qi = it * 32 + li;
   float qf[BA_D2];
-  if (qi < T) ba_load_half<VW>(qb + (size_t)qi * rs + lh * BA_D2, qf);
-  else {
-#pragma unroll
-    for (int s = 0; s < BA_D2; ++s) qf[s] = 0.f;
-  }
+  load_half_row<BA_D2, VW>(qb + (size_t)qi * rs + lh * BA_D2, qi < T, qf);
 
-  f32x16 o0, o1;          // O[query erow(e, lh)][d = li] and [d = 32 + li], not yet divided by the row sum
-#pragma unroll
-  for (int e = 0; e < 16; ++e) { o0[e] = 0.f; o1[e] = 0.f; }
+  // O[query tile_row(e, lh)][d = li] and [d = 32 + li], not yet divided by the row sum
+  f32x16 o0 = tile_zero(), o1 = tile_zero();
   float m = -INFINITY, l = 0.f;   // running maximum / sum of query qi (the same value in both lane halves)
 
   const int nt = (n + 31) >> 5;
@@ -93,16 +72,12 @@ __global__ __launch_bounds__(64) void attn_len_fwd_kernel(const BertAttnParams p
     // every tile visited holds at least one valid key (jt * 32 < n), so its maximum is finite
     const int kj = jt * 32 + li;
     float kf[BA_D2];
-    if (kj < n) ba_load_half<VW>(kb + (size_t)kj * rs + lh * BA_D2, kf);
-    else {
-#pragma unroll
-      for (int s = 0; s < BA_D2; ++s) kf[s] = 0.f;
-    }
-    // the tile's v rows, issued ahead of the score product: key erow(e, lh) on the registers, d on the lanes
+    load_half_row<BA_D2, VW>(kb + (size_t)kj * rs + lh * BA_D2, kj < n, kf);
+    // the tile's v rows, issued ahead of the score product: key tile_row(e, lh) on the registers, d on the lanes
     float v0[16], v1[16];
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int j = jt * 32 + ba_erow(e, lh);
+      const int j = jt * 32 + tile_row(e, lh);
       v0[e] = 0.f; v1[e] = 0.f;
       if (j < n) {
         const float* __restrict__ vr = vb + (size_t)j * rs + li;
@@ -110,16 +85,12 @@ __global__ __launch_bounds__(64) void attn_len_fwd_kernel(const BertAttnParams p
       }
     }
 
-    f32x16 a;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) a[e] = 0.f;
-#pragma unroll
-    for (int s = 0; s < BA_D2; ++s) a = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s], qf[s], a, 0, 0, 0);
+    f32x16 a = tile_product<BA_D2>(kf, qf);
 
     float mt = -INFINITY;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int j = jt * 32 + ba_erow(e, lh);
+      const int j = jt * 32 + tile_row(e, lh);
       const float s = (j < n) ? a[e] * p.scale : -INFINITY;
       a[e] = s;
       mt = fmaxf(mt, s);
@@ -138,10 +109,10 @@ __global__ __launch_bounds__(64) void attn_len_fwd_kernel(const BertAttnParams p
     l = l * alpha + ps;
     m = mn;
 
-    // the accumulators carry queries on their registers: the factor of query erow(e, lh) lives in lane erow(e, lh)
+    // the accumulators carry queries on their registers: the factor of query tile_row(e, lh) lives in lane tile_row(e, lh)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const float ar = __shfl(alpha, ba_erow(e, lh), 64);
+      const float ar = __shfl(alpha, tile_row(e, lh), 64);
       o0[e] *= ar; o1[e] *= ar;
     }
     // O += P V: A = the probability tile as it stands (row = query on lanes, k = key on registers / half), B = v rows
@@ -155,8 +126,8 @@ __global__ __launch_bounds__(64) void attn_len_fwd_kernel(const BertAttnParams p
   const float inv = 1.0f / l;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int i = it * 32 + ba_erow(e, lh);
-    const float r = __shfl(inv, ba_erow(e, lh), 64);
+    const int i = it * 32 + tile_row(e, lh);
+    const float r = __shfl(inv, tile_row(e, lh), 64);
     if (i < T) {
       ob[(size_t)i * ors + li] = o0[e] * r;
       ob[(size_t)i * ors + 32 + li] = o1[e] * r;

@@ -8,8 +8,8 @@
 //   F = 2 P R / (P + R), NaN -> 0; an empty text (len == 2) gives P = R = F = 0; F <- (F - b) / (1 - b) with a baseline b
 //
 // One workgroup of four waves per pair (i, j); j is the fast grid axis, so the workgroups in flight share candidate i's
-// states in L2.  S is produced in 32 x 32 tiles on v_mfma_f32_32x32x2_f32 (candidates on the accumulator registers,
-// references on the lanes), the K loop runs over D in chunks of 64 floats that a lane half loads as 16-byte pieces of its
+// states in L2.  S is produced in 32 x 32 tiles on v_mfma_f32_32x32x2_f32 (wave_tile.h: candidates on the accumulator
+// registers, references on the lanes), the K loop runs over D in chunks of 64 floats that a lane half loads as 16-byte pieces of its
 // own row, the next chunk's loads issued ahead of this chunk's 32 products.  Wave w owns the row tiles ti = w, w + 4, ...
 // and walks all column tiles: the running row maxima stay in registers (one value per accumulator element, folded over
 // the lanes once per row tile), the column maxima of a tile go to the wave's own [T] strip in LDS.  One barrier, then a
@@ -23,6 +23,7 @@
 // convention of distill.hip and bertattn.hip); the diagonal is 1 whatever the lengths are.
 #include "common.h"
 #include "kernels.h"
+#include "wave_tile.h"
 
 #include <cstdint>
 
@@ -31,22 +32,6 @@
 #define BS_WAVES 4
 #define BS_KC 64         // floats of a row per K chunk
 #define BS_KH 32         // of which one lane half carries
-
-// row of accumulator register e in lane half lh of a 32 x 32 MFMA result
-__device__ __forceinline__ int bs_erow(int e, int lh) { return (e & 3) + 8 * (e >> 2) + 4 * lh; }
-
-__device__ __forceinline__ void bs_load_half(const float* __restrict__ p, bool ok, float (&r)[BS_KH]) {
-  if (ok) {
-#pragma unroll
-    for (int s = 0; s < BS_KH; s += 4) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(p + s);
-      r[s] = t[0]; r[s + 1] = t[1]; r[s + 2] = t[2]; r[s + 3] = t[3];
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < BS_KH; ++s) r[s] = 0.f;
-  }
-}
 
 __global__ __launch_bounds__(64 * BS_WAVES) void bertscore_kernel(const float* __restrict__ xa, const int* __restrict__ lenA,
                                                                  const float* __restrict__ xb, const int* __restrict__ lenB,
@@ -87,7 +72,7 @@ __global__ __launch_bounds__(64 * BS_WAVES) void bertscore_kernel(const float* _
     const int t = ti * 32 + li;                 // this lane's candidate row (the A operand's row)
     const bool okA = t < la;
     const float* __restrict__ ap = A + (size_t)t * D + lh * BS_KH;
-    float rm[16];                               // max over the columns u = li (mod 32) seen so far of S[erow(e, lh)][u]
+    float rm[16];                               // max over the columns u = li (mod 32) seen so far of S[row of e][u]
 #pragma unroll
     for (int e = 0; e < 16; ++e) rm[e] = -INFINITY;
 
@@ -95,43 +80,40 @@ __global__ __launch_bounds__(64 * BS_WAVES) void bertscore_kernel(const float* _
       const int u = tj * 32 + li;               // this lane's reference row (the B operand's column)
       const bool okB = u < lb;
       const float* __restrict__ bp = B + (size_t)u * D + lh * BS_KH;
-      f32x16 acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.f;
+      f32x16 acc = tile_zero();
       float af[BS_KH], bf[BS_KH], an[BS_KH], bn[BS_KH];
-      bs_load_half(ap, okA, af);
-      bs_load_half(bp, okB, bf);
+      load_half_row<BS_KH, 4>(ap, okA, af);
+      load_half_row<BS_KH, 4>(bp, okB, bf);
       for (int k = 0; k < D; k += BS_KC) {
         const bool more = k + BS_KC < D;        // uniform
         if (more) {
-          bs_load_half(ap + k + BS_KC, okA, an);
-          bs_load_half(bp + k + BS_KC, okB, bn);
+          load_half_row<BS_KH, 4>(ap + k + BS_KC, okA, an);
+          load_half_row<BS_KH, 4>(bp + k + BS_KC, okB, bn);
         }
-#pragma unroll
-        for (int s = 0; s < BS_KH; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(af[s], bf[s], acc, 0, 0, 0);
+        acc = tile_mac<BS_KH>(af, bf, acc);
         if (more) {
 #pragma unroll
           for (int s = 0; s < BS_KH; ++s) { af[s] = an[s]; bf[s] = bn[s]; }
         }
       }
-      // acc[e] = S[ti * 32 + erow(e, lh)][u]
+      // acc[e] = S[ti * 32 + tile_row(e, lh)][u]
       float cm = -INFINITY;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const float sv = acc[e];
         if (okB) rm[e] = fmaxf(rm[e], sv);
-        if (ti * 32 + bs_erow(e, lh) < la) cm = fmaxf(cm, sv);
+        if (ti * 32 + tile_row(e, lh) < la) cm = fmaxf(cm, sv);
       }
       cm = fmaxf(cm, __shfl_xor(cm, 32, 64));
       if (lh == 0 && okB) s_col[wave][u] = fmaxf(s_col[wave][u], cm);
     }
-    // the row maxima over the 32 lanes of a half; lane li == e of half lh then stores row erow(e, lh)
+    // the row maxima over the 32 lanes of a half; lane li == e of half lh then stores row tile_row(e, lh)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       float v = rm[e];
 #pragma unroll
       for (int sh = 16; sh > 0; sh >>= 1) v = fmaxf(v, __shfl_xor(v, sh, 64));
-      const int te = ti * 32 + bs_erow(e, lh);
+      const int te = ti * 32 + tile_row(e, lh);
       if (li == e && te < la) s_row[te] = v;
     }
   }

@@ -24,11 +24,12 @@
 //                                                         37.5 us  (K loop 24.7): no gain over lockstep here
 // The loop runs at ~0.68 of its matrix-pipe time (1 536 MFMA cycles per SIMD and K tile); 192 workgroups use 192 CUs.
 // Within a 16-deep k-group lane group g = lane / 16 feeds k = 4g + j at MFMA step j for BOTH operands (the same
-// permuted-k trick as igemm.hip).  The attention part is the register-resident scheme of attention.hip (transposed
-// scores on v_mfma_f32_32x32x2_f32, probabilities reused as the A operand of P V) reading q, k, v from LDS; waves 0
-// and 1 each produce one 32-column half of the context.  Dropout uses the same counter-based stream (seed, element) as
-// attn_fwd_kernel, so attn_bwd_kernel regenerates the mask unchanged.
+// permuted-k trick as igemm.hip).  The attention part is the register-resident wave-tile scheme of wave_tile.h
+// (transposed scores on v_mfma_f32_32x32x2_f32, probabilities reused as the A operand of P V) reading q, k, v from LDS;
+// waves 0 and 1 each produce one 32-column half of the context.  Dropout is wave_tile.h's AttnDrop, the one stream that
+// attn_fwd_kernel draws from too, so attn_bwd_kernel regenerates the mask unchanged.
 #include "kernels.h"
+#include "wave_tile.h"
 
 namespace {
 
@@ -43,8 +44,6 @@ struct QkvAttnArgs {
   uint32_t seed;
   int dbg;   // timing experiments only (MMVQA_QA_DBG): 1 = no attention part, 2 = one K tile only, 4 = no q/k/v store
 };
-
-__device__ __forceinline__ int erow32(int e, int lh) { return (e & 3) + 8 * (e >> 2) + 4 * lh; }
 
 __global__ __launch_bounds__(512) void qkv_attn_fwd_kernel(const QkvAttnArgs p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -72,7 +71,7 @@ __global__ __launch_bounds__(512) void qkv_attn_fwd_kernel(const QkvAttnArgs p) 
   float mk[16];
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int j = erow32(e, lane >> 5);
+    const int j = tile_row(e, lane >> 5);
     mk[e] = (j < T) ? (float)p.mask[b * T + j] : 1.f;
   }
   f32x4 ra = {0, 0, 0, 0}, rb[3];
@@ -174,55 +173,37 @@ __global__ __launch_bounds__(512) void qkv_attn_fwd_kernel(const QkvAttnArgs p) 
   }
   float vv[16];
 #pragma unroll
-  for (int e = 0; e < 16; ++e) vv[e] = S[erow32(e, lh) * QA_LDS + 128 + dt * 32 + li];
-  f32x16 sc;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) sc[e] = 0.f;
-#pragma unroll
-  for (int s = 0; s < 32; ++s) sc = __builtin_amdgcn_mfma_f32_32x32x2f32(kf[s], qf[s], sc, 0, 0, 0);   // S^T[key][query]
+  for (int e = 0; e < 16; ++e) vv[e] = S[tile_row(e, lh) * QA_LDS + 128 + dt * 32 + li];
+  f32x16 sc[1] = {tile_product<32>(kf, qf)};   // S^T[key][query]
 
   float mx = -INFINITY;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int j = erow32(e, lh);
+    const int j = tile_row(e, lh);
     float s = -INFINITY;
     if (j < T && qvalid) {
-      s = sc[e] * 0.125f;                       // (q.k)/sqrt(64): a power of two, the product IS the quotient; then the mask term
+      s = sc[0][e] * 0.125f;                    // (q.k)/sqrt(64): a power of two, the product IS the quotient; then the mask term
       s = s - 10000.0f * (1.0f - mk[e]);
     }
-    sc[e] = s;
+    sc[0][e] = s;
     mx = fmaxf(mx, s);
   }
-  mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-  float sum = 0.f;
+  const float inv = tile_softmax<1>(sc, mx, qvalid);
+  const AttnDrop drop(p.seed, p.drop_p);
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const float ex = (sc[e] == -INFINITY) ? 0.f : expf(sc[e] - mx);
-    sc[e] = ex;
-    sum += ex;
-  }
-  sum += __shfl_xor(sum, 32, 64);
-  const float inv = qvalid ? 1.0f / sum : 0.f;
-  const float keep_scale = p.drop_p > 0.f ? 1.0f / (1.0f - p.drop_p) : 1.f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int j = erow32(e, lh);
-    float pr = sc[e] * inv;
+    const int j = tile_row(e, lh);
+    float pr = sc[0][e] * inv;
     if (dt == 0 && p.probs && j < T && qvalid) p.probs[((size_t)(b * p.heads + head) * T + j) * T + li] = pr;
-    if (p.drop_p > 0.f) {
-      const float u = rng_uniform(p.seed, (uint32_t)(((b * p.heads + head) * T + li) * T + j));
-      pr = (u >= p.drop_p) ? pr * keep_scale : 0.f;
-    }
-    sc[e] = pr;
+    if (drop.p > 0.f) pr = drop.keep(b * p.heads + head, T, li, j) ? pr * drop.ks : 0.f;
+    sc[0][e] = pr;
   }
-  f32x16 o;
+  f32x16 o = tile_zero();
 #pragma unroll
-  for (int e = 0; e < 16; ++e) o[e] = 0.f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) o = __builtin_amdgcn_mfma_f32_32x32x2f32(sc[e], vv[e], o, 0, 0, 0);   // O[query][d]
+  for (int e = 0; e < 16; ++e) o = __builtin_amdgcn_mfma_f32_32x32x2f32(sc[0][e], vv[e], o, 0, 0, 0);   // O[query][d]
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int i = erow32(e, lh);
+    const int i = tile_row(e, lh);
     if (i < T) p.ctx[(size_t)(b * T + i) * H + head * 64 + dt * 32 + li] = o[e];
   }
 }
