@@ -333,13 +333,15 @@ int mmvqa_maxpool_fwd(mmvqa_stream_t s, const float* z, const float* sc, const f
 int mmvqa_maxpool_bwd(mmvqa_stream_t s, const float* gp, const unsigned char* idx, const float* extra,
                       const float* z, const float* sc, const float* sh, const float* mean, const float* invstd,
                       float* g0, double* stat, int N, int H, int W, int C, int OH, int OW);
-/* LayerNorm over the last axis, optional residual input (y = LN(x + res)) */
+/* LayerNorm over the last axis, optional residual input (y = LN(x + res)).  H must be a multiple of 4 and at most
+ * 1024; forward and backward refuse any other H with MMVQA_ERR_ARG and launch nothing. */
 int mmvqa_layernorm_fwd(mmvqa_stream_t s, const float* x, const float* res, const float* gamma, const float* beta,
                         float* y, float* sum_out, float* mean, float* rstd, int rows, int H, float eps);
 int mmvqa_layernorm_bwd(mmvqa_stream_t s, const float* dy, const float* x, const float* gamma, const float* mean,
                         const float* rstd, const float* dres, float* dx, float* dgamma, float* dbeta, int rows,
                         int H);
-/* HF BertEmbeddings + visual-token overwrite (models/mmbert.py:60-67); vis is [num_vis][B][H] */
+/* HF BertEmbeddings + visual-token overwrite (models/mmbert.py:60-67); vis is [num_vis][B][H].  H as for LayerNorm:
+ * a multiple of 4, at most 1024, refused with MMVQA_ERR_ARG otherwise by the forward and the backward call alike. */
 int mmvqa_embed_fwd(mmvqa_stream_t s, const long long* ids, const long long* seg, const float* word,
                     const float* pos, const float* type, const float* gamma, const float* beta, const float* vis,
                     float* out, float* xhat, float* rstd, int B, int T, int H, int num_vis, float eps,

@@ -1029,6 +1029,7 @@ int k_embed_bwd(hipStream_t st, const float* dout, const long long* ids, const l
                 const float* rstd, const float* gamma, float* dword, float* dpos, float* dtype, float* dgamma,
                 float* dbeta, float* dvis, int B, int T, int H, int num_vis, float drop_p, uint32_t seed,
                 int pad_idx) {
+  if (H % 4 != 0 || H > 256 * LN_MAXV) return mmvqa_set_error(MMVQA_ERR_ARG, "embed: H=%d unsupported", H);
   hipLaunchKernelGGL(embed_bwd_kernel, dim3(cdiv_i((long)B * T, 4)), dim3(256), 0, st, dout, ids, seg, xhat, rstd,
                      gamma, dword, dpos, dtype, dgamma, dbeta, dvis, B, T, H, num_vis, drop_p, seed, pad_idx);
   KERNEL_CHECK_RET();

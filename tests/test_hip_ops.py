@@ -929,7 +929,9 @@ def test_supcon_sizes(N, D):
 
 
 def test_mlm_loss_unaligned_and_upstream_scale():
-    """rows that are not 16-byte aligned take the scalar kernel; the upstream gradient is applied on the device"""
+    """vocabulary sizes that are no multiple of 4: functional._padded copies such logits into an aligned buffer, so they
+    take the float4 kernels with pad columns (the scalar kernel is reached through the ABI in test_hip_chain_ops.py); the
+    upstream gradient is applied on the device"""
     torch.manual_seed(16)
     for V in (50, 1001, 30522):
         lg = (torch.randn(3, 5, V) * 2).requires_grad_(True)
