@@ -46,7 +46,10 @@ __global__ void amp_update_scale_kernel(float* scale, int* growth_tracker, const
   }
 }
 
-int k_amp_unscale(hipStream_t st, float* g, long n, const float* inv_scale, float* found_inf, int mul) {
+extern "C" int mmvqa_amp_unscale(mmvqa_stream_t s, float* g, long n, const float* inv_scale, float* found_inf,
+                                 int mul) {
+  hipStream_t st = (hipStream_t)s;
+  if (!g || !found_inf || (mul && !inv_scale)) return mmvqa_set_error(MMVQA_ERR_ARG, "amp_unscale: null pointer");
   if (n <= 0) return MMVQA_OK;
   long blocks = (n + 1023) / 1024;
   if (blocks > 2048) blocks = 2048;
@@ -55,8 +58,11 @@ int k_amp_unscale(hipStream_t st, float* g, long n, const float* inv_scale, floa
   return MMVQA_OK;
 }
 
-int k_amp_update_scale(hipStream_t st, float* scale, int* growth_tracker, const float* found_inf, double growth_factor,
-                       double backoff_factor, int growth_interval) {
+extern "C" int mmvqa_amp_update_scale(mmvqa_stream_t s, float* scale, int* growth_tracker, const float* found_inf,
+                                      double growth_factor, double backoff_factor, int growth_interval) {
+  hipStream_t st = (hipStream_t)s;
+  if (!scale || !growth_tracker || !found_inf) return mmvqa_set_error(MMVQA_ERR_ARG, "amp_update_scale: null pointer");
+  if (growth_interval <= 0) return mmvqa_set_error(MMVQA_ERR_ARG, "amp_update_scale: growth_interval=%d", growth_interval);
   hipLaunchKernelGGL(amp_update_scale_kernel, dim3(1), dim3(64), 0, st, scale, growth_tracker, found_inf, growth_factor,
                      backoff_factor, growth_interval);
   KERNEL_CHECK_RET();

@@ -350,6 +350,12 @@ static int attn_dispatch(const AttnParams& p, int bwd, hipStream_t st) {
 }
 
 int mmvqa_launch_attention(const AttnParams& p, int head_dim, int bwd, hipStream_t st) {
+  if (!p.q || !p.k || !p.v || !p.mask || !p.probs) return mmvqa_set_error(MMVQA_ERR_ARG, "attention: null operand");
+  if ((p.row_stride & 3) || (p.head_stride & 3) || (p.out_row_stride & 3) || (p.out_head_stride & 3))
+    return mmvqa_set_error(MMVQA_ERR_ARG, "attention: strides must be multiples of 4");
+  if (bwd && (!p.dout || !p.dq || !p.dk || !p.dv))
+    return mmvqa_set_error(MMVQA_ERR_ARG, "attention backward: null gradient pointer");
+  if (!bwd && !p.out) return mmvqa_set_error(MMVQA_ERR_ARG, "attention: null output");
   switch (head_dim) {
     case 8: return attn_dispatch<8>(p, bwd, st);
     case 12: return attn_dispatch<12>(p, bwd, st);
@@ -357,4 +363,9 @@ int mmvqa_launch_attention(const AttnParams& p, int head_dim, int bwd, hipStream
     case 96: return attn_dispatch<96>(p, bwd, st);
     default: return mmvqa_set_error(MMVQA_ERR_ARG, "attention: head_dim=%d unsupported (8,12,64,96)", head_dim);
   }
+}
+
+extern "C" int mmvqa_attention(const mmvqa_attn_desc* d, int head_dim, int backward, mmvqa_stream_t s) {
+  if (!d) return mmvqa_set_error(MMVQA_ERR_ARG, "attention: null operand");
+  return mmvqa_launch_attention(*d, head_dim, backward, (hipStream_t)s);
 }

@@ -135,9 +135,10 @@ __global__ __launch_bounds__(64) void attn_len_fwd_kernel(const BertAttnParams p
   }
 }
 
-int k_attention_len_fwd(hipStream_t st, const float* q, const float* k, const float* v, int row_stride, int head_stride,
-                        float* out, int out_row_stride, int out_head_stride, const int* len, int B, int T, int heads,
-                        float scale) {
+extern "C" int mmvqa_attention_len_fwd(mmvqa_stream_t s, const float* q, const float* k, const float* v, int row_stride,
+                                       int head_stride, float* out, int out_row_stride, int out_head_stride,
+                                       const int* len, int B, int T, int heads, float scale) {
+  hipStream_t st = (hipStream_t)s;
   const char* who = "attention_len_fwd";
   if (!q || !k || !v || !out || !len)
     return mmvqa_set_error(MMVQA_ERR_ARG, "%s: null operand (q, k, v, out and len are required)", who);

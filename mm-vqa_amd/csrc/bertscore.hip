@@ -145,8 +145,10 @@ __global__ __launch_bounds__(64 * BS_WAVES) void bertscore_kernel(const float* _
   }
 }
 
-int k_bertscore_mask(hipStream_t st, const float* xa, const int* lenA, const float* xb, const int* lenB, float* mask,
-                     float* prec, float* rec, int n, int T, int D, float baseline) {
+extern "C" int mmvqa_bertscore_mask(mmvqa_stream_t s, const float* xa, const int* lenA, const float* xb,
+                                    const int* lenB, float* mask, float* prec, float* rec, int n, int T, int D,
+                                    float baseline) {
+  hipStream_t st = (hipStream_t)s;
   const char* who = "bertscore_mask";
   if (!xa || !xb || !lenA || !lenB || !mask)
     return mmvqa_set_error(MMVQA_ERR_ARG, "%s: null operand (xa, lenA, xb, lenB and mask are required)", who);

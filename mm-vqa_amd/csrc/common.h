@@ -226,6 +226,7 @@ __device__ __forceinline__ void bn_coef_block_bwd(const float* __restrict__ P, c
 
 // --------------------------------------------------------------------------- host side
 int mmvqa_set_error(int code, const char* fmt, ...);
+const char* mmvqa_get_error();
 #define MMVQA_OK 0
 #define MMVQA_ERR_ARG -1
 #define MMVQA_ERR_HIP -2
@@ -240,3 +241,10 @@ int mmvqa_set_error(int code, const char* fmt, ...);
   } while (0)
 
 #define KERNEL_CHECK_RET() HIP_CHECK_RET(hipGetLastError())
+
+// early return of a failed call's code (the message is already set)
+#define TRY(x)                     \
+  do {                             \
+    int _r = (x);                  \
+    if (_r != MMVQA_OK) return _r; \
+  } while (0)

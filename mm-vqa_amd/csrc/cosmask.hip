@@ -89,7 +89,8 @@ __global__ void __launch_bounds__(256) cosine_mask_kernel(const float* __restric
   }
 }
 
-int k_normalize_rows(hipStream_t st, float* x, long long rows, int D, float eps) {
+extern "C" int mmvqa_normalize_rows(mmvqa_stream_t s, float* x, long long rows, int D, float eps) {
+  hipStream_t st = (hipStream_t)s;
   if (rows < 1 || D < 1 || D > CM_MAX_D)
     return mmvqa_set_error(MMVQA_ERR_ARG, "normalize_rows: rows=%lld D=%d (rows >= 1, 1 <= D <= %d)", rows, D, CM_MAX_D);
   if (!x) return mmvqa_set_error(MMVQA_ERR_ARG, "normalize_rows: null operand");
@@ -100,8 +101,9 @@ int k_normalize_rows(hipStream_t st, float* x, long long rows, int D, float eps)
   return MMVQA_OK;
 }
 
-int k_cosine_mask(hipStream_t st, const float* table, const int* rowsA, const int* colsA, const int* rowsB,
-                  const int* colsB, float* mask, int n, int D, int table_rows) {
+extern "C" int mmvqa_cosine_mask(mmvqa_stream_t s, const float* table, const int* rowsA, const int* colsA,
+                                 const int* rowsB, const int* colsB, float* mask, int n, int D, int table_rows) {
+  hipStream_t st = (hipStream_t)s;
   if (n < 1 || table_rows < 1 || D < 1 || D > CM_MAX_D)
     return mmvqa_set_error(MMVQA_ERR_ARG, "cosine_mask: n=%d table_rows=%d D=%d (n, table_rows >= 1, 1 <= D <= %d)", n,
                            table_rows, D, CM_MAX_D);

@@ -104,9 +104,10 @@ __global__ void __launch_bounds__(256) distill_mean_kernel(const float* __restri
   if (threadIdx.x == 0) *loss = (float)((double)((red[0] + red[1]) + (red[2] + red[3])) / count);
 }
 
-int k_distill_mse(hipStream_t st, const float* h, int ld, const void* table, int table_f16, long long table_rows,
-                  const long long* start, const int* count, int first, int B, int T, int H, float* row_sq, float* loss,
-                  float* dh, int dld, float gscale) {
+extern "C" int mmvqa_distill_mse(mmvqa_stream_t s, const float* h, int ld, const void* table, int table_f16,
+                                 long long table_rows, const long long* start, const int* count, int first, int B,
+                                 int T, int H, float* row_sq, float* loss, float* dh, int dld, float gscale) {
+  hipStream_t st = (hipStream_t)s;
   const char* who = "mmvqa_distill_mse";
   if (!h || !table || !start || !count || !row_sq || !loss)
     return mmvqa_set_error(MMVQA_ERR_ARG, "%s: null operand (h, table, start, count, row_sq and loss are required)", who);

@@ -854,9 +854,11 @@ static inline int grid_for(long n, int block = 256, int cap = 2048) {
   return (int)g;
 }
 
-int k_bn_coef_fwd(hipStream_t st, const double* stat, int C, double count, float eps, const float* gamma,
-                  const float* beta, float* run_mean, float* run_var, long long* nbt, float momentum, int reps,
-                  int training, float* scale, float* shift, float* mean, float* invstd) {
+extern "C" int mmvqa_bn_coef_fwd(mmvqa_stream_t s, const double* stat, int C, double count, float eps,
+                                 const float* gamma, const float* beta, float* run_mean, float* run_var, long long* nbt,
+                                 float momentum, int reps, int training, float* scale, float* shift, float* mean,
+                                 float* invstd) {
+  hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(bn_coef_fwd_kernel, dim3(cdiv_i(C, 16)), dim3(256), 0, st, stat, C, count, eps, gamma, beta,
                      run_mean, run_var, nbt, pow(1.0 - (double)momentum, (double)reps), reps, training, scale, shift,
                      mean, invstd);   // (1 - momentum)^reps on the host: a double pow() per thread was most of the kernel's math
@@ -916,8 +918,10 @@ __global__ __launch_bounds__(256) void bn_add_relu_fold_kernel(const float* __re
   }
 }
 
-int k_bn_act_add_fold(hipStream_t st, const float* z, const mmvqa_bn_fold* f3, int pre_act, const float* idn,
-                      const mmvqa_bn_fold* fd, int post_act, float* out, long rows, int C) {
+extern "C" int mmvqa_bn_act_add_fold(mmvqa_stream_t s, const float* z, const mmvqa_bn_fold* f3, int pre_act,
+                                     const float* idn, const mmvqa_bn_fold* fd, int post_act, float* out, long rows,
+                                     int C) {
+  hipStream_t st = (hipStream_t)s;
   if (C % 4 != 0 || !f3 || !f3->stat || f3->bwd || (fd && (!fd->stat || fd->bwd || !idn)))
     return mmvqa_set_error(MMVQA_ERR_ARG, "bn_act_add_fold: C=%d must be a multiple of 4 and the folds forward ones", C);
   const int cb = cdiv_i(C, 64);
@@ -941,10 +945,10 @@ int k_bn_act_add_fold(hipStream_t st, const float* z, const mmvqa_bn_fold* f3, i
   return MMVQA_OK;
 }
 
-int k_bn_add_relu_fold(hipStream_t st, const float* z, const mmvqa_bn_fold* f3, const float* idn, const mmvqa_bn_fold* fd,
-                       float* out, long rows, int C) {
-  if (!idn) return mmvqa_set_error(MMVQA_ERR_ARG, "bn_add_relu_fold: no identity tensor");
-  return k_bn_act_add_fold(st, z, f3, ACT_NONE, idn, fd, ACT_RELU, out, rows, C);
+extern "C" int mmvqa_bn_add_relu_fold(mmvqa_stream_t s, const float* z, const mmvqa_bn_fold* f3, const float* idn,
+                                      const mmvqa_bn_fold* fd, float* out, long rows, int C) {
+  if (!z || !idn || !out || !f3) return mmvqa_set_error(MMVQA_ERR_ARG, "bn_add_relu_fold: null operand");
+  return mmvqa_bn_act_add_fold(s, z, f3, ACT_NONE, idn, fd, ACT_RELU, out, rows, C);
 }
 
 int k_bn_coef_fwd_keep(hipStream_t st, const double* stat, int C, double count, float eps, const float* gamma,
@@ -956,46 +960,55 @@ int k_bn_coef_fwd_keep(hipStream_t st, const double* stat, int C, double count, 
   return MMVQA_OK;
 }
 
-int k_bn_coef_bwd(hipStream_t st, const double* stat, int C, double count, const float* gamma, const float* mean,
-                  const float* invstd, int training, float* P, float* Q, float* R, float* dgamma, float* dbeta) {
+extern "C" int mmvqa_bn_coef_bwd(mmvqa_stream_t s, const double* stat, int C, double count, const float* gamma,
+                                 const float* mean, const float* invstd, int training, float* P, float* Q, float* R,
+                                 float* dgamma, float* dbeta) {
+  hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(bn_coef_bwd_kernel, dim3(cdiv_i(C, 16)), dim3(256), 0, st, stat, C, count, gamma, mean,
                      invstd, training, P, Q, R, dgamma, dbeta);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
 
-int k_bn_add_relu(hipStream_t st, const float* z, const float* s, const float* b, const float* idn,
-                  const float* ids, const float* idb, float* out, long rows, int C) {
+extern "C" int mmvqa_bn_add_relu(mmvqa_stream_t s, const float* z, const float* sc, const float* sh, const float* idn,
+                                 const float* ids, const float* idb, float* out, long rows, int C) {
+  hipStream_t st = (hipStream_t)s;
+  if (C & 3) return mmvqa_set_error(MMVQA_ERR_ARG, "bn_add_relu: C %% 4 != 0");
   long n4 = rows * C / 4;
-  hipLaunchKernelGGL(bn_add_relu_kernel, dim3(grid_for(n4)), dim3(256), 0, st, z, s, b, idn, ids, idb, out, n4,
+  hipLaunchKernelGGL(bn_add_relu_kernel, dim3(grid_for(n4)), dim3(256), 0, st, z, sc, sh, idn, ids, idb, out, n4,
                      C / 4);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
 
-int k_maxpool_fwd(hipStream_t st, const float* z, const float* s, const float* b, float* out, unsigned char* idx,
-                  int N, int H, int W, int C, int OH, int OW) {
+extern "C" int mmvqa_maxpool_fwd(mmvqa_stream_t s, const float* z, const float* sc, const float* sh, float* out,
+                                 unsigned char* idx, int N, int H, int W, int C, int OH, int OW) {
+  hipStream_t st = (hipStream_t)s;
+  if (C & 3) return mmvqa_set_error(MMVQA_ERR_ARG, "maxpool: C %% 4 != 0");
   long total = (long)N * OH * OW * C / 4;
-  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, st, z, s, b, out, idx, N, H, W, C,
+  hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid_for(total)), dim3(256), 0, st, z, sc, sh, out, idx, N, H, W, C,
                      OH, OW);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
 
-int k_maxpool_bwd(hipStream_t st, const float* gp, const unsigned char* idx, const float* extra, const float* z,
-                  const float* s, const float* b, const float* mean, const float* invstd, float* g0, double* stat,
-                  int N, int H, int W, int C, int OH, int OW) {
+extern "C" int mmvqa_maxpool_bwd(mmvqa_stream_t s, const float* gp, const unsigned char* idx, const float* extra,
+                                 const float* z, const float* sc, const float* sh, const float* mean, const float* invstd,
+                                 float* g0, double* stat, int N, int H, int W, int C, int OH, int OW) {
+  hipStream_t st = (hipStream_t)s;
   if (C % 4 != 0 || 256 % (C / 4) != 0)
     return mmvqa_set_error(MMVQA_ERR_ARG, "maxpool_bwd: C/4 must divide 256 (C=%d)", C);
   long total = (long)N * H * W * C / 4;
-  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total, 256, 1024)), dim3(256), 0, st, gp, idx, extra, z, s,
-                     b, mean, invstd, g0, stat, N, H, W, C, OH, OW);
+  hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(grid_for(total, 256, 1024)), dim3(256), 0, st, gp, idx, extra, z, sc,
+                     sh, mean, invstd, g0, stat, N, H, W, C, OH, OW);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
 
-int k_layernorm_fwd(hipStream_t st, const float* x, const float* res, const float* gamma, const float* beta,
-                    float* y, float* sum_out, float* mean, float* rstd, int rows, int H, float eps) {
+extern "C" int mmvqa_layernorm_fwd(mmvqa_stream_t s, const float* x, const float* res, const float* gamma,
+                                   const float* beta, float* y, float* sum_out, float* mean, float* rstd, int rows,
+                                   int H, float eps) {
+  hipStream_t st = (hipStream_t)s;
   if (H % 4 != 0 || H > 256 * LN_MAXV) return mmvqa_set_error(MMVQA_ERR_ARG, "layernorm: H=%d unsupported", H);
   hipLaunchKernelGGL(layernorm_fwd_kernel, dim3(cdiv_i(rows, 4)), dim3(256), 0, st, x, res, gamma, beta, y,
                      sum_out, mean, rstd, rows, H, eps);
@@ -1003,8 +1016,10 @@ int k_layernorm_fwd(hipStream_t st, const float* x, const float* res, const floa
   return MMVQA_OK;
 }
 
-int k_layernorm_bwd(hipStream_t st, const float* dy, const float* x, const float* gamma, const float* mean,
-                    const float* rstd, const float* dres, float* dx, float* dgamma, float* dbeta, int rows, int H) {
+extern "C" int mmvqa_layernorm_bwd(mmvqa_stream_t s, const float* dy, const float* x, const float* gamma,
+                                   const float* mean, const float* rstd, const float* dres, float* dx, float* dgamma,
+                                   float* dbeta, int rows, int H) {
+  hipStream_t st = (hipStream_t)s;
   if (H % 4 != 0 || H > 256 * LN_MAXV) return mmvqa_set_error(MMVQA_ERR_ARG, "layernorm: H=%d unsupported", H);
   int rpw = rows >= 2048 ? 4 : (rows >= 512 ? 2 : 1);
   int grid = cdiv_i(rows, 4 * rpw);
@@ -1014,10 +1029,11 @@ int k_layernorm_bwd(hipStream_t st, const float* dy, const float* x, const float
   return MMVQA_OK;
 }
 
-int k_embed_fwd(hipStream_t st, const long long* ids, const long long* seg, const float* word, const float* pos,
-                const float* type, const float* gamma, const float* beta, const float* vis, float* out,
-                float* xhat, float* rstd, int B, int T, int H, int num_vis, float eps, float drop_p,
-                uint32_t seed) {
+extern "C" int mmvqa_embed_fwd(mmvqa_stream_t s, const long long* ids, const long long* seg, const float* word,
+                               const float* pos, const float* type, const float* gamma, const float* beta,
+                               const float* vis, float* out, float* xhat, float* rstd, int B, int T, int H, int num_vis,
+                               float eps, float drop_p, uint32_t seed) {
+  hipStream_t st = (hipStream_t)s;
   if (H % 4 != 0 || H > 256 * LN_MAXV) return mmvqa_set_error(MMVQA_ERR_ARG, "embed: H=%d unsupported", H);
   hipLaunchKernelGGL(embed_fwd_kernel, dim3(cdiv_i((long)B * T, 4)), dim3(256), 0, st, ids, seg, word, pos, type,
                      gamma, beta, vis, out, xhat, rstd, B, T, H, num_vis, eps, drop_p, seed);
@@ -1025,10 +1041,11 @@ int k_embed_fwd(hipStream_t st, const long long* ids, const long long* seg, cons
   return MMVQA_OK;
 }
 
-int k_embed_bwd(hipStream_t st, const float* dout, const long long* ids, const long long* seg, const float* xhat,
-                const float* rstd, const float* gamma, float* dword, float* dpos, float* dtype, float* dgamma,
-                float* dbeta, float* dvis, int B, int T, int H, int num_vis, float drop_p, uint32_t seed,
-                int pad_idx) {
+extern "C" int mmvqa_embed_bwd(mmvqa_stream_t s, const float* dout, const long long* ids, const long long* seg,
+                               const float* xhat, const float* rstd, const float* gamma, float* dword, float* dpos,
+                               float* dtype, float* dgamma, float* dbeta, float* dvis, int B, int T, int H, int num_vis,
+                               float drop_p, uint32_t seed, int pad_idx) {
+  hipStream_t st = (hipStream_t)s;
   if (H % 4 != 0 || H > 256 * LN_MAXV) return mmvqa_set_error(MMVQA_ERR_ARG, "embed: H=%d unsupported", H);
   hipLaunchKernelGGL(embed_bwd_kernel, dim3(cdiv_i((long)B * T, 4)), dim3(256), 0, st, dout, ids, seg, xhat, rstd,
                      gamma, dword, dpos, dtype, dgamma, dbeta, dvis, B, T, H, num_vis, drop_p, seed, pad_idx);
@@ -1036,13 +1053,16 @@ int k_embed_bwd(hipStream_t st, const float* dout, const long long* ids, const l
   return MMVQA_OK;
 }
 
-int k_meanpool_fwd(hipStream_t st, const float* h, const long long* mask, float* out, int B, int T, int H) {
+extern "C" int mmvqa_meanpool_fwd(mmvqa_stream_t s, const float* h, const long long* mask, float* out, int B, int T,
+                                  int H) {
+  hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(meanpool_fwd_kernel, dim3(B), dim3(256), 0, st, h, mask, out, B, T, H);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
-int k_meanpool_bwd(hipStream_t st, const float* dout, const long long* mask, float* dh, int B, int T, int H,
-                   int accumulate) {
+extern "C" int mmvqa_meanpool_bwd(mmvqa_stream_t s, const float* dout, const long long* mask, float* dh, int B, int T,
+                                  int H, int accumulate) {
+  hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(meanpool_bwd_kernel, dim3(B), dim3(256), 0, st, dout, mask, dh, B, T, H, accumulate);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
@@ -1051,8 +1071,10 @@ int k_meanpool_bwd(hipStream_t st, const float* dout, const long long* mask, flo
 static bool lsm_fast_ok(const float* logits, int ld, int V) {
   return ((uintptr_t)logits & 15) == 0 && (ld & 3) == 0 && ld >= ((V + 3) & ~3);
 }
-int k_lsm_grad(hipStream_t st, const float* logits, int ld, const long long* target, const float* row_lse,
-               float* dlogits, int dld, const float* gscale_ptr, float gscale_mul, int rows, int V) {
+extern "C" int mmvqa_mlm_grad(mmvqa_stream_t s, const float* logits, int ld, const long long* target,
+                              const float* row_lse, float* dlogits, int dld, const float* gscale_ptr, float gscale_mul,
+                              int rows, int V) {
+  hipStream_t st = (hipStream_t)s;
   if (!lsm_fast_ok(logits, ld, V) || !lsm_fast_ok(dlogits, dld, V))
     return mmvqa_set_error(MMVQA_ERR_ARG, "mlm_grad: logits/dlogits rows must be 16-byte aligned with ld >= round_up(V,4)");
   hipLaunchKernelGGL(lsm_grad_kernel, dim3(rows, cdiv_i((V + 3) >> 2, 256 * LSM_U)), dim3(256), 0, st, logits, ld, target,
@@ -1060,14 +1082,15 @@ int k_lsm_grad(hipStream_t st, const float* logits, int ld, const long long* tar
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
-int k_lsm_nll(hipStream_t st, const float* logits, int ld, const long long* target, float* row_loss, float* row_lse,
-              long long* pred, float* dlogits, int dld, const float* gscale_ptr, float gscale_mul, int rows, int V,
-              float* out3) {
+extern "C" int mmvqa_mlm_loss(mmvqa_stream_t s, const float* logits, int ld, const long long* target, float* row_loss,
+                              float* row_lse, long long* pred, float* dlogits, int dld, const float* gscale_ptr,
+                              float gscale_mul, int rows, int V, float* out3) {
+  hipStream_t st = (hipStream_t)s;
   if (row_lse && lsm_fast_ok(logits, ld, V) && (!dlogits || lsm_fast_ok(dlogits, dld, V))) {
     hipLaunchKernelGGL(lsm_stats_kernel, dim3(rows), dim3(1024), 0, st, logits, ld, target, row_loss, row_lse, pred, V);
     KERNEL_CHECK_RET();
     if (dlogits) {
-      int r = k_lsm_grad(st, logits, ld, target, row_lse, dlogits, dld, gscale_ptr, gscale_mul, rows, V);
+      int r = mmvqa_mlm_grad(st, logits, ld, target, row_lse, dlogits, dld, gscale_ptr, gscale_mul, rows, V);
       if (r != MMVQA_OK) return r;
     }
   } else {   // unaligned rows: scalar three-pass form
@@ -1082,27 +1105,33 @@ int k_lsm_nll(hipStream_t st, const float* logits, int ld, const long long* targ
   return MMVQA_OK;
 }
 
-int k_asl(hipStream_t st, const float* logits, int ld, const long long* target, float* row_loss, float* dlogits,
-          int dld, int rows, int C, float gpos, float gneg, float eps, float gscale) {
+extern "C" int mmvqa_asl_loss(mmvqa_stream_t s, const float* logits, int ld, const long long* target, float* row_loss,
+                              float* dlogits, int dld, int rows, int C, float gpos, float gneg, float eps,
+                              float gscale) {
+  hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(asl_kernel, dim3(rows), dim3(256), 0, st, logits, ld, target, row_loss, dlogits, dld, C, gpos,
                      gneg, eps, gscale);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
 
-int k_l2norm_fwd(hipStream_t st, const float* x, float* y, float* nrm, int rows, int D) {
+extern "C" int mmvqa_l2norm_fwd(mmvqa_stream_t s, const float* x, float* y, float* nrm, int rows, int D) {
+  hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(l2norm_fwd_kernel, dim3(cdiv_i(rows, 4)), dim3(256), 0, st, x, y, nrm, rows, D);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
-int k_l2norm_bwd(hipStream_t st, const float* dy, const float* y, const float* nrm, float* dx, int rows, int D) {
+extern "C" int mmvqa_l2norm_bwd(mmvqa_stream_t s, const float* dy, const float* y, const float* nrm, float* dx,
+                                int rows, int D) {
+  hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(l2norm_bwd_kernel, dim3(cdiv_i(rows, 4)), dim3(256), 0, st, dy, y, nrm, dx, rows, D);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
 
-int k_adam(hipStream_t st, float* p, float* g, float* m, float* v, long n, double lr, double b1, double b2, double eps,
-           int step, float gscale, int zero_grad) {
+extern "C" int mmvqa_adam(mmvqa_stream_t s, float* p, float* g, float* m, float* v, long n, double lr, double b1,
+                          double b2, double eps, int step, float gscale, int zero_grad) {
+  hipStream_t st = (hipStream_t)s;
   if (n % 4 != 0) return mmvqa_set_error(MMVQA_ERR_ARG, "adam: n must be a multiple of 4");
   // bias corrections and (1 - beta) in double, as torch.optim.Adam computes them from Python floats
   const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
@@ -1122,20 +1151,23 @@ int k_adam(hipStream_t st, float* p, float* g, float* m, float* v, long n, doubl
   return MMVQA_OK;
 }
 
-int k_axpy(hipStream_t st, float* y, const float* x, float a, long n) {
+extern "C" int mmvqa_axpy(mmvqa_stream_t s, float* y, const float* x, float a, long n) {
+  hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(axpy_kernel, dim3(grid_for(n)), dim3(256), 0, st, y, x, a, n);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
 
-int k_colsum(hipStream_t st, const float* x, int ld, int rows, int cols, float* out) {
+extern "C" int mmvqa_colsum(mmvqa_stream_t s, const float* x, int ld, int rows, int cols, float* out) {
+  hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(colsum_kernel, dim3(cdiv_i(cols, 256), cdiv_i(rows, 64)), dim3(256), 0, st, x, ld, rows, cols,
                      out);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
 
-int k_dropout(hipStream_t st, float* x, long n, float p, uint32_t seed) {
+extern "C" int mmvqa_dropout(mmvqa_stream_t s, float* x, long n, float p, uint32_t seed) {
+  hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(dropout_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, n, p, seed);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
@@ -1154,7 +1186,10 @@ __global__ void pixmask_kernel(int* out, int total, int OH, int OW, int SH, int 
   out[m] = (int)mk;
 }
 
-int k_pixmask(hipStream_t st, int* out, int N, int OH, int OW, int SH, int SW, int KH, int KW, int stride, int pad) {
+extern "C" int mmvqa_pixmask(mmvqa_stream_t s, int* out, int N, int OH, int OW, int SH, int SW, int KH, int KW,
+                             int stride, int pad) {
+  hipStream_t st = (hipStream_t)s;
+  if (!out) return mmvqa_set_error(MMVQA_ERR_ARG, "pixmask: null output");
   if (KH * KW > 32) return mmvqa_set_error(MMVQA_ERR_ARG, "pixmask: at most 32 taps");
   const int total = N * OH * OW;
   if (total <= 0) return MMVQA_OK;
@@ -1163,7 +1198,8 @@ int k_pixmask(hipStream_t st, int* out, int N, int OH, int OW, int SH, int SW, i
   return MMVQA_OK;
 }
 
-int k_dropout_copy(hipStream_t st, const float* x, float* y, long n, float p, uint32_t seed) {
+extern "C" int mmvqa_dropout_copy(mmvqa_stream_t s, const float* x, float* y, long n, float p, uint32_t seed) {
+  hipStream_t st = (hipStream_t)s;
   hipLaunchKernelGGL(dropout_copy_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, y, n, p, seed);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
@@ -1709,10 +1745,12 @@ static inline int pix_grid(long npix, int cgroups) {
   return (int)(g < 1 ? 1 : g);
 }
 
-int k_bn_act_add(hipStream_t st, const float* z, const float* s, const float* b, int pre_act, const float* idn,
-                 const float* ids, const float* idb, int idn_act, int post_act, float* out, long rows, int C) {
+extern "C" int mmvqa_bn_act_add(mmvqa_stream_t s, const float* z, const float* sc, const float* sh, int pre_act,
+                                const float* idn, const float* ids, const float* idb, int idn_act, int post_act,
+                                float* out, long rows, int C) {
+  hipStream_t st = (hipStream_t)s;
   long n4 = rows * C / 4;
-  hipLaunchKernelGGL(bn_act_add_kernel, dim3(grid_for(n4)), dim3(256), 0, st, z, s, b, pre_act, idn, ids, idb,
+  hipLaunchKernelGGL(bn_act_add_kernel, dim3(grid_for(n4)), dim3(256), 0, st, z, sc, sh, pre_act, idn, ids, idb,
                      idn_act, post_act, out, n4, C / 4);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
@@ -1723,8 +1761,10 @@ static bool dw_pixel_form() {   // A/B switch: the pixel-strided kernels even wh
   return v;
 }
 
-int k_dwconv_fwd(hipStream_t st, const float* z1, const float* s1, const float* b1, const float* w, float* z2,
-                 double* stat, int N, int H, int W, int C, int OH, int OW, int stride, int pad, const mmvqa_bn_fold* fold) {
+extern "C" int mmvqa_dwconv_fwd_fold(mmvqa_stream_t s, const float* z1, const float* s1, const float* b1,
+                                     const float* w, float* z2, double* stat, int N, int H, int W, int C, int OH,
+                                     int OW, int stride, int pad, const mmvqa_bn_fold* fold) {
+  hipStream_t st = (hipStream_t)s;
   if (C % 32) return mmvqa_set_error(MMVQA_ERR_ARG, "dwconv: C=%d must be a multiple of 32", C);
   if (fold && (!fold->stat || fold->bwd)) return mmvqa_set_error(MMVQA_ERR_ARG, "dwconv: the fold must be a forward one");
   mmvqa_bn_fold f1;
@@ -1743,11 +1783,17 @@ int k_dwconv_fwd(hipStream_t st, const float* z1, const float* s1, const float* 
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
+extern "C" int mmvqa_dwconv_fwd(mmvqa_stream_t s, const float* z1, const float* s1, const float* b1, const float* w, float* z2,
+                                double* stat, int N, int H, int W, int C, int OH, int OW, int stride, int pad) {
+  return mmvqa_dwconv_fwd_fold(s, z1, s1, b1, w, z2, stat, N, H, W, C, OH, OW, stride, pad, nullptr);
+}
 
-int k_dwconv_bwd_data(hipStream_t st, const float* g2, const float* z2, const float* P, const float* Q,
-                      const float* R, const float* w, const float* z1, const float* s1, const float* b1,
-                      const float* mean1, const float* invstd1, float* g1, double* stat, int N, int H, int W, int C,
-                      int OH, int OW, int stride, int pad, const mmvqa_bn_fold* fold) {
+extern "C" int mmvqa_dwconv_bwd_data_fold(mmvqa_stream_t s, const float* g2, const float* z2, const float* P,
+                                          const float* Q, const float* R, const float* w, const float* z1,
+                                          const float* s1, const float* b1, const float* mean1, const float* invstd1,
+                                          float* g1, double* stat, int N, int H, int W, int C, int OH, int OW,
+                                          int stride, int pad, const mmvqa_bn_fold* fold) {
+  hipStream_t st = (hipStream_t)s;
   if (C % 32) return mmvqa_set_error(MMVQA_ERR_ARG, "dwconv: C=%d must be a multiple of 32", C);
   if (fold && (!fold->stat || !fold->bwd)) return mmvqa_set_error(MMVQA_ERR_ARG, "dwconv_bwd_data: the fold must be a backward one");
   mmvqa_bn_fold f2;
@@ -1766,10 +1812,19 @@ int k_dwconv_bwd_data(hipStream_t st, const float* g2, const float* z2, const fl
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
+extern "C" int mmvqa_dwconv_bwd_data(mmvqa_stream_t s, const float* g2, const float* z2, const float* P, const float* Q,
+                                     const float* R, const float* w, const float* z1, const float* s1, const float* b1,
+                                     const float* mean1, const float* invstd1, float* g1, double* stat, int N, int H, int W,
+                                     int C, int OH, int OW, int stride, int pad) {
+  return mmvqa_dwconv_bwd_data_fold(s, g2, z2, P, Q, R, w, z1, s1, b1, mean1, invstd1, g1, stat, N, H, W, C, OH, OW, stride, pad,
+                                    nullptr);
+}
 
-int k_dwconv_bwd_weight(hipStream_t st, const float* g2, const float* z2, const float* P, const float* Q,
-                        const float* R, const float* z1, const float* s1, const float* b1, float* dw, int N, int H,
-                        int W, int C, int OH, int OW, int stride, int pad, const mmvqa_bn_fold* fold) {
+extern "C" int mmvqa_dwconv_bwd_weight_fold(mmvqa_stream_t s, const float* g2, const float* z2, const float* P,
+                                            const float* Q, const float* R, const float* z1, const float* s1,
+                                            const float* b1, float* dw, int N, int H, int W, int C, int OH, int OW,
+                                            int stride, int pad, const mmvqa_bn_fold* fold) {
+  hipStream_t st = (hipStream_t)s;
   if (C % 32) return mmvqa_set_error(MMVQA_ERR_ARG, "dwconv: C=%d must be a multiple of 32", C);
   if (fold && (!fold->stat || !fold->bwd)) return mmvqa_set_error(MMVQA_ERR_ARG, "dwconv_bwd_weight: the fold must be a backward one");
   mmvqa_bn_fold f2;
@@ -1790,15 +1845,25 @@ int k_dwconv_bwd_weight(hipStream_t st, const float* g2, const float* z2, const 
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
+extern "C" int mmvqa_dwconv_bwd_weight(mmvqa_stream_t s, const float* g2, const float* z2, const float* P, const float* Q,
+                                       const float* R, const float* z1, const float* s1, const float* b1, float* dw, int N, int H,
+                                       int W, int C, int OH, int OW, int stride, int pad) {
+  return mmvqa_dwconv_bwd_weight_fold(s, g2, z2, P, Q, R, z1, s1, b1, dw, N, H, W, C, OH, OW, stride, pad, nullptr);
+}
 
-int k_se_pool(hipStream_t st, const float* z, const float* s, const float* b, float* pool, int N, int HW, int C,
-              const mmvqa_bn_fold* fold) {
+extern "C" int mmvqa_se_pool_fold(mmvqa_stream_t s, const float* z, const float* sc, const float* sh, float* pool, int N,
+                                  int HW, int C, const mmvqa_bn_fold* fold) {
+  hipStream_t st = (hipStream_t)s;
   if (fold && (!fold->stat || fold->bwd || C % 4)) return mmvqa_set_error(MMVQA_ERR_ARG, "se_pool: the fold must be a forward one and C a multiple of 4");
   mmvqa_bn_fold f;
   if (fold) f = *fold; else memset(&f, 0, sizeof(f));
-  hipLaunchKernelGGL(se_pool_kernel, dim3(cdiv_i(C, 64), N), dim3(256), 0, st, z, s, b, f, pool, HW, C);
+  hipLaunchKernelGGL(se_pool_kernel, dim3(cdiv_i(C, 64), N), dim3(256), 0, st, z, sc, sh, f, pool, HW, C);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
+}
+extern "C" int mmvqa_se_pool(mmvqa_stream_t s, const float* z, const float* sc, const float* sh, float* pool, int N, int HW,
+                             int C) {
+  return mmvqa_se_pool_fold(s, z, sc, sh, pool, N, HW, C, nullptr);
 }
 
 int k_se_dgate(hipStream_t st, const float* t, const float* z, const float* s, const float* b, float* dgate, int N,
@@ -1807,13 +1872,18 @@ int k_se_dgate(hipStream_t st, const float* t, const float* z, const float* s, c
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
+extern "C" int mmvqa_se_dgate(mmvqa_stream_t s, const float* t, const float* z, const float* sc, const float* sh, float* dgate,
+                              int N, int HW, int C) {
+  return k_se_dgate((hipStream_t)s, t, z, sc, sh, dgate, N, HW, C, nullptr, 0);
+}
 
-int k_act_bwd_stats(hipStream_t st, const float* t, const float* gate, const float* add, const float* z,
-                    const float* s, const float* b, const float* mean, const float* invstd, int act, float* out,
-                    double* stat, long npix, int HW, int C) {
+extern "C" int mmvqa_act_bwd_stats(mmvqa_stream_t s, const float* t, const float* gate, const float* add,
+                                   const float* z, const float* sc, const float* sh, const float* mean,
+                                   const float* invstd, int act, float* out, double* stat, long npix, int HW, int C) {
+  hipStream_t st = (hipStream_t)s;
   if (C % 4) return mmvqa_set_error(MMVQA_ERR_ARG, "act_bwd_stats: C=%d must be a multiple of 4", C);
   const int cg = (C + 31) / 32;
-  hipLaunchKernelGGL(act_bwd_stats_kernel, dim3(pix_grid(npix, cg), cg), dim3(256), 0, st, t, gate, add, z, s, b,
+  hipLaunchKernelGGL(act_bwd_stats_kernel, dim3(pix_grid(npix, cg), cg), dim3(256), 0, st, t, gate, add, z, sc, sh,
                      mean, invstd, act, out, stat, npix, HW, C);
   KERNEL_CHECK_RET();
   return MMVQA_OK;

@@ -23,12 +23,6 @@ int mmvqa_set_error(int code, const char* fmt, ...) {
 }
 const char* mmvqa_get_error() { return g_err; }
 
-#define TRY(x)                    \
-  do {                            \
-    int _r = (x);                 \
-    if (_r != MMVQA_OK) return _r; \
-  } while (0)
-
 // --------------------------------------------------------------------------- parameter table
 namespace {
 
@@ -349,7 +343,7 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
         blk.rpre = a.f((size_t)B * blk.rd); blk.r = a.f((size_t)B * blk.rd);
         max_mid = std::max(max_mid, std::max(Min, Mout) * blk.mid);
         max_se = std::max(max_se, (size_t)B * blk.mid);
-        max_separt = std::max(max_separt, k_se_fc_bwd_scratch_floats(B, blk.mid, blk.rd));
+        max_separt = std::max(max_separt, mmvqa_se_fc_bwd_scratch_floats(B, blk.mid, blk.rd));
         if (!k_se_fc_bwd_ok(blk.rd)) {   // refuse here, not at the first backward
           mmvqa_set_error(MMVQA_ERR_ARG, "plan: squeeze-excite reduce width %d exceeds what se_fc_bwd supports", blk.rd);
           return 0;
@@ -629,20 +623,20 @@ static int lin_wgrad(mmvqa_engine* e, hipStream_t st, const float* dy, int dy_ld
   g.B = x; g.b_ld = x_ld; g.g_Cs = L.in;
   g.C = GRD(L.w); g.c_ld = L.in; g.c_atomic = 1;
   RUN(PROF_IGEMM, 2.0 * M * L.out * L.in, mmvqa_launch_igemm(g, KIND_WGRAD, 0, 0, st));
-  if (bias_from_colsum && L.b >= 0) RUN(PROF_OTHER, 0, k_colsum(st, dy, dy_ld, (int)M, L.out, GRD(L.b)));
+  if (bias_from_colsum && L.b >= 0) RUN(PROF_OTHER, 0, mmvqa_colsum(st, dy, dy_ld, (int)M, L.out, GRD(L.b)));
   return MMVQA_OK;
 }
 
 static int ln_fwd(mmvqa_engine* e, hipStream_t st, const float* x, const LNRef& ln, float* y, float* mean,
                   float* rstd, long rows, float eps) {
-  RUNB(HB_LAYERNORM_FWD, 8.0 * rows * e->d.hidden, k_layernorm_fwd(st, x, nullptr, PRM(ln.g), PRM(ln.b), y, nullptr, mean, rstd, (int)rows,
+  RUNB(HB_LAYERNORM_FWD, 8.0 * rows * e->d.hidden, mmvqa_layernorm_fwd(st, x, nullptr, PRM(ln.g), PRM(ln.b), y, nullptr, mean, rstd, (int)rows,
                                      e->d.hidden, eps));
   return MMVQA_OK;
 }
 static int ln_bwd(mmvqa_engine* e, hipStream_t st, const float* dy, const float* x, const LNRef& ln,
                   const float* mean, const float* rstd, const float* dres, float* dx, long rows, bool data_only = false) {
   // data_only (mmvqa_engine_backward_feature): the gradient with respect to x alone, dgamma / dbeta are not accumulated
-  RUNB(HB_LAYERNORM_BWD, (dres ? 16.0 : 12.0) * rows * e->d.hidden, k_layernorm_bwd(st, dy, x, PRM(ln.g), mean, rstd, dres, dx,
+  RUNB(HB_LAYERNORM_BWD, (dres ? 16.0 : 12.0) * rows * e->d.hidden, mmvqa_layernorm_bwd(st, dy, x, PRM(ln.g), mean, rstd, dres, dx,
                                      data_only ? nullptr : GRD(ln.g), data_only ? nullptr : GRD(ln.b), (int)rows,
                                      e->d.hidden));
   return MMVQA_OK;
@@ -658,7 +652,7 @@ static void conv_geom(GemmParams& g, const ConvRef& c, int SH, int SW, int Cs, i
 static int bn_coef_fwd(mmvqa_engine* e, hipStream_t st, BNRef& bn) {
   REG(REG_BNCOEF);
   RUN(PROF_OTHER, 0,
-      k_bn_coef_fwd(st, stat_ptr(e, bn.stat_f), bn.C, bn.count, bn.eps, PRM(bn.gamma), PRM(bn.beta),
+      mmvqa_bn_coef_fwd(st, stat_ptr(e, bn.stat_f), bn.C, bn.count, bn.eps, PRM(bn.gamma), PRM(bn.beta),
                     e->bufs + bn.rmean, e->bufs + bn.rvar, e->nbt + bn.nbt, 0.1f, bn.reps, e->training,
                     WS(bn.scale), WS(bn.shift), WS(bn.mean), WS(bn.invstd)));
   return MMVQA_OK;
@@ -666,7 +660,7 @@ static int bn_coef_fwd(mmvqa_engine* e, hipStream_t st, BNRef& bn) {
 static int bn_coef_bwd(mmvqa_engine* e, hipStream_t st, BNRef& bn) {
   REG(REG_BNCOEF);
   RUN(PROF_OTHER, 0,
-      k_bn_coef_bwd(st, stat_ptr(e, bn.stat_b), bn.C, bn.count, PRM(bn.gamma), WS(bn.mean), WS(bn.invstd),
+      mmvqa_bn_coef_bwd(st, stat_ptr(e, bn.stat_b), bn.C, bn.count, PRM(bn.gamma), WS(bn.mean), WS(bn.invstd),
                     e->training, WS(bn.P), WS(bn.Q), WS(bn.R), GRD(bn.gamma), GRD(bn.beta)));
   return MMVQA_OK;
 }
@@ -805,7 +799,7 @@ static int tap_act(const mmvqa_engine* e) { return e->d.use_relu ? ACT_RELU : AC
 // (fp32 operands: not in the f16 mode, whose contract rounds every tap product's operands -- the implicit GEMM)
 static bool tap_is_thin(const mmvqa_engine* e, const TapRef& t) {
   static const bool thin_off = getenv("MMVQA_NO_TAP_THIN") != nullptr;   // A/B switch
-  return !thin_off && e->prec == MMVQA_PREC_F32 && t.C <= 32 && k_tap_thin_ok(t.M, e->d.hidden, t.C, t.HW);
+  return !thin_off && e->prec == MMVQA_PREC_F32 && t.C <= 32 && mmvqa_tap_thin_ok(t.M, e->d.hidden, t.C, t.HW);
 }
 
 // u = act(fmap W_tap^T), consumed by the epilogue: EPI_TAP_FWD pools it into the visual token, EPI_TAP_BWD turns it into du.
@@ -828,7 +822,7 @@ static int tap_fwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
   float* vis = WS(e->vis) + (size_t)k * e->B * e->d.hidden;
   if (tap_is_thin(e, t)) {
     TRY(prof_begin(e, st, PROF_MATRIX, 2.0 * (double)t.M * e->d.hidden * t.C, HB_TAP_THIN_FWD, 4.0 * (double)t.M * t.C));
-    TRY(k_tap_thin_fwd(st, fmap, bn_in ? WS(bn_in->scale) : nullptr, bn_in ? WS(bn_in->shift) : nullptr,
+    TRY(mmvqa_tap_thin_fwd(st, fmap, bn_in ? WS(bn_in->scale) : nullptr, bn_in ? WS(bn_in->shift) : nullptr,
                                       PRM(t.w), vis, t.M, e->d.hidden, t.C, t.HW, tap_act(e)));
     TRY(prof_end(e, st));
     return MMVQA_OK;
@@ -850,7 +844,7 @@ static int tap_bwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
   const float* dv = WS(e->dvis) + (size_t)k * e->B * Hd;
   if (tap_is_thin(e, t)) {
     TRY(prof_begin(e, st, PROF_MATRIX, 2.0 * (double)t.M * Hd * t.C, HB_TAP_THIN_BWD, 4.0 * (double)t.M * (t.C + Hd)));
-    TRY(k_tap_thin_bwd(st, fmap, bn_in ? WS(bn_in->scale) : nullptr, bn_in ? WS(bn_in->shift) : nullptr,
+    TRY(mmvqa_tap_thin_bwd(st, fmap, bn_in ? WS(bn_in->scale) : nullptr, bn_in ? WS(bn_in->shift) : nullptr,
                        PRM(t.w), dv, WS(e->du), t.M, Hd, t.C, t.HW, tap_act(e)));
     TRY(prof_end(e, st));
   } else {
@@ -1047,7 +1041,7 @@ static int resnet_forward(mmvqa_engine* e, hipStream_t st) {
   } else {
     pend_tap = 4; pend_x = WS(e->z0); pend_bn = &e->stem_bn;
   }
-  RUNB(HB_MAXPOOL_FWD, 4.0 * B * e->SH * e->SW * w + 5.0 * B * e->PH * e->PW * w, k_maxpool_fwd(st, WS(e->z0), WS(e->stem_bn.scale), WS(e->stem_bn.shift), WS(e->p0),
+  RUNB(HB_MAXPOOL_FWD, 4.0 * B * e->SH * e->SW * w + 5.0 * B * e->PH * e->PW * w, mmvqa_maxpool_fwd(st, WS(e->z0), WS(e->stem_bn.scale), WS(e->stem_bn.shift), WS(e->p0),
                                    reinterpret_cast<unsigned char*>(WS(e->pool_idx)), B, e->SH, e->SW, w, e->PH,
                                    e->PW));
   const float* x = WS(e->p0);
@@ -1073,14 +1067,14 @@ static int resnet_forward(mmvqa_engine* e, hipStream_t st) {
       mmvqa_bn_fold f3, fd;
       set_fold_fwd(e, f3, b.b3);
       if (b.has_ds) { TRY(sc.need(ev_ds)); set_fold_fwd(e, fd, b.bd); }
-      RUNB(HB_BN_ADD_RELU, 12.0 * rows * b.c3.Cout, k_bn_add_relu_fold(st, WS(b.z3), &f3, b.has_ds ? WS(b.zd) : x, b.has_ds ? &fd : nullptr,
+      RUNB(HB_BN_ADD_RELU, 12.0 * rows * b.c3.Cout, mmvqa_bn_add_relu_fold(st, WS(b.z3), &f3, b.has_ds ? WS(b.zd) : x, b.has_ds ? &fd : nullptr,
                                             WS(b.out), rows, b.c3.Cout));
     } else if (b.has_ds) {
       TRY(sc.need(ev_ds));
-      RUNB(HB_BN_ADD_RELU, 12.0 * rows * b.c3.Cout, k_bn_add_relu(st, WS(b.z3), WS(b.b3.scale), WS(b.b3.shift), WS(b.zd), WS(b.bd.scale),
+      RUNB(HB_BN_ADD_RELU, 12.0 * rows * b.c3.Cout, mmvqa_bn_add_relu(st, WS(b.z3), WS(b.b3.scale), WS(b.b3.shift), WS(b.zd), WS(b.bd.scale),
                                        WS(b.bd.shift), WS(b.out), rows, b.c3.Cout));
     } else {
-      RUNB(HB_BN_ADD_RELU, 12.0 * rows * b.c3.Cout, k_bn_add_relu(st, WS(b.z3), WS(b.b3.scale), WS(b.b3.shift), x, nullptr, nullptr,
+      RUNB(HB_BN_ADD_RELU, 12.0 * rows * b.c3.Cout, mmvqa_bn_add_relu(st, WS(b.z3), WS(b.b3.scale), WS(b.b3.shift), x, nullptr, nullptr,
                                        WS(b.out), rows, b.c3.Cout));
     }
     x = WS(b.out);
@@ -1211,7 +1205,7 @@ static int resnet_backward(mmvqa_engine* e, hipStream_t st) {
   TRY(sc.need(ev_prevG));
   TRY(sc.need(ev_tap[4]));
   RUNB(HB_MAXPOOL_BWD, 12.0 * B * e->SH * e->SW * w + 5.0 * B * e->PH * e->PW * w,
-      k_maxpool_bwd(st, WS(e->gbuf[cur]), reinterpret_cast<unsigned char*>(WS(e->pool_idx)), WS(e->tapgrad[4]),
+      mmvqa_maxpool_bwd(st, WS(e->gbuf[cur]), reinterpret_cast<unsigned char*>(WS(e->pool_idx)), WS(e->tapgrad[4]),
                     WS(e->z0), WS(e->stem_bn.scale), WS(e->stem_bn.shift), WS(e->stem_bn.mean),
                     WS(e->stem_bn.invstd), g0, stat_ptr(e, e->stem_bn.stat_b), B, e->SH, e->SW, w, e->PH, e->PW));
   TRY(bn_coef_bwd(e, st, e->stem_bn));
@@ -1237,10 +1231,10 @@ static int effnet_forward(mmvqa_engine* e, hipStream_t st) {
     if (fold && !have_coef) {
       mmvqa_bn_fold f;
       set_fold_fwd(e, f, bn);
-      RUNB(HB_BN_ACT_ADD, (idn ? 12.0 : 8.0) * rows * C, k_bn_act_add_fold(st, z, &f, act, idn, nullptr, ACT_NONE, out, rows, C));
+      RUNB(HB_BN_ACT_ADD, (idn ? 12.0 : 8.0) * rows * C, mmvqa_bn_act_add_fold(st, z, &f, act, idn, nullptr, ACT_NONE, out, rows, C));
     } else {
       if (!have_coef) TRY(bn_coef_fwd(e, st, bn));
-      RUNB(HB_BN_ACT_ADD, (idn ? 12.0 : 8.0) * rows * C, k_bn_act_add(st, z, WS(bn.scale), WS(bn.shift), act, idn, nullptr, nullptr, 0,
+      RUNB(HB_BN_ACT_ADD, (idn ? 12.0 : 8.0) * rows * C, mmvqa_bn_act_add(st, z, WS(bn.scale), WS(bn.shift), act, idn, nullptr, nullptr, 0,
                                       ACT_NONE, out, rows, C));
     }
     return MMVQA_OK;
@@ -1266,12 +1260,12 @@ static int effnet_forward(mmvqa_engine* e, hipStream_t st) {
       mmvqa_bn_fold fa, fdw;
       if (fold) { set_fold_fwd(e, fa, b.b_a); set_fold_fwd(e, fdw, b.b_dw); }
       TRY(conv_fwd(e, st, b.c_a, x, {}, B, b.H, b.W, b.H, b.W, WS(b.za), b.b_a, !fold));
-      RUNB(HB_DWCONV_FWD, 4.0 * ((double)B * b.H * b.W + (double)Mout) * b.mid, k_dwconv_fwd(st, WS(b.za), WS(b.b_a.scale), WS(b.b_a.shift), PRM(b.dw_w), WS(b.zdw),
+      RUNB(HB_DWCONV_FWD, 4.0 * ((double)B * b.H * b.W + (double)Mout) * b.mid, mmvqa_dwconv_fwd_fold(st, WS(b.za), WS(b.b_a.scale), WS(b.b_a.shift), PRM(b.dw_w), WS(b.zdw),
                                       e->training ? stat_ptr(e, b.b_dw.stat_f) : nullptr, B, b.H, b.W, b.mid, b.OH, b.OW,
                                       b.stride, b.pad, fold ? &fa : nullptr));
       if (!fold) TRY(bn_coef_fwd(e, st, b.b_dw));
       // squeeze-excite: gate = sigmoid(W_e silu(W_r mean_hw(a2) + b_r) + b_e)
-      RUNB(HB_SE_POOL, 4.0 * Mout * b.mid, k_se_pool(st, WS(b.zdw), WS(b.b_dw.scale), WS(b.b_dw.shift), WS(b.pool), B, b.OH * b.OW, b.mid,
+      RUNB(HB_SE_POOL, 4.0 * Mout * b.mid, mmvqa_se_pool_fold(st, WS(b.zdw), WS(b.b_dw.scale), WS(b.b_dw.shift), WS(b.pool), B, b.OH * b.OW, b.mid,
                                       fold ? &fdw : nullptr));
       RUN(PROF_MATRIX, 2.0 * B * b.mid * b.rd, k_skinny_fwd(st, WS(b.pool), b.mid, PRM(b.se_r.w), PRM(b.se_r.b), ACT_SILU, WS(b.rpre), WS(b.r),
                                       B, b.rd, b.mid));
@@ -1344,7 +1338,7 @@ static int effnet_backward(mmvqa_engine* e, hipStream_t st) {
     if (b.type == 0) {
       // out = silu(bn(za)) + x
       TRY(scx.need(ev_gA[pi]));
-      RUNB(HB_ACT_BWD_STATS, 12.0 * Mout * b.cout, k_act_bwd_stats(st, G, nullptr, nullptr, WS(b.za), WS(b.b_a.scale), WS(b.b_a.shift),
+      RUNB(HB_ACT_BWD_STATS, 12.0 * Mout * b.cout, mmvqa_act_bwd_stats(st, G, nullptr, nullptr, WS(b.za), WS(b.b_a.scale), WS(b.b_a.shift),
                                          WS(b.b_a.mean), WS(b.b_a.invstd), ACT_SILU, gA, stat_ptr(e, b.b_a.stat_b), Mout,
                                          b.OH * b.OW, b.cout));
       dz_first = gA;
@@ -1375,18 +1369,18 @@ static int effnet_backward(mmvqa_engine* e, hipStream_t st) {
                                      WS(e->eff_separt), 1, B, b.mid, b.rd));
       // du2 = (t*gate + dpool/HW) * silu'(bn2(zdw)); BN2 sums
       TRY(scx.need(ev_gB[pi]));
-      RUNB(HB_ACT_BWD_STATS, 12.0 * Mout * b.mid, k_act_bwd_stats(st, gA, WS(b.gate), dpool, WS(b.zdw), WS(b.b_dw.scale), WS(b.b_dw.shift),
+      RUNB(HB_ACT_BWD_STATS, 12.0 * Mout * b.mid, mmvqa_act_bwd_stats(st, gA, WS(b.gate), dpool, WS(b.zdw), WS(b.b_dw.scale), WS(b.b_dw.shift),
                                          WS(b.b_dw.mean), WS(b.b_dw.invstd), ACT_SILU, gB, stat_ptr(e, b.b_dw.stat_b), Mout,
                                          b.OH * b.OW, b.mid));
       mmvqa_bn_fold fdw_w, fdw_d;
       if (fold) { set_fold_bwd(e, fdw_w, b.b_dw, false); set_fold_bwd(e, fdw_d, b.b_dw, true); }
       else TRY(bn_coef_bwd(e, st, b.b_dw));
       TRY(scx.fork());
-      RUNB_ON(sd, HB_DWCONV_BWD_WEIGHT, 4.0 * (2.0 * Mout + (double)Min) * b.mid, k_dwconv_bwd_weight(sd, gB, WS(b.zdw), WS(b.b_dw.P), WS(b.b_dw.Q), WS(b.b_dw.R), WS(b.za),
+      RUNB_ON(sd, HB_DWCONV_BWD_WEIGHT, 4.0 * (2.0 * Mout + (double)Min) * b.mid, mmvqa_dwconv_bwd_weight_fold(sd, gB, WS(b.zdw), WS(b.b_dw.P), WS(b.b_dw.Q), WS(b.b_dw.R), WS(b.za),
                                            WS(b.b_a.scale), WS(b.b_a.shift), GRD(b.dw_w), B, b.H, b.W, b.mid, b.OH, b.OW,
                                            b.stride, b.pad, fold ? &fdw_w : nullptr));
       TRY(scx.mark(&ev_gB[pi]));
-      RUNB(HB_DWCONV_BWD_DATA, 4.0 * (2.0 * Mout + 2.0 * (double)Min) * b.mid, k_dwconv_bwd_data(st, gB, WS(b.zdw), WS(b.b_dw.P), WS(b.b_dw.Q), WS(b.b_dw.R), PRM(b.dw_w),
+      RUNB(HB_DWCONV_BWD_DATA, 4.0 * (2.0 * Mout + 2.0 * (double)Min) * b.mid, mmvqa_dwconv_bwd_data_fold(st, gB, WS(b.zdw), WS(b.b_dw.P), WS(b.b_dw.Q), WS(b.b_dw.R), PRM(b.dw_w),
                                            WS(b.za), WS(b.b_a.scale), WS(b.b_a.shift), WS(b.b_a.mean), WS(b.b_a.invstd), gA,
                                            stat_ptr(e, b.b_a.stat_b), B, b.H, b.W, b.mid, b.OH, b.OW, b.stride, b.pad, fold ? &fdw_d : nullptr));
       dz_first = gA;
@@ -1412,7 +1406,7 @@ static int effnet_backward(mmvqa_engine* e, hipStream_t st) {
   const long M0 = (long)B * e->SH * e->SW;
   const int C0 = e->stem_conv.Cout;
   TRY(scx.need(ev_G[cur ^ 1]));
-  RUNB(HB_ACT_BWD_STATS, 12.0 * M0 * C0, k_act_bwd_stats(st, WS(e->gbuf[cur]), nullptr, nullptr, WS(e->z0), WS(e->stem_bn.scale),
+  RUNB(HB_ACT_BWD_STATS, 12.0 * M0 * C0, mmvqa_act_bwd_stats(st, WS(e->gbuf[cur]), nullptr, nullptr, WS(e->z0), WS(e->stem_bn.scale),
                                      WS(e->stem_bn.shift), WS(e->stem_bn.mean), WS(e->stem_bn.invstd), ACT_SILU, g0,
                                      stat_ptr(e, e->stem_bn.stat_b), M0, e->SH * e->SW, C0));
   TRY(bn_coef_bwd(e, st, e->stem_bn));
@@ -1468,7 +1462,7 @@ static int drop_grad(mmvqa_engine* e, hipStream_t st, SideReads& sr, const float
   if (p > 0.f) {
     const long n = (long)e->B * e->T * e->d.hidden;
     TRY(sr.write(WS(e->t_b)));
-    RUNB(HB_DROPOUT_COPY, 8.0 * n, k_dropout_copy(st, g, WS(e->t_b), n, p, seed));
+    RUNB(HB_DROPOUT_COPY, 8.0 * n, mmvqa_dropout_copy(st, g, WS(e->t_b), n, p, seed));
     *out = WS(e->t_b);
   }
   return MMVQA_OK;
@@ -1492,7 +1486,7 @@ static int bert_forward(mmvqa_engine* e, hipStream_t st, const float* x_in, cons
       // north-star block = QKV products + attention, whichever launches carry them: bench.py adds the three regions)
       REG(REG_QKV_ATTN);
       RUN(PROF_ATTN, 2.0 * M * 3 * H * H + 4.0 * e->B * d.heads * (double)e->T * e->T * (H / d.heads),
-          k_qkv_attn_fwd(st, WS(L.xn1), PRM(L.qkv.w), PRM(L.qkv.b), e->mask, WS(L.qkvo), WS(L.probs), WS(L.ctx), e->B, e->T,
+          mmvqa_qkv_attention_fwd(st, WS(L.xn1), PRM(L.qkv.w), PRM(L.qkv.b), e->mask, WS(L.qkvo), WS(L.probs), WS(L.ctx), e->B, e->T,
                          H, d.heads, p, site_seed(e, i, 0)));
     } else {
     { REG(REG_QKV); TRY(lin_fwd(e, st, WS(L.xn1), H, M, L.qkv, WS(L.qkvo), 3 * H, ACT_NONE, nullptr, 0.f, 0, nullptr, 0)); }
@@ -1649,7 +1643,7 @@ static void fb_attn_fill(mmvqa_engine* e, const FBLayerRef& L, int layer, int w,
 static int fb_attn_call(mmvqa_engine* e, hipStream_t st, const mmvqa_fb_attn_desc& a, int bwd) {
   REG(REG_ATTN);
   const double fl = (bwd ? 10.0 : 4.0) * (double)a.B * 8 * a.n * (a.n_mem + (a.n == 2 ? 2 : 0)) * 64;
-  RUN(PROF_ATTN, fl, k_fb_attention(st, a, bwd));
+  RUN(PROF_ATTN, fl, mmvqa_fb_attention(&a, bwd, st));
   return MMVQA_OK;
 }
 
@@ -1680,13 +1674,13 @@ static int fb_forward(mmvqa_engine* e, hipStream_t st, const float* x_in, const 
       // x = x + W2(drop(gelu(gate) * u)), (u | gate) = W1 LN_f(x)
       TRY(ln_fwd(e, st, WS(L.xmid) + r0 * H, L.ln_f, WS(L.xn_f) + r0 * H, WS(L.mean_f) + r0, WS(L.rstd_f) + r0, Mw, 1e-5f));
       TRY(lin_fwd(e, st, WS(L.xn_f) + r0 * H, H, Mw, L.w1, WS(L.pre) + r0 * 8 * H, 8 * H, ACT_NONE, nullptr, 0.f, 0, nullptr, 0));
-      RUN(PROF_OTHER, 0, k_geglu_fwd(st, WS(L.pre) + r0 * 8 * H, WS(L.gg) + r0 * 4 * H, Mw, 4 * H, p, site_seed(e, i, 1),
+      RUN(PROF_OTHER, 0, mmvqa_geglu_fwd(st, WS(L.pre) + r0 * 8 * H, WS(L.gg) + r0 * 4 * H, Mw, 4 * H, p, site_seed(e, i, 1),
                                      (uint32_t)(r0 * 4 * H)));
       TRY(lin_fwd(e, st, WS(L.gg) + r0 * 4 * H, 4 * H, Mw, L.w2, WS(e->fb_hid) + (i + 1) * M * H + r0 * H, H, ACT_NONE, nullptr, 0.f,
                   0, WS(L.xmid) + r0 * H, H));
     }
     if (w + 1 < nwin) {   // the memory the last window would write is never read
-      RUN(PROF_OTHER, 0, k_fb_aggregate_fwd(st, WS(e->fb_hid) + r0 * H, (long long)(M * H), NL + 1, PRM(e->fb_lw),
+      RUN(PROF_OTHER, 0, mmvqa_fb_aggregate_fwd(st, WS(e->fb_hid) + r0 * H, (long long)(M * H), NL + 1, PRM(e->fb_lw),
                                             WS(e->fb_agg) + r0 * H, Mw, H));
       REG(REG_QKV);
       TRY(lin_fwd(e, st, WS(e->fb_agg) + r0 * H, H, Mw, e->fb_kv, WS(e->fb_mem) + r0 * 1024, 1024, ACT_NONE, nullptr, 0.f, 0, nullptr, 0));
@@ -1721,7 +1715,7 @@ static int fb_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, SideR
       // softmax(layer_weight)_l * dagg into each hidden's gradient (the top one at once, the others when the loop gets there)
       { REG(REG_QKV);
         TRY(lin_dgrad(e, st, WS(e->fb_dmem) + r0 * 1024, 1024, Mw, e->fb_kv, s2, H, 0, nullptr, 0, nullptr, nullptr, 0)); }
-      RUN(PROF_OTHER, 0, k_fb_aggregate_bwd(st, s2, WS(e->fb_hid) + r0 * H, (long long)(M * H), NL + 1, PRM(e->fb_lw),
+      RUN(PROF_OTHER, 0, mmvqa_fb_aggregate_bwd(st, s2, WS(e->fb_hid) + r0 * H, (long long)(M * H), NL + 1, PRM(e->fb_lw),
                                             WS(e->fb_dhs), (long long)2 * B * H, ghid + NL * M * H + r0 * H,
                                             sr.data_only ? nullptr : GRD(e->fb_lw), Mw, H));
     }
@@ -1729,7 +1723,7 @@ static int fb_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, SideR
       FBLayerRef& L = e->fb[i];
       const float* gout = ghid + (i + 1) * M * H + r0 * H;
       TRY(lin_dgrad(e, st, gout, H, Mw, L.w2, s1, 4 * H, 0, nullptr, 0, nullptr, nullptr, 0));
-      RUN(PROF_OTHER, 0, k_geglu_bwd(st, s1, WS(L.pre) + r0 * 8 * H, WS(L.g_pre) + r0 * 8 * H, Mw, 4 * H, p, site_seed(e, i, 1),
+      RUN(PROF_OTHER, 0, mmvqa_geglu_bwd(st, s1, WS(L.pre) + r0 * 8 * H, WS(L.g_pre) + r0 * 8 * H, Mw, 4 * H, p, site_seed(e, i, 1),
                                      (uint32_t)(r0 * 4 * H)));
       TRY(lin_dgrad(e, st, WS(L.g_pre) + r0 * 8 * H, 8 * H, Mw, L.w1, s2, H, 0, nullptr, 0, nullptr, nullptr, 0));
       TRY(ln_bwd(e, st, s2, WS(L.xmid) + r0 * H, L.ln_f, WS(L.mean_f) + r0, WS(L.rstd_f) + r0, gout, WS(L.g_mid) + r0 * H, Mw,
@@ -1753,7 +1747,7 @@ static int fb_backward(mmvqa_engine* e, hipStream_t st, const float* x_in, SideR
       TRY(ln_bwd(e, st, dxn, WS(e->fb_hid) + i * M * H + r0 * H, L.ln_a, WS(L.mean_a) + r0, WS(L.rstd_a) + r0,
                  WS(L.g_mid) + r0 * H, ghid + i * M * H + r0 * H, Mw, sr.data_only));
       if (wrote_mem)
-        RUN(PROF_OTHER, 0, k_axpy(st, ghid + i * M * H + r0 * H, WS(e->fb_dhs) + (size_t)i * 2 * B * H, 1.0f, Mw * H));
+        RUN(PROF_OTHER, 0, mmvqa_axpy(st, ghid + i * M * H + r0 * H, WS(e->fb_dhs) + (size_t)i * 2 * B * H, 1.0f, Mw * H));
     }
   }
   if (!sr.data_only) {
@@ -1790,7 +1784,7 @@ static int heads_forward(mmvqa_engine* e, hipStream_t st, const float* h) {
   const float* hin = h;
   long HM = M;
   if (d.head_kind == 1) {
-    RUN(PROF_OTHER, 0, k_meanpool_fwd(st, h, e->mask, WS(e->hd_pool), e->B, e->T, H));
+    RUN(PROF_OTHER, 0, mmvqa_meanpool_fwd(st, h, e->mask, WS(e->hd_pool), e->B, e->T, H));
     hin = WS(e->hd_pool);
     HM = e->B;
   }
@@ -1799,12 +1793,12 @@ static int heads_forward(mmvqa_engine* e, hipStream_t st, const float* h) {
   TRY(ln_fwd(e, st, WS(e->hd_c0), e->cls_ln, WS(e->hd_c1), WS(e->hd_mean), WS(e->hd_rstd), HM, 1e-12f));
   TRY(lin_fwd(e, st, WS(e->hd_c1), H, HM, e->cls2, e->logits, e->logits_ld, ACT_NONE, nullptr, 0.f, 0, nullptr, 0));
   if (d.supcon && e->feat) {
-    RUN(PROF_OTHER, 0, k_meanpool_fwd(st, h, e->mask, WS(e->sc_pool), e->B, e->T, H));
+    RUN(PROF_OTHER, 0, mmvqa_meanpool_fwd(st, h, e->mask, WS(e->sc_pool), e->B, e->T, H));
     TRY(lin_fwd(e, st, WS(e->sc_pool), H, e->B, e->head0, WS(e->sc_a), H, ACT_SERF, WS(e->sc_pre), 0.f, 0, nullptr, 0));
     TRY(lin_fwd(e, st, WS(e->sc_a), H, e->B, e->head2, WS(e->sc_f), d.feat_dim, ACT_NONE, nullptr, 0.f, 0, nullptr, 0));
     // the normalised features stay in the engine's workspace for the backward pass: the caller may drop its
     // `feat` tensor before backward (supcon_utils.py:283-284 rebinds it to split_feat(feat))
-    RUN(PROF_OTHER, 0, k_l2norm_fwd(st, WS(e->sc_f), WS(e->sc_y), WS(e->sc_nrm), e->B, d.feat_dim));
+    RUN(PROF_OTHER, 0, mmvqa_l2norm_fwd(st, WS(e->sc_f), WS(e->sc_y), WS(e->sc_nrm), e->B, d.feat_dim));
     HIP_CHECK_RET(hipMemcpyAsync(e->feat, WS(e->sc_y), (size_t)e->B * d.feat_dim * sizeof(float),
                                  hipMemcpyDeviceToDevice, st));
   }
@@ -1829,7 +1823,7 @@ static int heads_backward(mmvqa_engine* e, hipStream_t st, const float* h, const
     g.B = WS(e->hd_c1); g.b_ld = H; g.g_Cs = H;
     g.C = GRD(e->cls2.w); g.c_ld = H; g.c_atomic = 1;
     RUN_ON(wst, PROF_IGEMM, 2.0 * HM * d.n_classes * H, mmvqa_launch_igemm(g, KIND_WGRAD, 0, 0, wst));
-    RUN_ON(wst, PROF_OTHER, 0, k_colsum(wst, dlogits, dl_ld, (int)HM, d.n_classes, GRD(e->cls2.b)));
+    RUN_ON(wst, PROF_OTHER, 0, mmvqa_colsum(wst, dlogits, dl_ld, (int)HM, d.n_classes, GRD(e->cls2.b)));
   }
   TRY(lin_dgrad(e, st, dlogits, dl_ld, HM, e->cls2, WS(e->t_b), H, 0, nullptr, 0, nullptr, nullptr, 0));  // dc1
   TRY(ln_bwd(e, st, WS(e->t_b), WS(e->hd_c0), e->cls_ln, WS(e->hd_mean), WS(e->hd_rstd), nullptr, WS(e->t_c), HM, sr.data_only));
@@ -1840,19 +1834,19 @@ static int heads_backward(mmvqa_engine* e, hipStream_t st, const float* h, const
   if (d.head_kind == 1) {
     TRY(sr.write(WS(e->t_c)));
     TRY(lin_dgrad(e, st, WS(e->t_b), H, HM, e->fc1, WS(e->t_c), H, 0, nullptr, 0, nullptr, nullptr, 0));
-    RUN(PROF_OTHER, 0, k_meanpool_bwd(st, WS(e->t_c), e->mask, dh, e->B, e->T, H, 0));
+    RUN(PROF_OTHER, 0, mmvqa_meanpool_bwd(st, WS(e->t_c), e->mask, dh, e->B, e->T, H, 0));
   } else {
     TRY(lin_dgrad(e, st, WS(e->t_b), H, HM, e->fc1, dh, H, 0, nullptr, 0, nullptr, nullptr, 0));
   }
   if (d.supcon && dfeat) {
     TRY(sr.write(WS(e->t_b))); TRY(sr.write(WS(e->t_c)));
     float* df = WS(e->t_b);  // [B][feat_dim]
-    RUN(PROF_OTHER, 0, k_l2norm_bwd(st, dfeat, WS(e->sc_y), WS(e->sc_nrm), df, e->B, d.feat_dim));
+    RUN(PROF_OTHER, 0, mmvqa_l2norm_bwd(st, dfeat, WS(e->sc_y), WS(e->sc_nrm), df, e->B, d.feat_dim));
     TRY(lin_wgrad(e, st, df, d.feat_dim, WS(e->sc_a), H, e->B, e->head2, true));
     TRY(lin_dgrad(e, st, df, d.feat_dim, e->B, e->head2, WS(e->t_c), H, ACT_SERF, WS(e->sc_pre), H, GRD(e->head0.b), nullptr, 0));
     TRY(lin_wgrad(e, st, WS(e->t_c), H, WS(e->sc_pool), H, e->B, e->head0, false));
     TRY(lin_dgrad(e, st, WS(e->t_c), H, e->B, e->head0, WS(e->t_d), H, 0, nullptr, 0, nullptr, nullptr, 0));
-    RUN(PROF_OTHER, 0, k_meanpool_bwd(st, WS(e->t_d), e->mask, dh, e->B, e->T, H, 1));
+    RUN(PROF_OTHER, 0, mmvqa_meanpool_bwd(st, WS(e->t_d), e->mask, dh, e->B, e->T, H, 1));
   }
   return MMVQA_OK;
 }
@@ -1877,7 +1871,7 @@ static int prepare_workspace(mmvqa_engine* e, hipStream_t st) {
   if (e->ws_ready) return MMVQA_OK;
   for (auto& kv : e->pixmask_off) {
     const mmvqa_engine::PixGeom& q = kv.second;
-    TRY(k_pixmask(st, reinterpret_cast<int*>(WS(q.off)), q.N, q.OH, q.OW, q.H, q.W, q.KH, q.KH, q.stride, q.pad));
+    TRY(mmvqa_pixmask(st, reinterpret_cast<int*>(WS(q.off)), q.N, q.OH, q.OW, q.H, q.W, q.KH, q.KH, q.stride, q.pad));
   }
   for (int i = 0; i < 3; ++i) HIP_CHECK_RET(hipMemsetAsync(WS(e->sk_cnt[i]), 0, SK_CNT_N * sizeof(unsigned int), st));
   e->ws_ready = true;
@@ -1921,7 +1915,7 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
   const float pe = training ? d.p_emb_drop : 0.f;
   e->prof_reg = REG_EMBED;
   RUN(PROF_OTHER, 0,
-      k_embed_fwd(st, ids, seg, PRM(e->emb_word), PRM(e->emb_pos), PRM(e->emb_type), PRM(e->emb_ln.g),
+      mmvqa_embed_fwd(st, ids, seg, PRM(e->emb_word), PRM(e->emb_pos), PRM(e->emb_type), PRM(e->emb_ln.g),
                   PRM(e->emb_ln.b), WS(e->vis), WS(e->emb_out), WS(e->emb_xhat), WS(e->emb_rstd), e->B, e->T,
                   d.hidden, d.num_vis, 1e-12f, pe, site_seed(e, 100, 0)));
   e->prof_reg = REG_BACKBONE;
@@ -1960,7 +1954,7 @@ int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int d
   const float pe = e->training ? d.p_emb_drop : 0.f;
   e->prof_reg = REG_EMBED;
   RUN(PROF_OTHER, 0,
-      k_embed_bwd(st, WS(e->t_a), e->ids, e->seg, WS(e->emb_xhat), WS(e->emb_rstd), PRM(e->emb_ln.g),
+      mmvqa_embed_bwd(st, WS(e->t_a), e->ids, e->seg, WS(e->emb_xhat), WS(e->emb_rstd), PRM(e->emb_ln.g),
                   GRD(e->emb_word), GRD(e->emb_pos), GRD(e->emb_type), GRD(e->emb_ln.g), GRD(e->emb_ln.b),
                   WS(e->dvis), e->B, e->T, d.hidden, d.num_vis, pe, site_seed(e, 100, 0), 0));
   e->prof_reg = REG_BACKBONE;
@@ -2019,7 +2013,7 @@ int engine_backward_feature(mmvqa_engine* e, hipStream_t st, const float* dlogit
   return tap_bwd(e, st, k, WS(off), nullptr, dA, EpiOpt(), true);
 }
 
-int engine_create(const mmvqa_model_desc* desc, mmvqa_engine** out) {
+extern "C" int mmvqa_engine_create(const mmvqa_model_desc* desc, mmvqa_engine** out) {
   if (!desc || !out) return mmvqa_set_error(MMVQA_ERR_ARG, "engine_create: null argument");
   const mmvqa_model_desc& d = *desc;
   if (d.hidden % 8 != 0 || d.hidden > 1024 || d.n_layers < 1 || d.num_vis != 5)

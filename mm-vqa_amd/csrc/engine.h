@@ -1,5 +1,5 @@
 // Host runtime of the MMBERT hot path: parameter table, workspace plan and the launch sequences of
-// Model.forward / backward (models/mmbert.py:129-167).  Pure C++ over the HIP launchers in kernels.h.
+// Model.forward / backward (models/mmbert.py:129-167).  Pure C++ over the op entry points of include/mmvqa.h and the launchers in kernels.h.
 #pragma once
 #include <map>
 #include <string>
@@ -199,3 +199,12 @@ struct mmvqa_engine {
   long long reg_launch[REG_N][PROF_NCLS] = {};
   double reg_ms[REG_N][PROF_NCLS] = {}, reg_flops[REG_N][PROF_NCLS] = {};
 };
+
+// engine.cpp: what the mmvqa_engine_* entry points of abi.cpp run behind their argument checks
+size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW);
+int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long long* ids, const long long* seg,
+                   const long long* mask, float* logits, int logits_ld, float* feat, int training, uint32_t seed);
+int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, const float* dfeat);
+int engine_backward_feature(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, float* dA);
+int engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, int* C);
+int engine_profile_collect(mmvqa_engine* e);

@@ -342,7 +342,10 @@ inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 
 }  // namespace
 
-int k_fb_attention(hipStream_t st, const mmvqa_fb_attn_desc& p, int bwd) {
+extern "C" int mmvqa_fb_attention(const mmvqa_fb_attn_desc* d, int bwd, mmvqa_stream_t s) {
+  hipStream_t st = (hipStream_t)s;
+  if (!d) return mmvqa_set_error(MMVQA_ERR_ARG, "fb_attention: null descriptor");
+  const mmvqa_fb_attn_desc& p = *d;
   const int J = p.n_mem + (p.n == 2 ? 2 : 0);
   if (p.B <= 0 || (p.n != 1 && p.n != 2) || p.n_mem < 0 || (p.n_mem & 1) || J < 1 || J > FB_MAXKEYS)
     return mmvqa_set_error(MMVQA_ERR_ARG, "fb_attention: B=%d n=%d n_mem=%d (n in {1,2}, n_mem even, 1 <= keys <= %d)", p.B, p.n,
@@ -380,7 +383,9 @@ static int fb_agg_check(const char* who, const float* a, const float* hid, long 
   return MMVQA_OK;
 }
 
-int k_fb_aggregate_fwd(hipStream_t st, const float* hid, long long hstride, int nh, const float* lw, float* agg, long rows, int H) {
+extern "C" int mmvqa_fb_aggregate_fwd(mmvqa_stream_t s, const float* hid, long long hstride, int nh, const float* lw,
+                                      float* agg, long rows, int H) {
+  hipStream_t st = (hipStream_t)s;
   int r = fb_agg_check("fb_aggregate_fwd", agg, hid, hstride, nh, lw, rows, H);
   if (r != MMVQA_OK) return r;
   const long n4 = rows * (H / 4);
@@ -389,8 +394,10 @@ int k_fb_aggregate_fwd(hipStream_t st, const float* hid, long long hstride, int 
   return MMVQA_OK;
 }
 
-int k_fb_aggregate_bwd(hipStream_t st, const float* dagg, const float* hid, long long hstride, int nh, const float* lw, float* dh,
-                       long long dstride, float* dtop, float* dlw, long rows, int H) {
+extern "C" int mmvqa_fb_aggregate_bwd(mmvqa_stream_t s, const float* dagg, const float* hid, long long hstride, int nh,
+                                      const float* lw, float* dh, long long dstride, float* dtop, float* dlw, long rows,
+                                      int H) {
+  hipStream_t st = (hipStream_t)s;
   int r = fb_agg_check("fb_aggregate_bwd", dagg, hid, hstride, nh, lw, rows, H);
   if (r != MMVQA_OK) return r;
   if (!dh || (dstride & 3) || !al16(dh) || !al16(dtop))
@@ -413,7 +420,9 @@ static int fb_geglu_check(const char* who, const void* a, const void* b, const v
   return MMVQA_OK;
 }
 
-int k_geglu_fwd(hipStream_t st, const float* pre, float* y, long M, int F, float drop_p, uint32_t seed, uint32_t idx0) {
+extern "C" int mmvqa_geglu_fwd(mmvqa_stream_t s, const float* pre, float* y, long M, int F, float drop_p, uint32_t seed,
+                               uint32_t idx0) {
+  hipStream_t st = (hipStream_t)s;
   int r = fb_geglu_check("geglu_fwd", pre, y, y, M, F, drop_p, idx0);
   if (r != MMVQA_OK) return r;
   const long n4 = M * (F / 4);
@@ -422,8 +431,9 @@ int k_geglu_fwd(hipStream_t st, const float* pre, float* y, long M, int F, float
   return MMVQA_OK;
 }
 
-int k_geglu_bwd(hipStream_t st, const float* dy, const float* pre, float* dpre, long M, int F, float drop_p, uint32_t seed,
-                uint32_t idx0) {
+extern "C" int mmvqa_geglu_bwd(mmvqa_stream_t s, const float* dy, const float* pre, float* dpre, long M, int F,
+                               float drop_p, uint32_t seed, uint32_t idx0) {
+  hipStream_t st = (hipStream_t)s;
   int r = fb_geglu_check("geglu_bwd", dy, pre, dpre, M, F, drop_p, idx0);
   if (r != MMVQA_OK) return r;
   const long n4 = M * (F / 4);

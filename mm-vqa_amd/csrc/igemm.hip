@@ -116,7 +116,6 @@ __device__ __forceinline__ void static_for(F&& f) {
 #define MAX_TAPS 32
 #define SC1_AUX 16       // cache-policy bits of the raw buffer builtins on gfx950: 1 = sc0, 2 = nt, 16 = sc1 (write-through / L1 bypass)
 #define SK_PART_MAX 8    // most splits of one tile in the ticketed split-K (host-checked)
-#define TRY_RET(x) do { int r_ = (x); if (r_ != MMVQA_OK) return r_; } while (0)
 
 // Phase timestamps of every workgroup (tools/igemm_trace.py builds the library with -DIGEMM_TRACE):
 // [wg][8] = {entry, loader state ready, first tile in LDS, K loop done, end} in s_memtime ticks (per-XCD counter),
@@ -1764,9 +1763,9 @@ static int launch_cfg(GemmParams p, hipStream_t stream) {
       if (!f.publish || !f.out0 || !f.out1 || !f.out2)
         return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: this launch cannot fold its BatchNorm coefficients in the kernel and has nowhere to publish them");
       if (f.bwd)
-        TRY_RET(k_bn_coef_bwd(stream, f.stat, C, f.count, f.gamma, f.mean, f.invstd, 1, f.out0, f.out1, f.out2, f.dgamma, f.dbeta));
+        TRY(mmvqa_bn_coef_bwd(stream, f.stat, C, f.count, f.gamma, f.mean, f.invstd, 1, f.out0, f.out1, f.out2, f.dgamma, f.dbeta));
       else
-        TRY_RET(k_bn_coef_fwd_keep(stream, f.stat, C, f.count, f.eps, f.gamma, f.beta, f.run_mean, f.run_var, f.nbt, f.keep,
+        TRY(k_bn_coef_fwd_keep(stream, f.stat, C, f.count, f.eps, f.gamma, f.beta, f.run_mean, f.run_var, f.nbt, f.keep,
                                    f.reps, 1, f.out0, f.out1, f.out2, f.out3));
       p.a_c0 = f.out0; p.a_c1 = f.out1; p.a_c2 = f.out2;
       p.a_fold.stat = nullptr;
@@ -1875,20 +1874,32 @@ static int launch_one(GemmParams p, int kind, int nchw, int tile, hipStream_t st
 // dimensions) alone -- the uniform-tap path even lets the hardware range check of a 2 GB buffer window stand in for
 // per-element bounds tests -- so a descriptor whose dimensions disagree with each other (or a prologue / epilogue
 // option without its tensors) would read outside the caller's buffers.  Such a descriptor is refused here.
-static int validate_desc(const GemmParams& p, int kind, int nchw) {
 #define BAD(...) return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: " __VA_ARGS__)
-  if (kind < KIND_FWD || kind > KIND_WGRAD) BAD("unknown kind %d", kind);
+// the part that does not depend on the product's size: mmvqa_igemm refuses these even for an empty product
+static int validate_operands(const GemmParams& p, int kind, int nchw) {
+  if (kind < KIND_FWD || kind > KIND_WGRAD) BAD("kind=%d", kind);
+  if (!p.A || !p.B || (!p.C && p.epi_mode != EPI_TAP_FWD)) BAD("null operand");
+  if (!nchw) {   // NHWC operands: rows of A and B, and every tap's channel run, start 16-byte aligned
+    if ((p.a_ld & 3) || (p.b_ld & 3) || (p.g_KH * p.g_KW > 1 && (p.g_Cs & 3)))
+      BAD("a_ld=%d b_ld=%d g_Cs=%d must be multiples of 4", p.a_ld, p.b_ld, p.g_Cs);
+    if (kind == KIND_DGRAD && (p.N & 3)) return mmvqa_set_error(MMVQA_ERR_ARG, "igemm dgrad: N=%d must be a multiple of 4", p.N);
+  }
+  if (p.a_pro == PRO_DZ && (!p.A2 || (!p.a_fold.stat && (!p.a_c0 || !p.a_c1 || !p.a_c2))))
+    BAD("PRO_DZ needs A2 and three coefficient arrays (or a_fold)");
+  if (p.g_SH <= 0 || p.g_SW <= 0 || p.g_OH <= 0 || p.g_OW <= 0 || p.g_Cs <= 0) BAD("gather geometry not set");
+  return MMVQA_OK;
+}
+
+static int validate_desc(const GemmParams& p, int kind, int nchw) {
+  if (int r = validate_operands(p, kind, nchw)) return r;
   if (p.reserved0 != MMVQA_PREC_F32 && p.reserved0 != MMVQA_PREC_F16) BAD("unknown operand precision %d (reserved0)", p.reserved0);
   if (p.reserved1 != 0) BAD("reserved1=%d must be 0 (the persistent form was removed)", p.reserved1);
   if (p.reserved0 == MMVQA_PREC_F16 && (p.a_pro == PRO_AFFINE_SILU || p.a_pro == PRO_SILU_GATE || p.b_pro == PRO_AFFINE_SILU ||
                                         p.b_pro == PRO_SILU_GATE || p.gate))
     BAD("the f16 operand family has no SiLU / gate prologues (a_pro %d, b_pro %d)", p.a_pro, p.b_pro);
-  if (!p.A || !p.B) BAD("operand pointer is null (A=%p B=%p)", (const void*)p.A, (const void*)p.B);
-  if (!p.C && p.epi_mode != EPI_TAP_FWD) BAD("output pointer is null");
   const int KH = p.g_KH > 0 ? p.g_KH : 1, KW = p.g_KH > 0 ? p.g_KW : 1;
   const long taps = (long)KH * KW;
-  if (KW <= 0 || p.g_Cs <= 0 || (p.g_KH > 0 && (p.g_stride <= 0 || p.g_pad < 0))) BAD("bad geometry (KH=%d KW=%d Cs=%d stride=%d pad=%d)", p.g_KH, p.g_KW, p.g_Cs, p.g_stride, p.g_pad);
-  if (p.g_OH <= 0 || p.g_OW <= 0 || p.g_SH <= 0 || p.g_SW <= 0) BAD("bad image dims (SH=%d SW=%d OH=%d OW=%d)", p.g_SH, p.g_SW, p.g_OH, p.g_OW);
+  if (KW <= 0 || (p.g_KH > 0 && (p.g_stride <= 0 || p.g_pad < 0))) BAD("bad geometry (KH=%d KW=%d Cs=%d stride=%d pad=%d)", p.g_KH, p.g_KW, p.g_Cs, p.g_stride, p.g_pad);
   const long ohw = (long)p.g_OH * p.g_OW;
   if (kind == KIND_WGRAD) {
     if ((long)p.N != taps * p.g_Cs) BAD("wgrad: N=%d != taps*Cs=%ld", p.N, taps * p.g_Cs);
@@ -1910,7 +1921,6 @@ static int validate_desc(const GemmParams& p, int kind, int nchw) {
     if (f.publish && (!f.out0 || !f.out1 || !f.out2 || (f.bwd ? (!f.dgamma || !f.dbeta) : !f.out3))) BAD("a_fold.publish without output arrays");
     if (nchw && kind != KIND_WGRAD) BAD("a_fold: not for the NCHW stem forward");
   } else if (p.a_pro != PRO_NONE && (!p.a_c0 || !p.a_c1)) BAD("A prologue %d without coefficients", p.a_pro);
-  if (p.a_pro == PRO_DZ && (!p.A2 || (!p.a_c2 && !p.a_fold.stat))) BAD("BatchNorm-backward prologue without A2 / c2");
   if (p.stat_slots < 0 || p.stat_slots > MMVQA_STAT_SLOTS || (p.stat_slots & (p.stat_slots - 1))) BAD("stat_slots=%d is not a power of two <= %d", p.stat_slots, MMVQA_STAT_SLOTS);
   if (p.b_pro != PRO_NONE && (!p.b_c0 || !p.b_c1)) BAD("B prologue %d without coefficients", p.b_pro);
   if ((p.a_pro == PRO_SILU_GATE || p.b_pro == PRO_SILU_GATE) && (!p.gate || p.gate_hw <= 0)) BAD("gate prologue without gate tensor");
@@ -1987,6 +1997,15 @@ int mmvqa_launch_igemm(GemmParams p, int kind, int nchw, int tile, hipStream_t s
   }
   p.splitk = it->second.splitk;
   return launch_one(p, kind, nchw, it->second.tile, stream);
+}
+
+extern "C" int mmvqa_igemm(const mmvqa_gemm_desc* d, int kind, int nchw, int tile, mmvqa_stream_t s) {
+  if (!d) return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: null descriptor");
+  // an empty product launches nothing: the launcher returns OK before it looks at the descriptor, and so it stays for the
+  // engine; this entry point has always refused malformed operands first
+  if (d->M <= 0 || d->N <= 0 || d->K <= 0)
+    if (int r = validate_operands(*d, kind, nchw)) return r;
+  return mmvqa_launch_igemm(*d, kind, nchw, tile, (hipStream_t)s);
 }
 
 // tile: 0 = auto, 1 = 128x128, 2 = 128x64, 3 = 64x64 (BK 64), 4 = 64x128, 5 = 64x64 with 8 waves (K-tile split in 2),

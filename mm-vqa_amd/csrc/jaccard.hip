@@ -69,8 +69,10 @@ __global__ void __launch_bounds__(256) jaccard_mask_kernel(const int* __restrict
   }
 }
 
-int k_jaccard_mask(hipStream_t st, const int* offsets, const int* ids, const int* rowsA, const int* colsA,
-                   const int* rowsB, const int* colsB, float* mask, int n, int table_rows) {
+extern "C" int mmvqa_jaccard_mask(mmvqa_stream_t s, const int* offsets, const int* ids, const int* rowsA,
+                                  const int* colsA, const int* rowsB, const int* colsB, float* mask, int n,
+                                  int table_rows) {
+  hipStream_t st = (hipStream_t)s;
   if (n < 1 || table_rows < 1) return mmvqa_set_error(MMVQA_ERR_ARG, "jaccard_mask: n=%d table_rows=%d (both >= 1)", n, table_rows);
   if (!offsets || !ids || !rowsA || !colsA || !rowsB || !colsB || !mask)
     return mmvqa_set_error(MMVQA_ERR_ARG, "jaccard_mask: null operand");

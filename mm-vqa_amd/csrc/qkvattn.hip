@@ -212,8 +212,11 @@ __global__ __launch_bounds__(512) void qkv_attn_fwd_kernel(const QkvAttnArgs p) 
 
 bool k_qkv_attn_fwd_ok(int T, int H, int heads) { return T >= 1 && T <= 32 && heads >= 1 && heads * 64 == H && H % QA_BK == 0; }
 
-int k_qkv_attn_fwd(hipStream_t st, const float* xn, const float* W, const float* bias, const long long* mask, float* qkv,
-                   float* probs, float* ctx, int B, int T, int H, int heads, float drop_p, uint32_t seed) {
+extern "C" int mmvqa_qkv_attention_fwd(mmvqa_stream_t s, const float* xn, const float* W, const float* bias,
+                                       const long long* mask, float* qkv, float* probs, float* ctx, int B, int T, int H,
+                                       int heads, float drop_p, uint32_t seed) {
+  hipStream_t st = (hipStream_t)s;
+  if (B <= 0 || drop_p < 0.f || drop_p >= 1.f) return mmvqa_set_error(MMVQA_ERR_ARG, "qkv_attention_fwd: B=%d drop_p=%g", B, (double)drop_p);
   if (!k_qkv_attn_fwd_ok(T, H, heads))
     return mmvqa_set_error(MMVQA_ERR_ARG, "qkv_attn_fwd: needs T <= 32 and head dimension 64 (T=%d H=%d heads=%d)", T, H, heads);
   if (!xn || !W || !mask || !qkv || !probs || !ctx) return mmvqa_set_error(MMVQA_ERR_ARG, "qkv_attn_fwd: null operand");

@@ -411,10 +411,18 @@ int k_skinny_fwd(hipStream_t st, const float* x, int x_ld, const float* W, const
   HIP_CHECK_RET(hipGetLastError());
   return MMVQA_OK;
 }
+// gate = sigmoid(W_e silu(W_r pool + b_r) + b_e): the two layers of one squeeze-excite block
+extern "C" int mmvqa_se_fc_fwd(mmvqa_stream_t s, const float* pool, const float* Wr, const float* br, const float* We,
+                               const float* be, float* rpre, float* r, float* gpre, float* gate, int B, int mid, int rd) {
+  hipStream_t st = (hipStream_t)s;
+  int rc = k_skinny_fwd(st, pool, mid, Wr, br, ACT_SILU, rpre, r, B, rd, mid);
+  if (rc != MMVQA_OK) return rc;
+  return k_skinny_fwd(st, r, rd, We, be, ACT_SIGMOID, gpre, gate, B, mid, rd);
+}
 
 bool k_se_fc_bwd_ok(int rd) { return rd > 0 && rd <= SE_MAXRD; }
 
-size_t k_se_fc_bwd_scratch_floats(int B, int mid, int rd) { (void)mid; return (size_t)B * rd; }
+extern "C" size_t mmvqa_se_fc_bwd_scratch_floats(int B, int mid, int rd) { (void)mid; return (size_t)B * rd; }
 
 // gradients of both squeeze-excite layers: accumulates dW_e, db_e, dW_r, db_r; writes dpool[B, mid].
 // scratch: B*rd floats, zero on entry (scratch_is_zero: the caller's previous kernel cleared it; else a memset is queued)
@@ -436,4 +444,9 @@ int k_se_fc_bwd(hipStream_t st, const float* dgate, const float* gpre, const flo
   }
   HIP_CHECK_RET(hipGetLastError());
   return MMVQA_OK;
+}
+extern "C" int mmvqa_se_fc_bwd(mmvqa_stream_t s, const float* dgate, const float* gpre, const float* r, const float* rpre,
+                               const float* pool, const float* We, const float* Wr, float* dWe, float* dbe, float* dWr,
+                               float* dbr, float* dpool, float* scratch, int B, int mid, int rd) {
+  return k_se_fc_bwd((hipStream_t)s, dgate, gpre, r, rpre, pool, We, Wr, dWe, dbe, dWr, dbr, dpool, scratch, 0, B, mid, rd);
 }

@@ -160,9 +160,11 @@ __global__ void __launch_bounds__(256) soft_ce_mean_kernel(const float* __restri
 
 static bool sce_vec_ok(const void* p, int ld) { return p && (ld & 3) == 0 && ((uintptr_t)p & 15) == 0; }
 
-int k_soft_ce(hipStream_t st, const float* logits, int ld, const long long* target, const long long* category,
-              const float* table, int table_ld, int n_cat, int mode, double smoothing, float* row_loss, float* loss,
-              float* dlogits, int dld, int rows, int C, float gscale) {
+extern "C" int mmvqa_soft_ce_loss(mmvqa_stream_t s, const float* logits, int ld, const long long* target,
+                                  const long long* category, const float* table, int table_ld, int n_cat, int mode,
+                                  double smoothing, float* row_loss, float* loss, float* dlogits, int dld, int rows,
+                                  int C, float gscale) {
+  hipStream_t st = (hipStream_t)s;
   if (mode < 0 || mode > 2) return mmvqa_set_error(MMVQA_ERR_ARG, "soft_ce_loss: mode=%d (0 hard, 1 uniform, 2 category table)", mode);
   if (rows <= 0 || C <= 0) return mmvqa_set_error(MMVQA_ERR_ARG, "soft_ce_loss: rows=%d C=%d (both >= 1)", rows, C);
   if (!logits || !target || !row_loss || !loss) return mmvqa_set_error(MMVQA_ERR_ARG, "soft_ce_loss: null operand");

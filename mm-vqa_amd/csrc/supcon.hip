@@ -213,8 +213,8 @@ __global__ void supcon_reduce_kernel(const float* __restrict__ row_loss, float* 
 
 // mask == nullptr: the unmasked kernels, ws = 4*N floats (lse, row losses); otherwise the masked ones, ws = 6*N floats
 // (2*N more: the mask row sums).  Every argument is checked before the first HIP call.
-int k_supcon(hipStream_t st, const float* f, const float* mask, float* loss, float* df, float* ws, int N, int D,
-             float temp, float base_temp, float gscale) {
+static int supcon(hipStream_t st, const float* f, const float* mask, float* loss, float* df, float* ws, int N, int D,
+                  float temp, float base_temp, float gscale) {
   const char* who = mask ? "supcon_masked" : "supcon";
   if (!f) return mmvqa_set_error(MMVQA_ERR_ARG, "%s: f is null", who);
   if (!loss) return mmvqa_set_error(MMVQA_ERR_ARG, "%s: loss is null", who);
@@ -247,4 +247,15 @@ int k_supcon(hipStream_t st, const float* f, const float* mask, float* loss, flo
   hipLaunchKernelGGL(supcon_reduce_kernel, dim3(1), dim3(256), 0, st, row_loss, loss, R, coef);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
+}
+
+extern "C" int mmvqa_supcon_loss(mmvqa_stream_t s, const float* f, float* loss, float* df, float* ws, int N, int D, float temp,
+                                 float base_temp, float gscale) {
+  return supcon((hipStream_t)s, f, nullptr, loss, df, ws, N, D, temp, base_temp, gscale);
+}
+extern "C" int mmvqa_supcon_loss_masked(mmvqa_stream_t s, const float* f, const float* mask, float* loss, float* df, float* ws,
+                                        int N, int D, float temp, float base_temp, float gscale) {
+  // a null mask is refused here: to the launcher it would mean the unmasked loss
+  if (!mask) return mmvqa_set_error(MMVQA_ERR_ARG, "supcon_masked: mask is null (mmvqa_supcon_loss is the loss without one)");
+  return supcon((hipStream_t)s, f, mask, loss, df, ws, N, D, temp, base_temp, gscale);
 }

@@ -200,14 +200,15 @@ __global__ __launch_bounds__(256) void tap_thin_bwd_kernel(const float* __restri
 
 }  // namespace
 
-bool k_tap_thin_ok(long M, int N, int C, int HW) {
+extern "C" int mmvqa_tap_thin_ok(long M, int N, int C, int HW) {
   return (C == 24 || C == 64) && M % 32 == 0 && HW % 32 == 0 && N % 4 == 0 && M / 32 >= 1024;
 }
 
 // out[img][n] += mean_hw act(sum_c x'[pix][c] W[n][c]),  x' = x or relu(x*sc+sh) (sc non-null); out is zeroed by the caller
-int k_tap_thin_fwd(hipStream_t st, const float* x, const float* sc, const float* sh, const float* W, float* out, long M,
-                   int N, int C, int HW, int act) {
-  if (!k_tap_thin_ok(M, N, C, HW)) return mmvqa_set_error(MMVQA_ERR_ARG, "tap_thin_fwd: M=%ld N=%d C=%d HW=%d", M, N, C, HW);
+extern "C" int mmvqa_tap_thin_fwd(mmvqa_stream_t s, const float* x, const float* sc, const float* sh, const float* W,
+                                  float* out, long M, int N, int C, int HW, int act) {
+  hipStream_t st = (hipStream_t)s;
+  if (!mmvqa_tap_thin_ok(M, N, C, HW)) return mmvqa_set_error(MMVQA_ERR_ARG, "tap_thin_fwd: M=%ld N=%d C=%d HW=%d", M, N, C, HW);
   const int ntiles = (int)(M / 32);
   const int gx = cdiv_i(N, 64);
   // about 4 waves per SIMD over the chip, every wave a contiguous run of row tiles (few image changes per wave)
@@ -230,9 +231,10 @@ int k_tap_thin_fwd(hipStream_t st, const float* x, const float* sc, const float*
 }
 
 // du[pix][n] = dv[img][n] / HW * act'(sum_c x'[pix][c] W[n][c])   (N a multiple of 4)
-int k_tap_thin_bwd(hipStream_t st, const float* x, const float* sc, const float* sh, const float* W, const float* dv,
-                   float* du, long M, int N, int C, int HW, int act) {
-  if (!k_tap_thin_ok(M, N, C, HW)) return mmvqa_set_error(MMVQA_ERR_ARG, "tap_thin_bwd: M=%ld N=%d C=%d HW=%d", M, N, C, HW);
+extern "C" int mmvqa_tap_thin_bwd(mmvqa_stream_t s, const float* x, const float* sc, const float* sh, const float* W,
+                                  const float* dv, float* du, long M, int N, int C, int HW, int act) {
+  hipStream_t st = (hipStream_t)s;
+  if (!mmvqa_tap_thin_ok(M, N, C, HW)) return mmvqa_set_error(MMVQA_ERR_ARG, "tap_thin_bwd: M=%ld N=%d C=%d HW=%d", M, N, C, HW);
   const int ntiles = (int)(M / 32);
   const int gx = cdiv_i(N, 64);
   int gy = cdiv_i(4096, gx);

@@ -64,12 +64,6 @@ static long long bert_add(mmvqa_bert* e, const std::string& name, long long d0, 
   return t.offset;
 }
 
-#define TRY(x)                     \
-  do {                             \
-    int _r = (x);                  \
-    if (_r != MMVQA_OK) return _r; \
-  } while (0)
-
 // y[M][N] = act(x[M][K] W^T + b), W [N][K]
 static int bert_linear(hipStream_t st, const float* x, int M, int K, const float* W, const float* b, int N, int act, float* y) {
   mmvqa_gemm_desc g;

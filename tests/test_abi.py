@@ -118,6 +118,67 @@ def test_supcon_refuses_bad_arguments_on_the_host():
     assert rc == -1 and err.startswith(b"supcon_masked: ") and b"mask is null" in err, (rc, err)
 
 
+def test_entry_points_refuse_bad_arguments_on_the_host():
+    """every argument check of an op entry point answers an ABI caller the same wherever the check lives: each row is
+    refused with MMVQA_ERR_ARG and its message before any HIP call (no GPU here, the pointers are never dereferenced)"""
+    from mmvqa_amd import _lib as L
+    lib = L.lib()
+    p, q = 0x1000, 0x2000
+
+    def gemm(**kw):
+        d = L.GemmDesc()
+        d.M, d.N, d.K = 64, 64, 64
+        d.A, d.B, d.C = 0x1000, 0x2000, 0x3000
+        d.a_ld, d.b_ld, d.c_ld, d.g_Cs = 64, 64, 64, 64
+        d.g_SH = d.g_SW = d.g_OH = d.g_OW = d.g_KH = d.g_KW = d.g_stride = 1
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return C.byref(d)
+
+    def attn(**kw):
+        d = L.AttnDesc()
+        d.q = d.k = d.v = d.out = d.mask = d.probs = d.dout = d.dq = d.dk = d.dv = p
+        d.row_stride = d.out_row_stride = 96
+        d.head_stride = d.out_head_stride = 8
+        d.B, d.T, d.heads, d.sqrt_d = 2, 16, 12, 8.0 ** 0.5
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return C.byref(d)
+
+    def fold(bwd):
+        f = L.BnFold()
+        f.stat, f.slots, f.bwd, f.count, f.gamma, f.beta = p, 1, bwd, 8.0, p, p
+        return C.byref(f)
+
+    dw = (p, p, p, p, p, p, 2, 8, 8)            # z1, s1, b1, w, z2, stat, N, H, W  (then C, OH, OW, stride, pad)
+    table = (
+        ("bn_add_relu", (None, p, p, p, q, None, None, p, 8, 6), b"bn_add_relu: C % 4 != 0"),
+        ("maxpool_fwd", (None, p, p, p, p, p, 2, 8, 8, 6, 4, 4), b"maxpool: C % 4 != 0"),
+        ("maxpool_bwd", (None, p, p, None, p, p, p, p, p, p, p, 2, 8, 8, 24, 4, 4), b"maxpool_bwd: C/4 must divide 256 (C=24)"),
+        ("qkv_attention_fwd", (None, p, p, p, p, p, p, p, 0, 16, 768, 12, 0.0, 1), b"qkv_attention_fwd: B=0 drop_p=0"),
+        ("qkv_attention_fwd", (None, p, p, p, p, p, p, p, 2, 16, 768, 12, 1.0, 1), b"qkv_attention_fwd: B=2 drop_p=1"),
+        ("amp_unscale", (None, None, 64, p, p, 1), b"amp_unscale: null pointer"),
+        ("amp_unscale", (None, p, 64, None, p, 1), b"amp_unscale: null pointer"),
+        ("amp_update_scale", (None, p, p, p, 2.0, 0.5, 0), b"amp_update_scale: growth_interval=0"),
+        ("pixmask", (None, None, 2, 4, 4, 8, 8, 3, 3, 2, 1), b"pixmask: null output"),
+        ("bn_add_relu_fold", (None, None, fold(0), q, None, p, 8, 64), b"bn_add_relu_fold: null operand"),
+        ("attention", (attn(q=None), 8, 0, None), b"attention: null operand"),
+        ("attention", (attn(row_stride=6), 8, 0, None), b"attention: strides must be multiples of 4"),
+        ("attention", (attn(dq=None), 8, 1, None), b"attention backward: null gradient pointer"),
+        ("fb_attention", (None, 0, None), b"fb_attention: null descriptor"),
+        ("igemm", (gemm(a_ld=6), L.KIND_FWD, 0, 0, None), b"igemm: a_ld=6 b_ld=64 g_Cs=64 must be multiples of 4"),
+        ("igemm", (gemm(N=6), L.KIND_DGRAD, 0, 0, None), b"igemm dgrad: N=6 must be a multiple of 4"),
+        ("dwconv_fwd", (None,) + dw + (48, 8, 8, 1, 1), b"dwconv: C=48 must be a multiple of 32"),
+        ("dwconv_fwd_fold", (None,) + dw + (32, 8, 8, 1, 1, fold(1)), b"dwconv: the fold must be a forward one"),
+        ("se_pool_fold", (None, p, p, p, p, 2, 64, 32, fold(1)), b"se_pool: the fold must be a forward one and C a multiple of 4"),
+        ("embed_bwd", (None, p, p, p, p, p, p, p, p, p, p, p, p, 2, 16, 6, 4, 0.0, 1, 0), b"embed: H=6 unsupported"),
+    )
+    for name, args, what in table:
+        rc = getattr(lib, "mmvqa_" + name)(*args)
+        err = lib.mmvqa_last_error()
+        assert rc == -1 and what in err, (name, what, rc, err)
+
+
 def test_missing_library_fails_loudly(monkeypatch):
     from mmvqa_amd import _lib as L
     monkeypatch.setattr(L, "_lib", None)
