@@ -540,6 +540,37 @@ int mmvqa_bn_act_add_fold(mmvqa_stream_t s, const float* z, const mmvqa_bn_fold*
 /* torch.optim.Adam defaults over a flat buffer; g is scaled by gscale first and zeroed when zero_grad != 0 */
 int mmvqa_adam(mmvqa_stream_t s, float* p, float* g, float* m, float* v, long n, double lr, double b1, double b2,
                double eps, int step, float gscale, int zero_grad);
+/* Adam with per-range learning rate, weight decay and mode (optimizer groups, no-decay tensors, frozen tensors) in ONE
+ * launch over [lo, lo + n) of the flat buffers.  p / g / m / v are the bases of the WHOLE buffers; segs is the table on
+ * the host, segs_dev the same table in device memory.  The caller uploads segs_dev when an entry changes (a learning
+ * rate step, a tensor frozen) and not otherwise: the step-dependent factors are derived from the launch arguments, in
+ * double as mmvqa_adam derives them, so the table does not change from step to step.  The call itself copies nothing
+ * and waits for nothing.
+ *   table: nseg entries (1..MMVQA_ADAM_MAX_SEGS), ascending, disjoint, non-empty, covering [0, end) without gaps with
+ *          lo + n <= end; begin / end are float indices and multiples of 4 (the engine aligns every tensor to 4 floats:
+ *          a 16-byte access never straddles two tensors).  Adjacent ranges with equal settings are merged by the caller.
+ *   mode:  MMVQA_ADAM_L2        g += weight_decay * p on the scaled gradient (torch.optim.Adam(weight_decay=))
+ *          MMVQA_ADAM_DECOUPLED p *= 1 - lr * weight_decay before the update (torch.optim.AdamW)
+ *          MMVQA_ADAM_FROZEN    p, m, v are neither read nor written; g is zeroed when zero_grad != 0
+ * betas, eps, step, gscale and zero_grad are shared by all segments.  One segment of mode 0 with weight_decay 0 gives
+ * the bits of mmvqa_adam, and launches over pieces of a range give the bits of one launch over the range.
+ * Refused on the host with MMVQA_ERR_ARG before any HIP call: a null pointer, lo or n negative or no multiple of 4, nseg
+ * outside 1..MMVQA_ADAM_MAX_SEGS, a table that is unsorted, overlapping, gapped, misaligned or shorter than lo + n, an
+ * unknown mode. */
+#define MMVQA_ADAM_L2 0
+#define MMVQA_ADAM_DECOUPLED 1
+#define MMVQA_ADAM_FROZEN 2
+#define MMVQA_ADAM_MAX_SEGS 4096
+typedef struct mmvqa_adam_seg {
+  long long begin, end;       /* [begin, end) in floats from the base of the buffers */
+  double lr, weight_decay;
+  int mode;                   /* MMVQA_ADAM_* */
+  int reserved;               /* 0 */
+} mmvqa_adam_seg;
+size_t mmvqa_sizeof_adam_seg(void);
+int mmvqa_adam_groups(mmvqa_stream_t s, float* p, float* g, float* m, float* v, long lo, long n,
+                      const mmvqa_adam_seg* segs, const mmvqa_adam_seg* segs_dev, int nseg, double b1, double b2,
+                      double eps, int step, float gscale, int zero_grad);
 /* loss scaling (torch.amp.GradScaler semantics): found_inf[0] = 1 if any of g[0..n) is inf / nan (left as it is
  * otherwise); with multiply != 0 also g *= inv_scale[0] in place.  Device pointers. */
 int mmvqa_amp_unscale(mmvqa_stream_t s, float* g, long n, const float* inv_scale, float* found_inf, int multiply);
@@ -624,6 +655,23 @@ int mmvqa_engine_tune(mmvqa_engine* e, int enable);
  * The fused QKV + attention launch is replaced by the unfused route in f16 mode.  ResNet encoders only: an
  * EfficientNet engine refuses MMVQA_PREC_F16 (MMVQA_ERR_ARG). */
 int mmvqa_engine_set_precision(mmvqa_engine* e, int mode);
+/* Frozen backbone (the reference's commented-out `for p in self.parameters(): p.requires_grad = False`,
+ * models/image_encoding.py:50-51).  flags are read by the next forward and recorded for its backward, as the precision
+ * mode is; 0 (the default) is the full backward.
+ *   MMVQA_FREEZE_BACKBONE: the parameters of the CNN body (transformer.trans.model.*, the floats between the embedding
+ *     block and the first tap weight) receive no gradient.  The backward runs heads, encoder and the embedding as
+ *     always, then only the weight gradient of the five taps (recompute of du, dW_tap; no data gradient), on the
+ *     caller's stream: no convolution data or weight gradient, no BatchNorm-backward coefficients, no max-pool,
+ *     depthwise or squeeze-excite backward.  The gradient callback still partitions the whole buffer; the frozen range
+ *     is announced as it stands (this call never writes it).  The forward is unchanged: train-mode BatchNorm keeps
+ *     using batch statistics and updating the running ones, as torch does with requires_grad=False under .train().
+ *   MMVQA_FREEZE_BN_STATS (only with MMVQA_FREEZE_BACKBONE): the backbone's BatchNorms use their running statistics and
+ *     leave running_mean / running_var / num_batches_tracked alone (backbone.eval()); dropout and everything outside
+ *     the backbone stay as `training` says.
+ * Any other bit, or MMVQA_FREEZE_BN_STATS alone, is refused with MMVQA_ERR_ARG and changes nothing. */
+#define MMVQA_FREEZE_BACKBONE 1
+#define MMVQA_FREEZE_BN_STATS 2
+int mmvqa_engine_set_frozen(mmvqa_engine* e, int flags);
 /* per-kernel-class timing (HIP events on the launch stream) of the NEXT forward+backward:
  * enable, run, then read back {n_launches, total_ms, algorithmic_flops} per class.
  * enable = 1: as the step normally runs (weight-gradient GEMMs on the second stream beside the data-gradient chain, so

@@ -22,6 +22,9 @@ EPI_PLAIN, EPI_TAP_FWD, EPI_TAP_BWD = 0, 1, 2
 PREC_F32, PREC_F16 = 0, 1   # mmvqa_gemm_desc.reserved0 / mmvqa_engine_set_precision
 SOFT_CE_HARD, SOFT_CE_UNIFORM, SOFT_CE_CATEGORY = 0, 1, 2   # mmvqa_soft_ce_loss modes
 HEAD_MLM, HEAD_VQA, HEAD_NONE = 0, 1, 2   # mmvqa_model_desc.head_kind
+ADAM_L2, ADAM_DECOUPLED, ADAM_FROZEN = 0, 1, 2   # mmvqa_adam_seg.mode
+ADAM_MAX_SEGS = 4096
+FREEZE_BACKBONE, FREEZE_BN_STATS = 1, 2   # mmvqa_engine_set_frozen
 STAT_SLOTS = 16
 
 
@@ -121,6 +124,12 @@ class ModelDesc(C.Structure):
     ]
 
 
+class AdamSeg(C.Structure):
+    """mirror of mmvqa_adam_seg"""
+    _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong), ("lr", C.c_double), ("weight_decay", C.c_double),
+                ("mode", C.c_int), ("reserved", C.c_int)]
+
+
 class BertDesc(C.Structure):
     """mirror of mmvqa_bert_desc"""
     _fields_ = [
@@ -193,6 +202,8 @@ SIGNATURES = {
     "mmvqa_act_bwd_stats": (_i, [_P] * 9 + [_i, _P, _P, _l, _i, _i]),
     "mmvqa_bn_act_add": (_i, [_P, _P, _P, _P, _i, _P, _P, _P, _i, _i, _P, _l, _i]),
     "mmvqa_adam": (_i, [_P, _P, _P, _P, _P, _l, _d, _d, _d, _d, _i, _f, _i]),
+    "mmvqa_sizeof_adam_seg": (_sz, []),
+    "mmvqa_adam_groups": (_i, [_P, _P, _P, _P, _P, _l, _l, _P, _P, _i, _d, _d, _d, _i, _f, _i]),
     "mmvqa_axpy": (_i, [_P, _P, _P, _f, _l]),
     "mmvqa_colsum": (_i, [_P, _P, _i, _i, _i, _P]),
     "mmvqa_dropout": (_i, [_P, _P, _l, _f, _u32]),
@@ -239,6 +250,7 @@ SIGNATURES = {
     "mmvqa_amp_unscale": (_i, [_P, _P, _l, _P, _P, _i]),
     "mmvqa_amp_update_scale": (_i, [_P, _P, _P, _P, _d, _d, _i]),
     "mmvqa_engine_set_precision": (_i, [_P, _i]),
+    "mmvqa_engine_set_frozen": (_i, [_P, _i]),
     "mmvqa_engine_profile": (_i, [_P, _i]),
     "mmvqa_engine_profile_read": (_i, [_P, _i, C.POINTER(_ll), C.POINTER(_d), C.POINTER(_d)]),
     "mmvqa_engine_profile_read_region": (_i, [_P, _i, _i, C.POINTER(_ll), C.POINTER(_d), C.POINTER(_d)]),
@@ -276,6 +288,8 @@ def lib():
         got = getattr(L, f"mmvqa_sizeof_{nm}_desc")()
         if got != C.sizeof(st):
             raise MMVQAError(f"ABI mismatch: sizeof(mmvqa_{nm}_desc) = {got} in the library, {C.sizeof(st)} in Python")
+    if L.mmvqa_sizeof_adam_seg() != C.sizeof(AdamSeg):
+        raise MMVQAError(f"ABI mismatch: sizeof(mmvqa_adam_seg) = {L.mmvqa_sizeof_adam_seg()} in the library, {C.sizeof(AdamSeg)} in Python")
     _lib = L
     return L
 

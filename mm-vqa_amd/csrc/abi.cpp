@@ -97,6 +97,14 @@ int mmvqa_engine_set_precision(mmvqa_engine* e, int mode) {
   e->prec = mode;
   return MMVQA_OK;
 }
+int mmvqa_engine_set_frozen(mmvqa_engine* e, int flags) {
+  if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "set_frozen: null engine");
+  if ((flags & ~(MMVQA_FREEZE_BACKBONE | MMVQA_FREEZE_BN_STATS)) || flags == MMVQA_FREEZE_BN_STATS)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "set_frozen: flags=%d (1 = backbone without gradient, 3 = and its BatchNorms on "
+                                          "running statistics)", flags);
+  e->frozen_next = flags;
+  return MMVQA_OK;
+}
 int mmvqa_engine_tune(mmvqa_engine* e, int enable) {
   if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "tune: null engine");
   if (enable != 0 && enable != 1) return mmvqa_set_error(MMVQA_ERR_ARG, "tune: enable=%d is neither 0 nor 1", enable);

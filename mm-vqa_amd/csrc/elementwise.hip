@@ -812,6 +812,109 @@ __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float*
   }
 }
 
+// Adam over a segment table (mmvqa_adam_groups): the streaming structure of adam_kernel<2>, with the learning rate, the
+// weight decay and the mode of an element looked up in `segs` (ascending, disjoint, covering the range; every bound a
+// multiple of 4 floats, so a float4 lies in one segment).  p / g / m / v are the bases of the WHOLE buffers and
+// [lo4, lo4 + n4) the float4 range of this launch, so that a ranged launch finds its elements in the global table.
+// Lookup: the 64 lanes of a wave hold 64 consecutive float4.  The wave's first index is made uniform (readfirstlane)
+// and searched with scalar loads and scalar branches; when the wave's last float4 ends inside the same segment, which
+// is every wave but the few that straddle a boundary, that is the whole lookup.  A straddling wave walks forward from
+// there lane by lane.  The per-segment factors are derived where mmvqa_adam derives them, in double from the launch
+// arguments (step_size = float(lr / bc1), decay = float(1 - lr wd)), and kept while the thread stays in one segment.
+struct AdamSegF { float step_size, wd, decay; int mode; };
+__device__ __forceinline__ AdamSegF adam_seg_factors(const mmvqa_adam_seg* __restrict__ segs, int s, double bc1) {
+  const double lr = segs[s].lr, wd = segs[s].weight_decay;
+  AdamSegF f;
+  f.mode = segs[s].mode;
+  f.step_size = (float)(lr / bc1);
+  f.wd = f.mode == MMVQA_ADAM_L2 ? (float)wd : 0.f;
+  f.decay = f.mode == MMVQA_ADAM_DECOUPLED ? (float)(1.0 - lr * wd) : 1.f;
+  return f;
+}
+__global__ void adam_groups_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                   float* __restrict__ v, long lo4, long n4, const mmvqa_adam_seg* __restrict__ segs,
+                                   int nseg, double bc1, float b1, float omb1, float b2, float omb2, float eps,
+                                   float bc2_sqrt, float gscale, int zero_grad) {
+  constexpr int U = 2;
+  const long stride = (long)gridDim.x * blockDim.x;
+  const int lane = threadIdx.x & 63;
+  // the roundings of adam_kernel's `upd`, with the two weight-decay forms in front: L2 adds wd p to the scaled gradient
+  // (torch.optim.Adam), the decoupled form shrinks p first (torch.optim.AdamW: p.mul_(1 - lr wd))
+  auto upd = [&](const AdamSegF& f, f32x4& pv, const f32x4& gv, f32x4& mv, f32x4& vv) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float gg = gv[e] * gscale;
+      float pp = pv[e];
+      if (f.wd != 0.f) gg = fmaf(f.wd, pp, gg);
+      if (f.mode == MMVQA_ADAM_DECOUPLED) pp = pp * f.decay;
+      mv[e] = fmaf(gg - mv[e], omb1, mv[e]);
+      vv[e] = fmaf(gg * gg, omb2, vv[e] * b2);
+      const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
+      pv[e] = fmaf(-f.step_size, mv[e] / denom, pp);
+    }
+  };
+  // segment of float4 j (absolute); cs / cf: the segment this slot of the thread was in last and its factors
+  auto lookup = [&](long j, int& cs, AdamSegF& cf) __attribute__((always_inline)) {
+    const long jw = j - lane;   // the wave's first float4: lanes are consecutive, the lowest active lane is lane 0
+    const long fw = 4 * (((long)__builtin_amdgcn_readfirstlane((int)(jw >> 32)) << 32) |
+                         (unsigned)__builtin_amdgcn_readfirstlane((int)jw));
+    int a = 0, b = nseg - 1;    // first segment whose end lies beyond fw
+    while (a < b) {
+      const int mid = (a + b) >> 1;
+      if (segs[mid].end > fw) b = mid; else a = mid + 1;
+    }
+    if (fw + 256 <= segs[a].end) {          // the whole wave in one segment
+      if (a != cs) { cf = adam_seg_factors(segs, a, bc1); cs = a; }
+    } else {
+      int s = a;
+      while (s < nseg - 1 && 4 * j >= segs[s].end) ++s;
+      cf = adam_seg_factors(segs, s, bc1);
+      cs = -1;
+    }
+  };
+  f32x4* P4 = reinterpret_cast<f32x4*>(p); f32x4* G4 = reinterpret_cast<f32x4*>(g);
+  f32x4* M4 = reinterpret_cast<f32x4*>(m); f32x4* V4 = reinterpret_cast<f32x4*>(v);
+  const f32x4 zero = {0, 0, 0, 0};
+  const long end4 = lo4 + n4;
+  int cs[U];
+  AdamSegF cf[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) cs[u] = -1;
+  long i = lo4 + (long)blockIdx.x * blockDim.x + threadIdx.x;
+  for (; i + (U - 1) * stride < end4; i += U * stride) {
+    f32x4 pv[U], gv[U], mv[U], vv[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long j = i + u * stride;
+      lookup(j, cs[u], cf[u]);
+      if (cf[u].mode != MMVQA_ADAM_FROZEN) {
+        pv[u] = P4[j]; gv[u] = G4[j]; mv[u] = __builtin_nontemporal_load(M4 + j); vv[u] = __builtin_nontemporal_load(V4 + j);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (cf[u].mode != MMVQA_ADAM_FROZEN) upd(cf[u], pv[u], gv[u], mv[u], vv[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const long j = i + u * stride;
+      if (cf[u].mode != MMVQA_ADAM_FROZEN) {
+        P4[j] = pv[u]; __builtin_nontemporal_store(mv[u], M4 + j); __builtin_nontemporal_store(vv[u], V4 + j);
+      }
+      if (zero_grad) G4[j] = zero;
+    }
+  }
+  for (; i < end4; i += stride) {
+    lookup(i, cs[0], cf[0]);
+    if (cf[0].mode != MMVQA_ADAM_FROZEN) {
+      f32x4 p0 = P4[i], g0 = G4[i], m0 = M4[i], v0 = V4[i];
+      upd(cf[0], p0, g0, m0, v0);
+      P4[i] = p0; M4[i] = m0; V4[i] = v0;
+    }
+    if (zero_grad) G4[i] = zero;
+  }
+}
+
 __global__ void axpy_kernel(float* __restrict__ y, const float* __restrict__ x, float a, long n) {
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   long stride = (long)gridDim.x * blockDim.x;
@@ -1147,6 +1250,43 @@ extern "C" int mmvqa_adam(mmvqa_stream_t s, float* p, float* g, float* m, float*
                      (float)sqrt(bc2), gscale, zero_grad)
   if (unroll >= 4) ADAM_GO(4); else if (unroll == 3) ADAM_GO(3); else if (unroll == 1) ADAM_GO(1); else ADAM_GO(2);
 #undef ADAM_GO
+  KERNEL_CHECK_RET();
+  return MMVQA_OK;
+}
+
+extern "C" size_t mmvqa_sizeof_adam_seg(void) { return sizeof(mmvqa_adam_seg); }
+
+extern "C" int mmvqa_adam_groups(mmvqa_stream_t s, float* p, float* g, float* m, float* v, long lo, long n,
+                                 const mmvqa_adam_seg* segs, const mmvqa_adam_seg* segs_dev, int nseg, double b1,
+                                 double b2, double eps, int step, float gscale, int zero_grad) {
+  hipStream_t st = (hipStream_t)s;
+  // everything the kernel's addressing relies on is checked here, on the host copy of the table, before any HIP call
+  if (!p || !g || !m || !v || !segs || !segs_dev) return mmvqa_set_error(MMVQA_ERR_ARG, "adam_groups: null pointer");
+  if (nseg < 1 || nseg > MMVQA_ADAM_MAX_SEGS)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "adam_groups: nseg=%d outside 1..%d", nseg, MMVQA_ADAM_MAX_SEGS);
+  if (lo < 0 || n < 0 || lo % 4 != 0 || n % 4 != 0)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "adam_groups: lo=%ld n=%ld must be non-negative multiples of 4", lo, n);
+  long long pos = 0;
+  for (int i = 0; i < nseg; ++i) {
+    const mmvqa_adam_seg& sg = segs[i];
+    if (sg.begin % 4 != 0 || sg.end % 4 != 0)
+      return mmvqa_set_error(MMVQA_ERR_ARG, "adam_groups: segment %d [%lld, %lld) is not aligned to 4 floats", i, sg.begin, sg.end);
+    if (sg.begin != pos || sg.end <= sg.begin)
+      return mmvqa_set_error(MMVQA_ERR_ARG, "adam_groups: segment %d [%lld, %lld) does not continue the table at %lld (segments "
+                             "are ascending, disjoint, non-empty and without gaps from 0)", i, sg.begin, sg.end, pos);
+    if (sg.mode != MMVQA_ADAM_L2 && sg.mode != MMVQA_ADAM_DECOUPLED && sg.mode != MMVQA_ADAM_FROZEN)
+      return mmvqa_set_error(MMVQA_ERR_ARG, "adam_groups: segment %d has unknown mode %d", i, sg.mode);
+    pos = sg.end;
+  }
+  if ((long long)lo + n > pos)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "adam_groups: [%ld, %ld) reaches beyond the table's %lld floats", lo, lo + n, pos);
+  if (n == 0) return MMVQA_OK;
+  const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);   // as mmvqa_adam
+  const char* cap_s = getenv("MMVQA_ADAM_WGS");
+  const int cap = cap_s ? atoi(cap_s) : 16384;
+  hipLaunchKernelGGL(adam_groups_kernel, dim3(grid_for(n / 4, 256, cap > 0 ? cap : 16384)), dim3(256), 0, st, p, g, m, v,
+                     lo / 4, n / 4, segs_dev, nseg, bc1, (float)b1, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2),
+                     (float)eps, (float)sqrt(bc2), gscale, zero_grad);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }

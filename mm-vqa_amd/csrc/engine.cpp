@@ -653,7 +653,7 @@ static int bn_coef_fwd(mmvqa_engine* e, hipStream_t st, BNRef& bn) {
   REG(REG_BNCOEF);
   RUN(PROF_OTHER, 0,
       mmvqa_bn_coef_fwd(st, stat_ptr(e, bn.stat_f), bn.C, bn.count, bn.eps, PRM(bn.gamma), PRM(bn.beta),
-                    e->bufs + bn.rmean, e->bufs + bn.rvar, e->nbt + bn.nbt, 0.1f, bn.reps, e->training,
+                    e->bufs + bn.rmean, e->bufs + bn.rvar, e->nbt + bn.nbt, 0.1f, bn.reps, e->bn_training,
                     WS(bn.scale), WS(bn.shift), WS(bn.mean), WS(bn.invstd)));
   return MMVQA_OK;
 }
@@ -661,16 +661,16 @@ static int bn_coef_bwd(mmvqa_engine* e, hipStream_t st, BNRef& bn) {
   REG(REG_BNCOEF);
   RUN(PROF_OTHER, 0,
       mmvqa_bn_coef_bwd(st, stat_ptr(e, bn.stat_b), bn.C, bn.count, PRM(bn.gamma), WS(bn.mean), WS(bn.invstd),
-                    e->training, WS(bn.P), WS(bn.Q), WS(bn.R), GRD(bn.gamma), GRD(bn.beta)));
+                    e->bn_training, WS(bn.P), WS(bn.Q), WS(bn.R), GRD(bn.gamma), GRD(bn.beta)));
   return MMVQA_OK;
 }
 
 // The ResNet path in training mode folds the BatchNorm coefficients inside the launches that consume them
 // (mmvqa_bn_fold: no coefficient launch between a convolution and its consumer on the dependency chain).
-static inline bool folding(const mmvqa_engine* e) { return e->bn_fold && e->training && e->d.cnn == 0; }
+static inline bool folding(const mmvqa_engine* e) { return e->bn_fold && e->bn_training && e->d.cnn == 0; }
 // The EfficientNet path folds where the FIRST consumer of a BatchNorm is an elementwise kernel (block end, depthwise
 // convolution, squeeze-excite pooling: forward) -- later consumers read what that launch published.
-static inline bool eff_folding(const mmvqa_engine* e) { return e->bn_fold && e->training && e->d.cnn != 0; }
+static inline bool eff_folding(const mmvqa_engine* e) { return e->bn_fold && e->bn_training && e->d.cnn != 0; }
 
 static void set_fold_fwd(mmvqa_engine* e, mmvqa_bn_fold& f, BNRef& bn) {
   memset(&f, 0, sizeof(f));
@@ -714,7 +714,7 @@ static int conv_fwd(mmvqa_engine* e, hipStream_t st, const ConvRef& c, const flo
   conv_geom(g, c, H, W, c.Cin, OH, OW);
   g.B = PRM(c.w); g.b_ld = g.K;
   g.C = z; g.c_ld = c.Cout;
-  if (e->training) { g.stat1 = stat_ptr(e, bn_out.stat_f); g.stat_bwd = 0; g.stat_slots = bn_out.slots; }
+  if (e->bn_training) { g.stat1 = stat_ptr(e, bn_out.stat_f); g.stat_bwd = 0; g.stat_slots = bn_out.slots; }
   set_sk(e, st, g);
   RUN(PROF_IGEMM, 2.0 * g.M * g.N * g.K, mmvqa_launch_igemm(g, KIND_FWD, 0, 0, st));
   return folding(e) || !coef ? MMVQA_OK : bn_coef_fwd(e, st, bn_out);
@@ -780,7 +780,7 @@ static GemmParams stem_desc(mmvqa_engine* e, int kind, const float* g0 = nullptr
     g.A = e->img;
     g.B = PRM(c.w); g.b_ld = taps;
     g.C = WS(e->z0); g.c_ld = c.Cout;
-    if (e->training) g.stat1 = stat_ptr(e, e->stem_bn.stat_f);
+    if (e->bn_training) g.stat1 = stat_ptr(e, e->stem_bn.stat_f);
   } else {
     g.M = c.Cout; g.N = taps; g.K = pixels;
     g.A = g0; g.A2 = WS(e->z0); g.a_ld = c.Cout; g.a_pro = PRO_DZ;
@@ -835,9 +835,10 @@ static int tap_fwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
 }
 
 // backward of one tap: du (recompute), dW_tap, and the gradient wrt the feature map (T_k or masked G)
-// (data_only: the recompute and the data gradient, no weight gradient -- mmvqa_engine_backward_feature)
+// (data_only: the recompute and the data gradient, no weight gradient -- mmvqa_engine_backward_feature;
+//  weight_only, its mirror: the recompute and dW_tap, no data gradient and dfmap unused -- the frozen backbone)
 static int tap_bwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, const BNRef* bn_in, float* dfmap,
-                   const EpiOpt& o, bool data_only = false) {
+                   const EpiOpt& o, bool data_only = false, bool weight_only = false) {
   REG(REG_TAP);
   const TapRef& t = e->taps[k];
   const int Hd = e->d.hidden;
@@ -863,6 +864,7 @@ static int tap_bwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
   w.C = GRD(t.w); w.c_ld = t.C; w.c_atomic = 1;
   RUN(PROF_IGEMM, 2.0 * (double)w.M * w.N * w.K, mmvqa_launch_igemm(w, KIND_WGRAD, 0, 0, st));
   }
+  if (weight_only) return MMVQA_OK;
   // dfmap[M][C] = du W_tap
   GemmParams dg = gp_linear_geom();
   dg.M = (int)t.M; dg.N = t.C; dg.K = Hd;
@@ -1016,7 +1018,7 @@ static int notify(mmvqa_engine* e, SideCtx& sc, long long lo, long long hi) {
 static int resnet_forward(mmvqa_engine* e, hipStream_t st) {
   const mmvqa_model_desc& d = e->d;
   const int B = e->B, w = d.resnet_width;
-  if (e->training)
+  if (e->bn_training)
     HIP_CHECK_RET(hipMemsetAsync(stat_ptr(e, 0), 0, e->statzone_floats / 2 * sizeof(float), st));
   HIP_CHECK_RET(hipMemsetAsync(WS(e->vis), 0, (size_t)5 * B * d.hidden * sizeof(float), st));
   {  // stem 7x7/2 on the NCHW image
@@ -1217,11 +1219,32 @@ static int resnet_backward(mmvqa_engine* e, hipStream_t st) {
   return MMVQA_OK;
 }
 
+// Backward of a frozen backbone (MMVQA_FREEZE_BACKBONE): nothing below the taps receives a gradient, so no gradient has to
+// reach a feature map.  What is left is the weight gradient of the five taps, from the feature maps the forward kept.
+// The taps share the `du` scratch, so they run one after the other, and there is nothing to run beside them: all on the
+// caller's stream, no side stream to join before the announcements.
+static int frozen_backbone_backward(mmvqa_engine* e, hipStream_t st) {
+  if (e->d.cnn == 1) {
+    for (auto& b : e->eff)
+      if (b.feature >= 0) TRY(tap_bwd(e, st, b.feature, WS(b.out), nullptr, nullptr, EpiOpt(), false, true));
+  } else {
+    TRY(tap_bwd(e, st, 0, WS(e->blocks.back().out), nullptr, nullptr, EpiOpt(), false, true));
+    for (int k = 1; k <= 3; ++k)
+      TRY(tap_bwd(e, st, k, WS(e->blocks[e->layer_end[3 - k]].out), nullptr, nullptr, EpiOpt(), false, true));
+    TRY(tap_bwd(e, st, 4, WS(e->z0), &e->stem_bn, nullptr, EpiOpt(), false, true));
+  }
+  if (e->grad_cb) {
+    e->grad_cb(e->grad_cb_user, e->taps[0].w, e->enc_lo);   // tap weights
+    e->grad_cb(e->grad_cb_user, e->emb_hi, e->taps[0].w);   // the frozen range, as it stands: this backward wrote none of it
+  }
+  return MMVQA_OK;
+}
+
 // --------------------------------------------------------------------------- EfficientNetV2 forward / backward
 static int effnet_forward(mmvqa_engine* e, hipStream_t st) {
   const mmvqa_model_desc& d = e->d;
   const int B = e->B;
-  if (e->training)
+  if (e->bn_training)
     HIP_CHECK_RET(hipMemsetAsync(stat_ptr(e, 0), 0, e->statzone_floats / 2 * sizeof(float), st));
   HIP_CHECK_RET(hipMemsetAsync(WS(e->vis), 0, (size_t)5 * B * d.hidden * sizeof(float), st));
   const long M0 = (long)B * e->SH * e->SW;
@@ -1261,7 +1284,7 @@ static int effnet_forward(mmvqa_engine* e, hipStream_t st) {
       if (fold) { set_fold_fwd(e, fa, b.b_a); set_fold_fwd(e, fdw, b.b_dw); }
       TRY(conv_fwd(e, st, b.c_a, x, {}, B, b.H, b.W, b.H, b.W, WS(b.za), b.b_a, !fold));
       RUNB(HB_DWCONV_FWD, 4.0 * ((double)B * b.H * b.W + (double)Mout) * b.mid, mmvqa_dwconv_fwd_fold(st, WS(b.za), WS(b.b_a.scale), WS(b.b_a.shift), PRM(b.dw_w), WS(b.zdw),
-                                      e->training ? stat_ptr(e, b.b_dw.stat_f) : nullptr, B, b.H, b.W, b.mid, b.OH, b.OW,
+                                      e->bn_training ? stat_ptr(e, b.b_dw.stat_f) : nullptr, B, b.H, b.W, b.mid, b.OH, b.OW,
                                       b.stride, b.pad, fold ? &fa : nullptr));
       if (!fold) TRY(bn_coef_fwd(e, st, b.b_dw));
       // squeeze-excite: gate = sigmoid(W_e silu(W_r mean_hw(a2) + b_r) + b_e)
@@ -1908,6 +1931,10 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
   e->img = img; e->ids = ids; e->seg = seg; e->mask = mask;
   e->logits = logits; e->logits_ld = logits_ld; e->feat = feat;
   e->training = training; e->seed = seed;
+  e->frozen = e->frozen_next;
+  // `training` means dropout everywhere and batch statistics in the backbone's BatchNorms; the two part only under
+  // MMVQA_FREEZE_BN_STATS (backbone.eval() inside model.train())
+  e->bn_training = training && !(e->frozen & MMVQA_FREEZE_BN_STATS);
   if (e->prec != MMVQA_PREC_F32 && d.cnn != 0)
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward: f16 operand mode covers the ResNet encoders only");
   StepScope scope(e, e->prec);
@@ -1959,6 +1986,7 @@ int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int d
                   WS(e->dvis), e->B, e->T, d.hidden, d.num_vis, pe, site_seed(e, 100, 0), 0));
   e->prof_reg = REG_BACKBONE;
   if (e->grad_cb) e->grad_cb(e->grad_cb_user, 0, e->emb_hi);            // embedding tables + LayerNorm
+  if (e->frozen & MMVQA_FREEZE_BACKBONE) return frozen_backbone_backward(e, st);
   return d.cnn == 1 ? effnet_backward(e, st) : resnet_backward(e, st);
 }
 

@@ -157,7 +157,10 @@ struct mmvqa_engine {
   // ---- step state
   const long long *ids = nullptr, *seg = nullptr, *mask = nullptr;
   const float* img = nullptr;
-  int training = 0;
+  int training = 0;      // dropout (and everything else outside the backbone's BatchNorms) of the last forward
+  int bn_training = 0;   // the backbone's BatchNorms used batch statistics: = training unless MMVQA_FREEZE_BN_STATS
+  int frozen = 0;        // MMVQA_FREEZE_* of the last forward: its backward reads them here
+  int frozen_next = 0;   // mmvqa_engine_set_frozen: taken by the next forward
   uint32_t seed = 0;
   float* logits = nullptr;
   int logits_ld = 0;

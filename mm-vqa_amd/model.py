@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import operator
 
 import torch
 import torch.nn as nn
@@ -31,6 +32,9 @@ _NEVER_USED = ("transformer.blocks.norm2.", "transformer.trans.model.fc.",
 # the Feedback Transformer's one to_kv weight (feedback_transformer_pytorch.py:229-230,246): the engine lists it under the
 # reference's first name; the reference's state_dict carries it under every layer's name and as shared_kv_proj
 _FB = "transformer.block."
+_BACKBONE = "transformer.trans.model."   # the CNN body (models/image_encoding.py:43-62); the five tap convolutions are not in it
+_NOT_FROZEN = (0, ())
+_REQUIRES_GRAD = operator.attrgetter("requires_grad")
 _FB_KV = _FB + "layers.0.0.fn.fn.to_kv.weight"
 
 
@@ -119,15 +123,16 @@ class _HeadSeq(_Node):
 
 class _ModelFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, model, anchor, img, ids, seg, mask, prec):
+    def forward(ctx, model, anchor, img, ids, seg, mask, prec, frozen):
         ctx.model = model
         ctx.prec = prec
-        return model._engine_forward(img, ids, seg, mask, prec)
+        ctx.frozen = frozen   # (engine flags, [lo, hi) ranges of flat_grads without gradient) as this forward read them
+        return model._engine_forward(img, ids, seg, mask, prec, frozen[0])
 
     @staticmethod
     def backward(ctx, *grads):
-        ctx.model._engine_backward(*grads, prec=ctx.prec)
-        return (None,) * 7
+        ctx.model._engine_backward(*grads, prec=ctx.prec, frozen=ctx.frozen)
+        return (None,) * 8
 
 
 def autocast_precision(model_desc) -> int:
@@ -159,6 +164,7 @@ class Model(nn.Module):
         self._ws = None
         self._seed_ctr = 0
         self._fwd_state = None
+        self._bn_stats_running = False
         dev = torch.device(device) if device is not None else torch.device("cpu")
         self._build(desc_from_args(args, feat_dim), dev, init=True)
 
@@ -344,12 +350,67 @@ class Model(nn.Module):
         return self._flat_grad
 
     def attach_grads(self):
-        """make every used parameter's .grad a view of the flat gradient buffer"""
+        """make the .grad of every used parameter that requires a gradient a view of the flat gradient buffer"""
         for name, kind, shp, off, cl in self._table:
             if kind == 0 and not name.startswith(_NEVER_USED):
                 p = self._params_by_name[name]
-                if p.grad is None:
+                if p.grad is None and p.requires_grad:
                     p.grad = self._view(self._flat_grad, shp, off, cl)
+
+    # ------------------------------------------------------------------ frozen parameters
+    def _frozen_state(self):
+        """(engine flags, merged [lo, hi) ranges of the flat buffers whose parameters have requires_grad=False), read
+        from the parameters now; _NOT_FROZEN when every parameter requires a gradient"""
+        tab = self._param_ranges()
+        if all(map(_REQUIRES_GRAD, self._ranges[2])):
+            return _NOT_FROZEN
+        ranges, backbone = [], True
+        for name, p, lo, hi in tab:
+            if p.requires_grad:
+                backbone = backbone and not name.startswith(_BACKBONE)
+            elif ranges and ranges[-1][1] == lo:
+                ranges[-1][1] = hi
+            else:
+                ranges.append([lo, hi])
+        flags = 0
+        if backbone:
+            flags = L.FREEZE_BACKBONE | (L.FREEZE_BN_STATS if self._bn_stats_running else 0)
+        return flags, tuple((lo, hi) for lo, hi in ranges)
+
+    def _param_ranges(self):
+        """[(name, parameter, lo, hi)] in buffer order; [lo, hi) runs to the next tensor (each starts on a multiple of 4
+        floats), so the ranges partition the flat parameter buffer"""
+        tab = getattr(self, "_ranges", None)
+        if tab is None or tab[0] is not self._table:
+            prm = sorted((off, name) for name, kind, _, off, _ in self._table if kind == 0)
+            ends = [o for o, _ in prm[1:]] + [self._flat[0].numel()]
+            rows = [(name, self._params_by_name[name], off, hi) for (off, name), hi in zip(prm, ends)]
+            tab = self._ranges = (self._table, rows, tuple(r[1] for r in rows))
+        return tab[1]
+
+    def freeze_backbone(self, bn_stats="batch"):
+        """The reference's commented-out freeze (models/image_encoding.py:50-51): requires_grad_(False) on every
+        parameter of the CNN body, transformer.trans.model.* (the five tap convolutions keep training).  Their .grad
+        becomes None, and training forwards skip the backbone's backward pass.  bn_stats="batch": BatchNorm keeps
+        normalising with batch statistics and updating the running ones, which is what torch does with frozen
+        parameters under .train().  bn_stats="running": the backbone's BatchNorms use their running statistics and leave
+        them alone (the backbone.eval() half of the usual freeze); dropout and the rest of the model stay in training
+        mode."""
+        if bn_stats not in ("batch", "running"):
+            raise ValueError(f"freeze_backbone: bn_stats={bn_stats!r} is neither 'batch' nor 'running'")
+        for name, p in self._params_by_name.items():
+            if name.startswith(_BACKBONE):
+                p.requires_grad_(False)
+                p.grad = None
+        self._bn_stats_running = bn_stats == "running"
+        return self
+
+    def unfreeze_backbone(self):
+        for name, p in self._params_by_name.items():
+            if name.startswith(_BACKBONE):
+                p.requires_grad_(True)
+        self._bn_stats_running = False
+        return self
 
     # ------------------------------------------------------------------ engine calls
     def _ensure_plan(self, B, T, IH, IW):
@@ -370,7 +431,7 @@ class Model(nn.Module):
         """dropout stream for training-mode forwards (counter-based RNG in the kernels)"""
         self._seed_ctr = int(seed) & 0x7FFFFFFF
 
-    def _engine_forward(self, img, ids, seg, mask, prec=0):
+    def _engine_forward(self, img, ids, seg, mask, prec=0, frozen_flags=0):
         d = self._desc
         if d.encoder == L.ENC_FEEDBACK and not 2 <= ids.shape[1] <= L.FB_MAX_T:
             raise ValueError(f"the feedback-transformer takes 2 <= T <= {L.FB_MAX_T} tokens, not T={ids.shape[1]}: one token "
@@ -392,6 +453,7 @@ class Model(nn.Module):
         feat = torch.empty(B, d.feat_dim, dtype=torch.float32, device=img.device) if d.supcon else None
         self._seed_ctr = (self._seed_ctr * 1103515245 + 12345) & 0x7FFFFFFF
         L.check(L.lib().mmvqa_engine_set_precision(self._handle, int(prec)))
+        L.check(L.lib().mmvqa_engine_set_frozen(self._handle, int(frozen_flags)))   # recorded by the forward for its backward
         L.check(L.lib().mmvqa_engine_forward(self._handle, L.stream_ptr(), L.ptr(img), L.ptr(ids), L.ptr(seg),
                                              L.ptr(mask), L.ptr(buf), ld, L.ptr(feat), 1 if self.training else 0,
                                              self._seed_ctr))
@@ -400,10 +462,10 @@ class Model(nn.Module):
         logits = logits.view(B, T, V) if d.head_kind != L.HEAD_VQA else logits
         return (logits, feat) if d.supcon else logits
 
-    def _engine_backward(self, dlogits, dfeat=None, prec=0):
+    def _engine_backward(self, dlogits, dfeat=None, prec=0, frozen=_NOT_FROZEN):
         img, ids, seg, mask, rows, V, ld = self._fwd_state
-        first = next(p for n, p in self._params_by_name.items() if not n.startswith(_NEVER_USED))
-        if first.grad is None:           # optimizer.zero_grad(set_to_none=True) semantics
+        first = next((p for n, p in self._params_by_name.items() if not n.startswith(_NEVER_USED) and p.requires_grad), None)
+        if first is not None and first.grad is None:           # optimizer.zero_grad(set_to_none=True) semantics
             self._flat_grad.zero_()
         g = dlogits.reshape(rows, V) if dlogits.dim() == 3 else dlogits
         if not (g.stride(1) == 1 and g.stride(0) % 4 == 0 and g.stride(0) >= ld and g.data_ptr() % 16 == 0):
@@ -418,6 +480,8 @@ class Model(nn.Module):
         if getattr(self, "_cb_error", None) is not None:
             err, self._cb_error = self._cb_error, None
             raise err
+        for lo, hi in frozen[1]:         # no gradient for these: whatever the engine computed there is discarded
+            self._flat_grad[lo:hi].zero_()
         self.attach_grads()
 
     def feature_gradient(self, img, input_ids, segment_ids, input_mask, target=None):
@@ -467,9 +531,16 @@ class Model(nn.Module):
         and the returned logits.  This rounds strictly less than torch's autocast, which also rounds each
         conv / linear output to fp16 and runs BatchNorm and elementwise ops on fp16 tensors: results are close
         to, not bit-equal to, the reference under autocast.  Other autocast dtypes (bf16) and EfficientNet
-        under fp16 autocast raise NotImplementedError.  Outside autocast everything is fp32 as before."""
+        under fp16 autocast raise NotImplementedError.  Outside autocast everything is fp32 as before.
+
+        requires_grad is honoured per parameter, read at each forward that runs with grad enabled: a parameter with
+        requires_grad=False gets no .grad and its range of flat_grads is zero after backward.  When every parameter of
+        the CNN body (transformer.trans.model.*) is frozen, its backward pass is not run at all (freeze_backbone()); the
+        gradient of any other frozen tensor is still computed and then discarded.  With a gradient-ready hook, such a
+        discarded range is announced as computed and zeroed when backward ends."""
         prec = autocast_precision(self._desc)
-        out = _ModelFn.apply(self, self._anchor, img, input_ids, segment_ids, input_mask, prec)
+        frozen = self._frozen_state() if torch.is_grad_enabled() else _NOT_FROZEN
+        out = _ModelFn.apply(self, self._anchor, img, input_ids, segment_ids, input_mask, prec, frozen)
         if self.dataset == "VQA-Med":
             return out, 0, 0   # models/mmbert.py:167
         return out

@@ -6,18 +6,95 @@ Same update as ``optim.Adam(model.parameters(), lr)`` at pretrain/roco_train.py:
 vqamed2019/train.py:160 (betas (0.9, 0.999), eps 1e-8, no weight decay).  Parameters whose
 gradient stays zero (the reference's never-used ``norm2`` / ``fc``) do not move, which equals the
 reference's "grad is None => skipped".
+
+Beyond the reference: optimizer groups (a learning rate / weight decay per set of tensors), weight decay in the
+``torch.optim.AdamW`` (decoupled, the default) or ``torch.optim.Adam(weight_decay=)`` (L2) form, and frozen parameters
+(``requires_grad=False``: neither the parameter nor its moments move).  All of it is one segment table in device
+memory and still one launch per step or per range (``mmvqa_adam_groups``); the table is uploaded when a learning rate,
+a weight decay or a parameter's ``requires_grad`` changes and not otherwise.  Built as before -- no groups, no weight
+decay, nothing frozen -- the optimizer calls ``mmvqa_adam`` as before.
 """
 from __future__ import annotations
+
+import ctypes as C
+import operator
+import re
 
 import torch
 
 from . import _lib as L
 
+_REQUIRES_GRAD = operator.attrgetter("requires_grad")
+_NORM_WEIGHT = re.compile(r"(^|\.)(LayerNorm|norm\d*|ln\d+|bn\d+|downsample\.1|classifier\.1|to_logits\.0)\.weight$")
+
+
+def no_decay(name: str) -> bool:
+    """ready ``match`` predicate of a group: the tensors that are customarily left out of weight decay -- every bias and
+    the scale of every LayerNorm (the embedding LayerNorm included) and BatchNorm"""
+    return name.endswith(".bias") or _NORM_WEIGHT.search(name) is not None
+
+
+def _matches(match, name):
+    if callable(match):
+        return bool(match(name))
+    if isinstance(match, str):
+        match = (match,)
+    return name.startswith(tuple(match))
+
+
+def assign_groups(names, groups):
+    """group index of every name: the first group of `groups` whose ``match`` (a prefix, a tuple of prefixes or a
+    callable(name)) accepts it, counted from 1; 0 = the default group (no match)"""
+    out = []
+    for n in names:
+        out.append(next((i + 1 for i, g in enumerate(groups) if _matches(g["match"], n)), 0))
+    return out
+
+
+def merge_segments(ranges):
+    """[(lo, hi, lr, weight_decay, mode)] in buffer order -> the same with adjacent ranges of equal settings merged;
+    a frozen range has no settings (lr = weight_decay = 0), so neighbouring frozen tensors merge whatever their group"""
+    out = []
+    for lo, hi, lr, wd, mode in ranges:
+        if mode == L.ADAM_FROZEN:
+            lr = wd = 0.0
+        if out and out[-1][1] == lo and out[-1][2:] == [lr, wd, mode]:
+            out[-1][1] = hi
+        else:
+            out.append([lo, hi, lr, wd, mode])
+    if len(out) > L.ADAM_MAX_SEGS:
+        raise L.MMVQAError(f"FusedAdam: the groups split the parameter buffer into {len(out)} segments, more than the "
+                           f"{L.ADAM_MAX_SEGS} one launch takes")
+    return [tuple(s) for s in out]
+
 
 class FusedAdam:
-    def __init__(self, model, lr=2e-5, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, model, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, groups=None):
+        """groups: list of dicts {match: prefix | tuple of prefixes | callable(name), lr?, weight_decay?}; a parameter
+        belongs to the first group that matches its name, the rest to the default group (lr, weight_decay), which is
+        param_groups[0].  decoupled: weight decay as torch.optim.AdamW applies it (p *= 1 - lr wd), else as
+        torch.optim.Adam(weight_decay=) does (g += wd p).  betas and eps are shared: a group that names its own is
+        refused.  Parameters with requires_grad=False are skipped (read again at every step): they and their moments
+        keep their values, also when they were frozen after some steps."""
         self.model = model
-        self.param_groups = [dict(lr=lr, betas=betas, eps=eps)]  # ReduceLROnPlateau-compatible
+        groups = [dict(g) for g in (groups or [])]
+        for g in groups:
+            extra = set(g) - {"match", "lr", "weight_decay"}
+            if "match" not in g or extra:
+                raise ValueError(f"FusedAdam: a group is {{match, lr?, weight_decay?}}, not {sorted(g)} (betas and eps are "
+                                 "shared by all groups)")
+        self.decoupled = bool(decoupled)
+        # ReduceLROnPlateau-compatible: one dict per group, the default group first
+        self.param_groups = [dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)]
+        self.param_groups += [dict(lr=g.get("lr", lr), betas=betas, eps=eps, weight_decay=g.get("weight_decay", weight_decay))
+                              for g in groups]
+        # (name, parameter, lo, hi) per tensor; a bare pair of flat buffers (anything with flat_params / flat_grads) is one
+        # tensor without a name that is never frozen
+        table = getattr(model, "_param_ranges", None)
+        self._ranges = table() if table is not None else [("", None, 0, model.flat_params.numel())]
+        self._names = [name for name, _, _, _ in self._ranges]
+        self._params = tuple(p for _, p, _, _ in self._ranges if p is not None)
+        self._group_of = assign_groups(self._names, groups)
         self.m = torch.zeros_like(model.flat_params)
         self.v = torch.zeros_like(model.flat_params)
         self.step_count = 0
@@ -25,6 +102,58 @@ class FusedAdam:
         self._stream = None          # overlap_backward(): the stream the early updates run on
         self._done = []              # [lo, hi) ranges already updated in the current step
         self._grad_scale = 1.0
+        self._plan_step = None       # the step number the plan below was made for
+        self._key = None             # settings the uploaded table was built from
+        self._segs = None            # (host ctypes array, device tensor, nseg) or None: the plain mmvqa_adam path
+        self._uploaded = None        # event behind the last upload: launches on other streams wait for it
+        self._retired = []           # the table before this one: a launch still queued may read it
+
+    # ------------------------------------------------------------------ segment table
+    def group_spec(self):
+        """what has to agree between a checkpoint and the optimizer that resumes from it: the form of the weight decay
+        and the parameter names of every group"""
+        names = [[] for _ in self.param_groups]
+        for n, g in zip(self._names, self._group_of):
+            names[g].append(n)
+        return dict(decoupled=self.decoupled, groups=names)
+
+    def segments(self):
+        """the merged table [(lo, hi, lr, weight_decay, mode)] of the current settings"""
+        mode = L.ADAM_DECOUPLED if self.decoupled else L.ADAM_L2
+        rows = []
+        for (name, p, lo, hi), gi in zip(self._ranges, self._group_of):
+            g = self.param_groups[gi]
+            rows.append((lo, hi, float(g["lr"]), float(g["weight_decay"]), mode if p is None or p.requires_grad else L.ADAM_FROZEN))
+        return merge_segments(rows)
+
+    def _plan(self, step):
+        """once per step: read the groups' settings and the parameters' requires_grad; build and upload the table when
+        they differ from what the device holds"""
+        if self._plan_step == step:
+            return
+        self._plan_step = step
+        b0, e0 = self.param_groups[0]["betas"], self.param_groups[0]["eps"]
+        if any(tuple(g["betas"]) != tuple(b0) or g["eps"] != e0 for g in self.param_groups):
+            raise L.MMVQAError("FusedAdam: betas and eps are shared by all groups; per-group values are not supported")
+        trained = tuple(map(_REQUIRES_GRAD, self._params))
+        key = (tuple((float(g["lr"]), float(g["weight_decay"])) for g in self.param_groups), trained)
+        if key == self._key:
+            return
+        self._key = key
+        if len(self.param_groups) == 1 and key[0][0][1] == 0.0 and all(trained):
+            self._segs = None        # one group, no decay, nothing frozen: mmvqa_adam, as always
+            return
+        segs = self.segments()
+        host = (L.AdamSeg * len(segs))()
+        for h, (lo, hi, lr, wd, mode) in zip(host, segs):
+            h.begin, h.end, h.lr, h.weight_decay, h.mode = lo, hi, lr, wd, mode
+        staged = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).pin_memory()
+        dev = torch.empty(staged.numel(), dtype=torch.uint8, device=self.m.device)
+        dev.copy_(staged, non_blocking=True)   # (pinned source: the copy is queued, nothing waits for the device)
+        self._uploaded = torch.cuda.Event()
+        self._uploaded.record()
+        self._retired = [self._segs]           # a fresh buffer per upload: a queued launch keeps reading its own table
+        self._segs = (host, dev, len(segs))
 
     # ------------------------------------------------------------------ update beside the backward pass
     def overlap_backward(self, reducer=None, grad_scale=1.0):
@@ -35,6 +164,8 @@ class FusedAdam:
         behind that bucket's all-reduce (work.wait() puts the wait on the update's stream, not on the host).
         step() then only updates what was never announced and joins the streams.  The arithmetic per element is the same
         kernel with the same step number: results are bit-identical to the one-launch form (tests/test_hip_train.py).
+        With groups, weight decay or frozen parameters every ranged launch reads the one global table with its own
+        [lo, hi).
         Contract: ONE backward per step (no gradient accumulation), zero_grad=True and this grad_scale in step()."""
         self._stream = torch.cuda.Stream()
         self._grad_scale = float(grad_scale)
@@ -45,11 +176,19 @@ class FusedAdam:
             self.model.set_grad_ready_hook(self._on_ready, with_event=True)
 
     def _adam(self, lo, hi, step, grad_scale, zero_grad, stream_ptr):
+        self._plan(step)
         g = self.param_groups[0]
         p = self.model.flat_params
-        L.check(L.lib().mmvqa_adam(stream_ptr, L.ptr(p[lo:hi]), L.ptr(self.model.flat_grads[lo:hi]), L.ptr(self.m[lo:hi]),
-                                   L.ptr(self.v[lo:hi]), hi - lo, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
-                                   step, grad_scale, 1 if zero_grad else 0))
+        if self._segs is None:
+            L.check(L.lib().mmvqa_adam(stream_ptr, L.ptr(p[lo:hi]), L.ptr(self.model.flat_grads[lo:hi]), L.ptr(self.m[lo:hi]),
+                                       L.ptr(self.v[lo:hi]), hi - lo, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                                       step, grad_scale, 1 if zero_grad else 0))
+            return
+        host, dev, nseg = self._segs
+        torch.cuda.current_stream().wait_event(self._uploaded)   # (a no-op on the stream that uploaded)
+        L.check(L.lib().mmvqa_adam_groups(stream_ptr, L.ptr(p), L.ptr(self.model.flat_grads), L.ptr(self.m), L.ptr(self.v),
+                                          lo, hi - lo, C.cast(host, C.c_void_p), L.ptr(dev), nseg, g["betas"][0],
+                                          g["betas"][1], g["eps"], step, grad_scale, 1 if zero_grad else 0))
 
     def _early(self, lo, hi, ready=None, work=None, stream=None):
         if hi <= lo or any(a < hi and lo < b for a, b in self._done):
@@ -98,12 +237,21 @@ class FusedAdam:
         self._done = []
 
     def state_dict(self):
-        return dict(m=self.m, v=self.v, step=self.step_count, param_groups=self.param_groups)
+        return dict(m=self.m, v=self.v, step=self.step_count, param_groups=self.param_groups, group_spec=self.group_spec())
 
     def load_state_dict(self, sd):
+        mine = self.group_spec()
+        theirs = sd.get("group_spec")
+        if theirs is None:           # written before there were groups: one group over everything, no weight decay
+            theirs = dict(decoupled=self.decoupled, groups=[list(self._names)])
+        if theirs != mine:
+            raise L.MMVQAError("FusedAdam.load_state_dict: the checkpoint's optimizer groups (which tensors belong to which "
+                               "group, or the form of the weight decay) differ from this optimizer's; build it with the "
+                               "groups the checkpoint was written with")
         self.m.copy_(sd["m"]); self.v.copy_(sd["v"])
         self.step_count = int(sd["step"])
         # in place: a scheduler built on this optimizer keeps pointing at the SAME list/dicts, so a later
-        # ReduceLROnPlateau step still reaches mmvqa_adam after --resume
-        for mine, theirs in zip(self.param_groups, sd["param_groups"]):
-            mine.update(theirs)
+        # ReduceLROnPlateau step still reaches the kernel after --resume
+        for mine_g, theirs_g in zip(self.param_groups, sd["param_groups"]):
+            mine_g.update(theirs_g)
+        self._plan_step = None

@@ -54,7 +54,7 @@ import torch.distributed as dist
 from torch.optim import lr_scheduler
 
 from . import (CategorySmoothing, FusedAdam, LabelSmoothing, Model, asl_loss, checkpoint, distill_loss, embedding_mask,
-               evaluate, jaccard_mask, mlm_loss, split_feat, supcon_loss, synth)
+               evaluate, jaccard_mask, mlm_loss, no_decay, split_feat, supcon_loss, synth)
 from . import data as D
 from .amp import GradScaler
 from .ddp import (GradReducer, comm_info, global_supcon_means, global_supcon_pairs, global_supcon_states, global_supcon_views,
@@ -104,6 +104,15 @@ def common_args(p):
                         "then divides them by the scale.  supcon: accepted, runs fp32 (the reference's SupCon loop has no "
                         "autocast).  Not with --overlap_adam")
     p.add_argument("--overlap_adam", action="store_true", help="Adam per finished gradient range beside the backward pass (measured time-neutral; not with --clip)")
+    # beyond the reference (its --weight_decay stays commented out, vqamed2019/train.py:53; its freeze too,
+    # models/image_encoding.py:50-51): the defaults reproduce a run without these options
+    p.add_argument("--weight_decay", type=float, default=0.0, help="decoupled (AdamW) weight decay")
+    p.add_argument("--adam_l2", action="store_true", help="weight decay as torch.optim.Adam(weight_decay=): added to the gradient")
+    p.add_argument("--decay_all", action="store_true", help="decay biases, LayerNorm and BatchNorm parameters too (default: they get 0)")
+    p.add_argument("--backbone_lr", type=float, default=None, help="learning rate of the CNN body (transformer.trans.model.*)")
+    p.add_argument("--freeze_backbone", action="store_true", help="the CNN body gets no gradient; its backward pass is not run")
+    p.add_argument("--freeze_bn_stats", action="store_true",
+                   help="with --freeze_backbone: its BatchNorms use and keep their running statistics (backbone.eval())")
     p.add_argument("--data_dir", type=str, default=None,
                    help="ROCO (mlm, supcon) or VQA-Med 2019 (vqa, eval) tree on disk; without it the batches are synthetic")
     p.add_argument("--vocab_file", type=str, default=None, help="WordPiece vocab.txt (with --data_dir)")
@@ -230,7 +239,36 @@ class Ctx:
         return float(t) / self.world
 
 
+def check_optimizer_args(args):
+    """the rules between the optimizer options; raises ValueError with the rule that is broken"""
+    if getattr(args, "freeze_bn_stats", False) and not getattr(args, "freeze_backbone", False):
+        raise ValueError("--freeze_bn_stats requires --freeze_backbone")
+    if getattr(args, "freeze_backbone", False) and getattr(args, "backbone_lr", None) is not None:
+        raise ValueError("--freeze_backbone with --backbone_lr: a frozen backbone has no learning rate")
+    if getattr(args, "weight_decay", 0.0) < 0:
+        raise ValueError("--weight_decay must not be negative")
+
+
+def optimizer_groups(args):
+    """FusedAdam's keyword arguments from the options; all defaults -> none but lr: one group, no decay, mmvqa_adam"""
+    kw = dict(lr=args.lr, weight_decay=getattr(args, "weight_decay", 0.0), decoupled=not getattr(args, "adam_l2", False))
+    groups = []
+    blr = getattr(args, "backbone_lr", None)
+    wd = kw["weight_decay"]
+    spare = wd != 0.0 and not getattr(args, "decay_all", False)
+    if blr is not None and spare:     # first match wins: the backbone's BatchNorm parameters take its rate and no decay
+        groups.append(dict(match=lambda n: n.startswith("transformer.trans.model.") and no_decay(n), lr=blr, weight_decay=0.0))
+    if blr is not None:
+        groups.append(dict(match="transformer.trans.model.", lr=blr))
+    if spare:
+        groups.append(dict(match=no_decay, weight_decay=0.0))
+    if groups:
+        kw["groups"] = groups
+    return kw
+
+
 def build(args, ctx, n_classes=None):
+    check_optimizer_args(args)
     torch.manual_seed(args.seed)          # identical replicas
     model = Model(args)
     if args.backbone_weights:
@@ -250,7 +288,9 @@ def build(args, ctx, n_classes=None):
     model.to(ctx.dev)
     model.set_seed(args.seed + ctx.rank)
     cs = sync_replicas(model)              # rank 0's replica everywhere, checksum compared across ranks
-    opt = FusedAdam(model, lr=args.lr)
+    if getattr(args, "freeze_backbone", False):
+        model.freeze_backbone("running" if args.freeze_bn_stats else "batch")
+    opt = FusedAdam(model, **optimizer_groups(args))
     sched = lr_scheduler.ReduceLROnPlateau(_SchedShim(opt), patience=args.patience, factor=args.factor)
     red = GradReducer(model.flat_grads, bucket_mb=getattr(args, "bucket_mb", 64.0))
     if ctx.world > 1:
@@ -265,7 +305,7 @@ def build(args, ctx, n_classes=None):
 
 
 class _SchedShim(torch.optim.Optimizer):
-    """lets torch's ReduceLROnPlateau drive FusedAdam.param_groups[0]['lr']"""
+    """lets torch's ReduceLROnPlateau drive the 'lr' of every FusedAdam.param_groups entry"""
 
     def __init__(self, fused):
         self.fused = fused
@@ -942,6 +982,10 @@ def parse_args(argv=None):
     if args.mixed_precision and args.overlap_adam:
         p.error("--overlap_adam cannot be combined with --mixed_precision: the whole gradient must be checked for "
                 "inf / nan before the first parameter update")
+    try:
+        check_optimizer_args(args)
+    except ValueError as ex:
+        p.error(str(ex))
     if getattr(args, "smoothing", None) is not None and not 0.0 <= args.smoothing <= 1.0:
         p.error(f"--smoothing {args.smoothing} is outside [0, 1]")
     if mode == "supcon":
