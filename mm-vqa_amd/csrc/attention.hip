@@ -8,6 +8,10 @@
 //   BertLayer  (models/transformer.py:19-30): S/sqrt(d) - 10000(1-mask[key]); softmax; dropout; .V
 //   RealFormer (models/realformer.py:30-45) : S/sqrt(d) + prev - 10000(1-mask[QUERY]); prev<-S; softmax; .V
 // fp32 op order follows the reference: (q.k)/sqrt(d), then +prev, then -10000*(1-m).
+// A QUERY mask shifts a whole row by one constant, which the softmax cancels: prev_out gets the shifted score as the
+// reference writes it, but the softmax of such a row takes the unshifted one.  Subtracting 10000 in fp32 first would
+// round the row's scores to a grid of 2^-10 and leave its probabilities (and through dK / dV every gradient) ~2e-4 off
+// the exact result.
 #include "wave_tile.h"
 
 // Global operands of the forward kernel that its one-tile form (HOIST) prefetches and its other forms load at the point
@@ -79,8 +83,9 @@ __global__ __launch_bounds__(64) void attn_fwd_kernel(const AttnParams p) {
         const size_t po = prev_at(b, T, qi, j, p.heads, head);
         if (p.prev_in) s = s + (HOIST ? h_pv[e] : p.prev_in[po]);
         const float mval = p.mask_on_query ? qmask : (HOIST ? h_mk[e] : key_mask(p.mask, b, T, j));
-        s = s - 10000.0f * (1.0f - mval);
-        if (p.prev_out) p.prev_out[po] = s;
+        const float sm = s - 10000.0f * (1.0f - mval);
+        if (p.prev_out) p.prev_out[po] = sm;
+        if (!p.mask_on_query) s = sm;
       }
       sc[jt][e] = s;
       mx = fmaxf(mx, s);
@@ -350,6 +355,8 @@ static int attn_dispatch(const AttnParams& p, int bwd, hipStream_t st) {
 }
 
 int mmvqa_launch_attention(const AttnParams& p, int head_dim, int bwd, hipStream_t st) {
+  if (p.B <= 0 || p.T <= 0 || p.heads <= 0 || !(p.drop_p >= 0.f && p.drop_p < 1.f))
+    return mmvqa_set_error(MMVQA_ERR_ARG, "attention: B=%d T=%d heads=%d drop_p=%g", p.B, p.T, p.heads, (double)p.drop_p);
   if (!p.q || !p.k || !p.v || !p.mask || !p.probs) return mmvqa_set_error(MMVQA_ERR_ARG, "attention: null operand");
   if ((p.row_stride & 3) || (p.head_stride & 3) || (p.out_row_stride & 3) || (p.out_head_stride & 3))
     return mmvqa_set_error(MMVQA_ERR_ARG, "attention: strides must be multiples of 4");
