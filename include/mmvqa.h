@@ -638,6 +638,42 @@ int mmvqa_engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, i
 int mmvqa_gradcam(mmvqa_stream_t s, const float* A, const float* dA, int B, int H, int W, int C, float* cam, int* valid,
                   float* up, int IH, int IW, const unsigned char* image_u8, const unsigned char* jet, float alpha,
                   unsigned char* overlay);
+/* Forward from cached visual tokens.  mmvqa_engine_visual_tokens: where the last forward left the
+ * num_vis visual tokens, [num_vis][B][hidden] as mmvqa_embed_fwd reads them, inside the bound workspace: valid until the
+ * next forward.  mmvqa_engine_forward_tokens: the EVAL-mode forward (no dropout, no BatchNorm touched) with `vis` in that
+ * layout in place of the backbone and its taps: the embedding with the overwrite, the encoder and the heads (or the
+ * headless copy), all on the given stream; logits / feat as in mmvqa_engine_forward.  The backbone's activations in the
+ * workspace are not those of `vis`: mmvqa_engine_backward and mmvqa_engine_backward_feature answer MMVQA_ERR_STATE
+ * until the next mmvqa_engine_forward.  fp32 operands only: MMVQA_ERR_ARG in the f16 operand mode, and for a null pointer
+ * or a bad logits_ld. */
+int mmvqa_engine_visual_tokens(mmvqa_engine* e, const float** vis);
+int mmvqa_engine_forward_tokens(mmvqa_engine* e, mmvqa_stream_t s, const float* vis, const long long* ids,
+                                const long long* seg, const long long* mask, float* logits, int logits_ld, float* feat);
+/* Attribution methods beyond Grad-CAM (vqamed2019/grad_cam.py:65-72), maps as in mmvqa_gradcam
+ * (H * W <= 256, C % 4 == 0, C <= 4096, else MMVQA_ERR_ARG before any HIP call).
+ * mmvqa_cam_weights: w [B][C] of method 0 (gradcam: mean_p dA, bit-equal to mmvqa_gradcam's own), 1 (gradcam++:
+ * sum_p max(g, 0) g^2 / (2 g^2 + S_c g^3 + 1e-7), 0 where g == 0) or 2 (xgradcam: sum_p g a / (S_c + 1e-7)), with
+ * S_c = sum_p A[b][p][c].
+ * mmvqa_cam_from_weights: the tail of mmvqa_gradcam (mean over channels of w * A, ReLU, division by the maximum, valid,
+ * resize, overlay) with the channel weights w [B][C] from memory, or with the map before the ReLU raw [B][H][W] from
+ * memory (then A may be NULL); exactly one of w and raw is non-NULL. */
+int mmvqa_cam_weights(mmvqa_stream_t s, int method, const float* A, const float* dA, int B, int H, int W, int C, float* w);
+int mmvqa_cam_from_weights(mmvqa_stream_t s, const float* A, const float* w, const float* raw, int B, int H, int W, int C,
+                           float* cam, int* valid, float* up, int IH, int IW, const unsigned char* image_u8,
+                           const unsigned char* jet, float alpha, unsigned char* overlay);
+/* Eigen-CAM's map before the ReLU: raw [B][H][W] = X v1 with X = A[b] as [H*W][C], every column centred over the
+ * positions, and v1 its first right singular vector, by 64 power iterations on the Gram matrix X X^T kept in
+ * gram [B][H*W][H*W] (scratch).  Sign: the entry of largest magnitude is positive (ties: lowest position).
+ * resid [B] = |G u - lambda u| / lambda of the result.  X all zero or H * W = 1: raw = 0 and resid = 0. */
+int mmvqa_eigencam_raw(mmvqa_stream_t s, const float* A, int B, int H, int W, int C, float* gram, float* raw, float* resid);
+/* Ablation-CAM's visual tokens: tokens [B][nc][hidden] = mean_p act(u[b][p][n] - Wt[n][c] A[b][p][c]) for the channels
+ * c = c0 .. c0 + nc - 1 of A [B][HW][C], i.e. the token of a bias-free 1x1 tap Wt [hidden][C] with channel c zeroed;
+ * act: 1 (ReLU) or 3 (SERF).  u [B * HW][hidden] = A Wt^T is scratch: computed first when compute_u != 0, reused
+ * (from an earlier chunk of the same pass) otherwise.  mmvqa_ablation_weights: w [B][C] = (score[b] - score_abl[b][c]) /
+ * score[b], zeros where score[b] == 0. */
+int mmvqa_ablated_tokens(mmvqa_stream_t s, const float* A, const float* Wt, float* u, int B, int HW, int C, int hidden,
+                         int act, int c0, int nc, int compute_u, float* tokens);
+int mmvqa_ablation_weights(mmvqa_stream_t s, const float* score, const float* score_abl, int B, int C, float* w);
 /* data-parallel overlap: cb(user, lo, hi) is called on the HOST thread inside mmvqa_engine_backward as soon as
  * the kernels completing grads[lo, hi) (float offsets) are enqueued and the given stream is ordered behind them, so
  * the caller can start the all-reduce of that range on its communication stream while backward continues.

@@ -245,6 +245,13 @@ SIGNATURES = {
     "mmvqa_engine_backward_feature": (_i, [_P, _P, _P, _i, _P]),
     "mmvqa_engine_feature_map": (_i, [_P, C.POINTER(_P), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "mmvqa_gradcam": (_i, [_P, _P, _P, _i, _i, _i, _i, _P, _P, _P, _i, _i, _P, _P, _f, _P]),
+    "mmvqa_engine_visual_tokens": (_i, [_P, C.POINTER(_P)]),
+    "mmvqa_engine_forward_tokens": (_i, [_P, _P, _P, _P, _P, _P, _P, _i, _P]),
+    "mmvqa_cam_weights": (_i, [_P, _i, _P, _P, _i, _i, _i, _i, _P]),
+    "mmvqa_cam_from_weights": (_i, [_P, _P, _P, _P, _i, _i, _i, _i, _P, _P, _P, _i, _i, _P, _P, _f, _P]),
+    "mmvqa_eigencam_raw": (_i, [_P, _P, _i, _i, _i, _i, _P, _P, _P]),
+    "mmvqa_ablated_tokens": (_i, [_P, _P, _P, _P, _i, _i, _i, _i, _i, _i, _i, _i, _P]),
+    "mmvqa_ablation_weights": (_i, [_P, _P, _P, _i, _i, _P]),
     "mmvqa_engine_set_grad_callback": (_i, [_P, _P, _P]),
     "mmvqa_engine_tune": (_i, [_P, _i]),
     "mmvqa_amp_unscale": (_i, [_P, _P, _l, _P, _P, _i]),

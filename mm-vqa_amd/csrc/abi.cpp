@@ -60,6 +60,7 @@ int mmvqa_engine_bind(mmvqa_engine* e, float* params, float* grads, float* bufs,
   e->ws_ready = false;        // tap-validity tables and tickets live in the (new) workspace: put in place by the next forward
   e->bound = true;
   e->img = nullptr;
+  e->tokens_only = false;
   return MMVQA_OK;
 }
 int mmvqa_engine_forward(mmvqa_engine* e, mmvqa_stream_t s, const float* img, const long long* ids,
@@ -80,6 +81,15 @@ int mmvqa_engine_backward_feature(mmvqa_engine* e, mmvqa_stream_t s, const float
 int mmvqa_engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, int* C) {
   if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "feature_map: null engine");
   return engine_feature_map(e, A, H, W, C);
+}
+int mmvqa_engine_visual_tokens(mmvqa_engine* e, const float** vis) {
+  if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "visual_tokens: null engine");
+  return engine_visual_tokens(e, vis);
+}
+int mmvqa_engine_forward_tokens(mmvqa_engine* e, mmvqa_stream_t s, const float* vis, const long long* ids,
+                                const long long* seg, const long long* mask, float* logits, int logits_ld, float* feat) {
+  if (!e || !vis || !ids || !seg || !mask || !logits) return mmvqa_set_error(MMVQA_ERR_ARG, "forward_tokens: null pointer");
+  return engine_forward_tokens(e, ST(s), vis, ids, seg, mask, logits, logits_ld, feat);
 }
 int mmvqa_engine_set_grad_callback(mmvqa_engine* e, mmvqa_grad_cb cb, void* user) {
   if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "set_grad_callback: null engine");

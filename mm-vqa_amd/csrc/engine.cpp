@@ -1930,7 +1930,7 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
                            d.head_kind == 2 ? "hidden" : "n_classes", out_w);
   e->img = img; e->ids = ids; e->seg = seg; e->mask = mask;
   e->logits = logits; e->logits_ld = logits_ld; e->feat = feat;
-  e->training = training; e->seed = seed;
+  e->training = training; e->seed = seed; e->tokens_only = false;
   e->frozen = e->frozen_next;
   // `training` means dropout everywhere and batch statistics in the backbone's BatchNorms; the two part only under
   // MMVQA_FREEZE_BN_STATS (backbone.eval() inside model.train())
@@ -1952,6 +1952,51 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
   if (d.head_kind == 2) {   // models/mmbert.py:159-161: logits = h; fc1 / classifier / head are not run
     return copy_rows(st, logits, (size_t)logits_ld, h, (size_t)d.hidden, (size_t)e->B * e->T, (size_t)d.hidden);
   }
+  return heads_forward(e, st, h);
+}
+
+// Where the last forward left the num_vis visual tokens: [num_vis][B][hidden] inside the bound workspace, as
+// mmvqa_embed_fwd reads them; valid until the next forward.
+int engine_visual_tokens(mmvqa_engine* e, const float** vis) {
+  if (!e->planned || !e->bound || (!e->img && !e->tokens_only))
+    return mmvqa_set_error(MMVQA_ERR_STATE, "engine_visual_tokens: plan/bind and run a forward first");
+  if (!vis) return mmvqa_set_error(MMVQA_ERR_ARG, "engine_visual_tokens: null pointer");
+  *vis = WS(e->vis);
+  return MMVQA_OK;
+}
+
+// The eval-mode forward from given visual tokens: `vis` [num_vis][B][hidden] takes the place of what the backbone and
+// its taps write, then exactly the launches of engine_forward after the backbone run on the caller's stream.  The
+// backbone's activations in the workspace are NOT those of these tokens afterwards: both backward entry points refuse.
+int engine_forward_tokens(mmvqa_engine* e, hipStream_t st, const float* vis, const long long* ids, const long long* seg,
+                          const long long* mask, float* logits, int logits_ld, float* feat) {
+  if (e->prec != MMVQA_PREC_F32)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward_tokens: runs with fp32 operands, not in the f16 operand mode");
+  if (!e->planned || !e->bound) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_forward_tokens: plan/bind first");
+  const mmvqa_model_desc& d = e->d;
+  const int out_w = d.head_kind == 2 ? d.hidden : d.n_classes;
+  if (logits_ld < out_w || (logits_ld & 3))
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward_tokens: logits_ld=%d must be >= %s=%d and %%4==0", logits_ld,
+                           d.head_kind == 2 ? "hidden" : "n_classes", out_w);
+  TRY(prepare_workspace(e, st));
+  e->img = nullptr; e->tokens_only = true;   // no backward of any kind after this forward
+  e->ids = ids; e->seg = seg; e->mask = mask;
+  e->logits = logits; e->logits_ld = logits_ld; e->feat = feat;
+  e->training = 0; e->bn_training = 0; e->seed = 0;
+  StepScope scope(e, MMVQA_PREC_F32);
+  const size_t n_vis = (size_t)d.num_vis * e->B * d.hidden;
+  if (vis != WS(e->vis)) HIP_CHECK_RET(hipMemcpyAsync(WS(e->vis), vis, n_vis * sizeof(float), hipMemcpyDeviceToDevice, st));
+  e->prof_reg = REG_EMBED;
+  RUN(PROF_OTHER, 0,
+      mmvqa_embed_fwd(st, ids, seg, PRM(e->emb_word), PRM(e->emb_pos), PRM(e->emb_type), PRM(e->emb_ln.g),
+                  PRM(e->emb_ln.b), WS(e->vis), WS(e->emb_out), WS(e->emb_xhat), WS(e->emb_rstd), e->B, e->T,
+                  d.hidden, d.num_vis, 1e-12f, 0.f, site_seed(e, 100, 0)));
+  e->prof_reg = REG_BACKBONE;
+  const float* h = nullptr;
+  TRY(encoder_forward(e, st, &h));
+  e->enc_out_final = (size_t)(h - e->ws);
+  if (d.head_kind == 2)
+    return copy_rows(st, logits, (size_t)logits_ld, h, (size_t)d.hidden, (size_t)e->B * e->T, (size_t)d.hidden);
   return heads_forward(e, st, h);
 }
 
@@ -2014,6 +2059,9 @@ int engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, int* C)
 // forward is conditional on `training` except dropout probabilities and BatchNorm statistics).  Parameters, gradient
 // buffer and BatchNorm buffers are not written.
 int engine_backward_feature(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, float* dA) {
+  if (e->planned && e->bound && e->tokens_only)
+    return mmvqa_set_error(MMVQA_ERR_STATE, "engine_backward_feature: the last forward ran from given visual tokens, so the "
+                                            "feature map in the workspace is not theirs; run an eval-mode forward first");
   if (!e->planned || !e->bound || !e->img)
     return mmvqa_set_error(MMVQA_ERR_STATE, "engine_backward_feature: run an eval-mode forward first");
   if (e->training)

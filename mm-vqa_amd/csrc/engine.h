@@ -157,6 +157,7 @@ struct mmvqa_engine {
   // ---- step state
   const long long *ids = nullptr, *seg = nullptr, *mask = nullptr;
   const float* img = nullptr;
+  bool tokens_only = false;   // the last forward was engine_forward_tokens: the backbone's activations are not its own
   int training = 0;      // dropout (and everything else outside the backbone's BatchNorms) of the last forward
   int bn_training = 0;   // the backbone's BatchNorms used batch statistics: = training unless MMVQA_FREEZE_BN_STATS
   int frozen = 0;        // MMVQA_FREEZE_* of the last forward: its backward reads them here
@@ -208,6 +209,9 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW);
 int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long long* ids, const long long* seg,
                    const long long* mask, float* logits, int logits_ld, float* feat, int training, uint32_t seed);
 int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, const float* dfeat);
+int engine_visual_tokens(mmvqa_engine* e, const float** vis);
+int engine_forward_tokens(mmvqa_engine* e, hipStream_t st, const float* vis, const long long* ids, const long long* seg,
+                          const long long* mask, float* logits, int logits_ld, float* feat);
 int engine_backward_feature(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, float* dA);
 int engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, int* C);
 int engine_profile_collect(mmvqa_engine* e);

@@ -34,6 +34,7 @@ _NEVER_USED = ("transformer.blocks.norm2.", "transformer.trans.model.fc.",
 _FB = "transformer.block."
 _BACKBONE = "transformer.trans.model."   # the CNN body (models/image_encoding.py:43-62); the five tap convolutions are not in it
 _NOT_FROZEN = (0, ())
+_TOKEN_PLAN_HW = 64                      # image size of the workspace layout behind forward_tokens (its backbone never runs)
 _REQUIRES_GRAD = operator.attrgetter("requires_grad")
 _FB_KV = _FB + "layers.0.0.fn.fn.to_kv.weight"
 
@@ -494,6 +495,24 @@ class Model(nn.Module):
         if torch.is_autocast_enabled("cuda"):
             raise NotImplementedError("attribution (feature_gradient / grad_cam) is fp32 in this version: call it outside "
                                       "torch.autocast")
+        logits, A = self.feature_map(img, input_ids, segment_ids, input_mask)
+        B, V = logits.shape
+        ld = self._fwd_state[6]
+        if target is None:
+            target = logits.argmax(1)
+        target = torch.as_tensor(target, device=logits.device).long().reshape(B)
+        g = torch.zeros(B, ld, dtype=torch.float32, device=logits.device)
+        g.scatter_(1, target.view(B, 1), 1.0)
+        dA = torch.empty_like(A)
+        L.check(L.lib().mmvqa_engine_backward_feature(self._handle, L.stream_ptr(), L.ptr(g), ld, L.ptr(dA)))
+        return logits, A, dA, target
+
+    def feature_map(self, img, input_ids, segment_ids, input_mask):
+        """The forward half of feature_gradient: an eval-mode forward under no_grad -> (logits [B, classes], A [B, H, W, C]),
+        A a copy of the deepest backbone feature map.  Same refusals, and self.training is restored."""
+        if torch.is_autocast_enabled("cuda"):
+            raise NotImplementedError("attribution (feature_gradient / grad_cam) is fp32 in this version: call it outside "
+                                      "torch.autocast")
         d = self._desc
         if d.head_kind != 1:
             raise NotImplementedError("feature_gradient needs the VQA head (dataset='VQA-Med'): one row of logits per sample")
@@ -505,21 +524,91 @@ class Model(nn.Module):
                 logits = self._engine_forward(img, input_ids, segment_ids, input_mask, L.PREC_F32)
         finally:
             self.train(was_training)
-        B, V = logits.shape
-        ld = self._fwd_state[6]
-        if target is None:
-            target = logits.argmax(1)
-        target = torch.as_tensor(target, device=logits.device).long().reshape(B)
-        g = torch.zeros(B, ld, dtype=torch.float32, device=logits.device)
-        g.scatter_(1, target.view(B, 1), 1.0)
+        B = logits.shape[0]
         ap, fh, fw, fc = C.c_void_p(), C.c_int(), C.c_int(), C.c_int()
         L.check(lib.mmvqa_engine_feature_map(self._handle, C.byref(ap), C.byref(fh), C.byref(fw), C.byref(fc)))
         H, W, Cc = fh.value, fw.value, fc.value
         off = ap.value - self._ws.data_ptr()
         A = self._ws[off:off + 4 * B * H * W * Cc].view(torch.float32).view(B, H, W, Cc).clone()   # (the next forward overwrites the workspace)
-        dA = torch.empty(B, H, W, Cc, dtype=torch.float32, device=logits.device)
-        L.check(lib.mmvqa_engine_backward_feature(self._handle, L.stream_ptr(), L.ptr(g), ld, L.ptr(dA)))
-        return logits, A, dA, target
+        return logits, A
+
+    def deepest_tap(self):
+        """-> (weight [hidden, C] of the 1x1 tap that the deepest feature map feeds, the visual-token row it fills, its
+        activation): conv2 / row 0 for the ResNets, conv7 / row 4 for EfficientNet (engine.cpp, feature_tap)"""
+        name, k = ("conv7", 4) if self._desc.cnn == 1 else ("conv2", 0)
+        w = self._params_by_name[f"transformer.trans.{name}.weight"]
+        return w.detach().reshape(w.shape[0], -1).contiguous(), k, (L.ACT_RELU if self._desc.use_relu else L.ACT_SERF)
+
+    def visual_tokens(self, img):
+        """The num_vis visual tokens of `img` [B, 3, H, W] -> [B, num_vis, hidden] fp32: the eval-mode backbone and its
+        taps under no_grad (self.training and the dropout stream's counter are restored).  Implemented as one whole eval
+        forward with a dummy text that fills two positions after the num_vis visual rows, whose output is discarded: the engine has no backbone-only entry, and the backbone is at least 80 % of a
+        forward.  fp32 only (NotImplementedError inside torch.autocast)."""
+        if torch.is_autocast_enabled("cuda"):
+            raise NotImplementedError("visual tokens (visual_tokens / forward_tokens) are fp32 in this version: call it "
+                                      "outside torch.autocast")
+        B = img.shape[0]
+        T = self._desc.num_vis + 2
+        ids = torch.zeros(B, T, dtype=torch.long, device=img.device)
+        ones = torch.ones(B, T, dtype=torch.long, device=img.device)
+        was_training, seed_ctr = self.training, self._seed_ctr
+        self.train(False)
+        try:
+            with torch.no_grad():
+                self._engine_forward(img, ids, ids, ones, L.PREC_F32)
+        finally:
+            self.train(was_training)
+            self._seed_ctr = seed_ctr                                        # an eval forward draws nothing: later training steps see the same stream
+        return self._read_visual_tokens(B)
+
+    def _read_visual_tokens(self, B):
+        """the tokens the last forward left in the workspace, copied out as [B, num_vis, hidden]"""
+        d = self._desc
+        vp = C.c_void_p()
+        L.check(L.lib().mmvqa_engine_visual_tokens(self._handle, C.byref(vp)))
+        off = vp.value - self._ws.data_ptr()
+        vis = self._ws[off:off + 4 * d.num_vis * B * d.hidden].view(torch.float32).view(d.num_vis, B, d.hidden)
+        return vis.permute(1, 0, 2).contiguous()
+
+    def forward_tokens(self, vis, input_ids, segment_ids, input_mask):
+        """The encoder and the heads from given visual tokens, without the backbone: vis [B, num_vis, hidden] (what
+        visual_tokens returns; rows may repeat one image's tokens for several questions, whatever batch size they were
+        computed at) -> the same tuple as forward.  Always eval mode and no_grad; self.training, parameters, .grad and
+        BatchNorm buffers are as before.  No backward of any kind is valid after it (the engine refuses).  fp32 only
+        (NotImplementedError inside torch.autocast)."""
+        if torch.is_autocast_enabled("cuda"):
+            raise NotImplementedError("visual tokens (visual_tokens / forward_tokens) are fp32 in this version: call it "
+                                      "outside torch.autocast")
+        d = self._desc
+        if not vis.is_cuda:
+            raise L.MMVQAError("mm-vqa_amd runs on the GPU only: move the model and inputs to 'cuda' "
+                               "(there is no CPU fallback by design)")
+        ids, seg, mask = (t.contiguous().long() for t in (input_ids, segment_ids, input_mask))
+        B, T = ids.shape
+        if tuple(vis.shape) != (B, d.num_vis, d.hidden):
+            raise ValueError(f"vis must be [B={B}, {d.num_vis}, {d.hidden}], not {tuple(vis.shape)}")
+        if d.encoder == L.ENC_FEEDBACK and not 2 <= T <= L.FB_MAX_T:
+            raise ValueError(f"the feedback-transformer takes 2 <= T <= {L.FB_MAX_T} tokens, not T={T}")
+        vis_e = vis.detach().float().permute(1, 0, 2).contiguous()            # the engine's [num_vis][B][hidden]
+        # the backbone is not run, but the workspace is laid out for an image size: a small one, so that hundreds of
+        # token rows (Ablation-CAM's variants) do not reserve the backbone's activations at 224 x 224
+        self._ensure_plan(B, T, _TOKEN_PLAN_HW, _TOKEN_PLAN_HW)
+        rows = B if d.head_kind == L.HEAD_VQA else B * T
+        V = d.hidden if d.head_kind == L.HEAD_NONE else d.n_classes
+        ld = (V + 3) & ~3
+        buf = torch.empty(rows, ld, dtype=torch.float32, device=vis.device)
+        if ld != V:
+            buf[:, V:].zero_()
+        feat = torch.empty(B, d.feat_dim, dtype=torch.float32, device=vis.device) if d.supcon else None
+        L.check(L.lib().mmvqa_engine_set_precision(self._handle, L.PREC_F32))
+        L.check(L.lib().mmvqa_engine_forward_tokens(self._handle, L.stream_ptr(), L.ptr(vis_e), L.ptr(ids), L.ptr(seg),
+                                                    L.ptr(mask), L.ptr(buf), ld, L.ptr(feat)))
+        logits = buf[:, :V]
+        logits = logits.view(B, T, V) if d.head_kind != L.HEAD_VQA else logits
+        out = (logits, feat) if d.supcon else logits
+        if self.dataset == "VQA-Med":
+            return out, 0, 0
+        return out
 
     def forward(self, img, input_ids, segment_ids, input_mask):
         """Inside torch.autocast("cuda", dtype=torch.float16) the forward and its backward run in the mixed-precision

@@ -860,7 +860,8 @@ def eval_setup(args):
 def run_gradcam(args):
     """vqamed2019/grad_cam2.py:99-188 over the whole test split instead of one named image: the model and checkpoint of
     `eval`, one attribution pass per batch (mmvqa_amd.gradcam.grad_cam), <save_dir>/<category>_<image name>.png per
-    row (grad_cam2.py:188's naming) and gradcam_index.csv (image, category, question index, target, predicted, valid)."""
+    row (grad_cam2.py:188's naming) and gradcam_index.csv (image, category, question index, target, predicted, valid).
+    --method other than gradcam (grad_cam.py:30,65-72) goes through mmvqa_amd.gradcam.attribute and adds a `method` column."""
     import csv
     from PIL import Image
     from . import gradcam as G
@@ -871,11 +872,16 @@ def run_gradcam(args):
     limit = len(rows) if args.limit is None else min(args.limit, len(rows))
     os.makedirs(args.save_dir, exist_ok=True)
     index, done = [], 0
+    extra = [] if args.method == "gradcam" else [args.method]
     for img, ids, seg, mask, tgt in batches:
         if done >= limit:
             break
-        res = G.grad_cam(model, img, ids, seg, mask, target=tgt if args.target == "answer" else None,
-                         image_u8=G.image_u8_from_normalised(img))
+        if args.method == "gradcam":
+            res = G.grad_cam(model, img, ids, seg, mask, target=tgt if args.target == "answer" else None,
+                             image_u8=G.image_u8_from_normalised(img))
+        else:
+            res = G.attribute(model, img, ids, seg, mask, method=args.method, target=tgt if args.target == "answer" else None,
+                              image_u8=G.image_u8_from_normalised(img))
         over, pred = res.overlay.cpu().numpy(), res.logits.argmax(1).cpu().tolist()
         target, valid = res.target.cpu().tolist(), res.valid.cpu().tolist()
         for b in range(img.shape[0]):
@@ -886,13 +892,13 @@ def run_gradcam(args):
             out = os.path.join(args.save_dir, f"{cat}_{name}.png")
             if ctx.rank == 0:
                 Image.fromarray(over[b], "RGB").save(out)
-            index.append([os.path.basename(out), cat, done, target[b], pred[b], valid[b]])
+            index.append([os.path.basename(out), cat, done, target[b], pred[b], valid[b]] + extra)
             done += 1
     p_idx = os.path.join(args.save_dir, "gradcam_index.csv")
     if ctx.rank == 0:
         with open(p_idx, "w", newline="") as f:
             w = csv.writer(f, lineterminator="\n")
-            w.writerow(["image", "category", "question_index", "target", "predicted", "valid"])
+            w.writerow(["image", "category", "question_index", "target", "predicted", "valid"] + (["method"] if extra else []))
             w.writerows(index)
         print("wrote", done, "overlays and", p_idx)
     return index
@@ -978,6 +984,10 @@ def parse_args(argv=None):
             p.add_argument("--target", type=str, default="answer", choices=["answer", "predicted"],
                            help="the class each map explains: the row's answer (grad_cam2.py:141) or the model's prediction")
             p.add_argument("--limit", type=int, default=None, help="stop after N rows of the split")
+            p.add_argument("--method", type=str, default="gradcam",
+                           choices=["gradcam", "gradcam++", "xgradcam", "eigencam", "ablationcam"],
+                           help="attribution method (vqamed2019/grad_cam.py:30,65-72); other than gradcam, the index "
+                                "gains a `method` column")
     args = p.parse_args(argv)
     if args.mixed_precision and args.overlap_adam:
         p.error("--overlap_adam cannot be combined with --mixed_precision: the whole gradient must be checked for "
