@@ -589,6 +589,18 @@ int mmvqa_dropout_copy(mmvqa_stream_t s, const float* x, float* y, long n, float
  * by mmvqa_gemm_desc.pixmask */
 int mmvqa_pixmask(mmvqa_stream_t s, int* out, int N, int OH, int OW, int SH, int SW, int KH, int KW, int stride,
                   int pad);
+/* Grouped batches: NI images feed B >= NI questions.  Device pointers, fp32 rows of H floats
+ * (H % 4 == 0), 16-byte aligned.  The kernels trust the CONTENTS of group / offsets: the caller validates them.
+ * mmvqa_vis_expand: vis_q [num_vis][B][H], vis_q[t][b][:] = vis_i[t][group[b]][:] with vis_i [num_vis][NI][H] and
+ * group int32 [B], every value in [0, NI).
+ * mmvqa_dvis_group_sum: dvis_i [num_vis][NI][H], dvis_i[t][i][:] = the fp32 sum of dvis_q[t][b][:] over
+ * offsets[i] <= b < offsets[i+1] (offsets int32 [NI+1], 0 = offsets[0] < ... < offsets[NI] = B), added in ascending b
+ * starting from the first row, without atomics: bit-equal from run to run and to a sequential fp32 host loop.
+ * MMVQA_ERR_ARG for a null pointer, NI < 1, B < NI, H % 4 != 0 or num_vis < 1. */
+int mmvqa_vis_expand(mmvqa_stream_t s, const float* vis_i, const int* group, float* vis_q, int NI, int B, int H,
+                     int num_vis);
+int mmvqa_dvis_group_sum(mmvqa_stream_t s, const float* dvis_q, const int* offsets, float* dvis_i, int NI, int B, int H,
+                         int num_vis);
 
 /* ---- engine level: the whole Model.forward / backward (models/mmbert.py:150-167) ------------ */
 int mmvqa_engine_create(const mmvqa_model_desc* desc, mmvqa_engine** out);
@@ -605,6 +617,13 @@ long long mmvqa_engine_buf_floats(const mmvqa_engine* e);
 long long mmvqa_engine_nbt_count(const mmvqa_engine* e);
 /* plan for a batch geometry; returns workspace bytes needed (0 on error) */
 size_t mmvqa_engine_plan(mmvqa_engine* e, int B, int T, int img_h, int img_w);
+/* Plan for a GROUPED batch geometry: NI images feed B >= NI text rows.  The backbone, its taps
+ * and their BatchNorm counts are laid out for NI images, the embedding, encoder and heads for B rows; the plan adds the
+ * expanded tokens and their gradient [num_vis][B][hidden] and room for group[B] and offsets[NI+1].  Returns 0 with a
+ * message for NI < 1 or NI > B.  After it mmvqa_engine_forward_grouped is the forward; mmvqa_engine_forward,
+ * mmvqa_engine_forward_tokens, mmvqa_engine_feature_map and mmvqa_engine_backward_feature answer MMVQA_ERR_STATE.
+ * mmvqa_engine_plan is the plan with NI == B and no grouping: no buffer and no launch more than before. */
+size_t mmvqa_engine_plan_grouped(mmvqa_engine* e, int NI, int B, int T, int img_h, int img_w);
 /* Borrowed buffers of the following forward / backward calls.  Part of the WORKSPACE holds state that must survive
  * between calls (tap-validity tables of the 3x3 weight gradients, the zeroed arrival tickets of the split-K GEMM
  * launches): the first forward after a bind puts it in place on that call's stream; the caller must not write to the
@@ -618,6 +637,16 @@ int mmvqa_engine_bind(mmvqa_engine* e, float* params, float* grads, float* bufs,
 int mmvqa_engine_forward(mmvqa_engine* e, mmvqa_stream_t s, const float* img, const long long* ids,
                          const long long* seg, const long long* mask, float* logits, int logits_ld, float* feat,
                          int training, uint32_t seed);
+/* The forward of a grouped plan: img [NI,3,h,w]; group int32 [B] (non-decreasing from 0 to NI-1 in steps of at most 1)
+ * and offsets int32 [NI+1] (questions of image i: offsets[i] <= b < offsets[i+1]) are DEVICE pointers whose contents the
+ * caller has validated; both are copied into the workspace on the stream, so the backward does not read the caller's
+ * buffers.  Backbone and taps on the NI images, mmvqa_vis_expand, then embedding / encoder / heads on the B rows as in
+ * mmvqa_engine_forward.  mmvqa_engine_backward after it sums the token gradients per image (mmvqa_dvis_group_sum) and
+ * runs the backbone's backward once, on NI images.  mmvqa_engine_visual_tokens gives the [num_vis][NI][hidden] tokens.
+ * MMVQA_ERR_STATE when the current plan is not grouped. */
+int mmvqa_engine_forward_grouped(mmvqa_engine* e, mmvqa_stream_t s, const float* img, const int* group,
+                                 const int* offsets, const long long* ids, const long long* seg, const long long* mask,
+                                 float* logits, int logits_ld, float* feat, int training, uint32_t seed);
 /* accumulates into grads; dlogits same layout as logits; dfeat nullable */
 int mmvqa_engine_backward(mmvqa_engine* e, mmvqa_stream_t s, const float* dlogits, int dlogits_ld,
                           const float* dfeat);

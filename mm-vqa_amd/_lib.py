@@ -239,8 +239,12 @@ SIGNATURES = {
     "mmvqa_engine_buf_floats": (_ll, [_P]),
     "mmvqa_engine_nbt_count": (_ll, [_P]),
     "mmvqa_engine_plan": (_sz, [_P, _i, _i, _i, _i]),
+    "mmvqa_engine_plan_grouped": (_sz, [_P, _i, _i, _i, _i, _i]),
     "mmvqa_engine_bind": (_i, [_P, _P, _P, _P, _P, _P, _sz]),
     "mmvqa_engine_forward": (_i, [_P, _P, _P, _P, _P, _P, _P, _i, _P, _i, _u32]),
+    "mmvqa_engine_forward_grouped": (_i, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _i, _P, _i, _u32]),
+    "mmvqa_vis_expand": (_i, [_P, _P, _P, _P, _i, _i, _i, _i]),
+    "mmvqa_dvis_group_sum": (_i, [_P, _P, _P, _P, _i, _i, _i, _i]),
     "mmvqa_engine_backward": (_i, [_P, _P, _P, _i, _P]),
     "mmvqa_engine_backward_feature": (_i, [_P, _P, _P, _i, _P]),
     "mmvqa_engine_feature_map": (_i, [_P, C.POINTER(_P), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),

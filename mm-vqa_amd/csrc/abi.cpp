@@ -44,7 +44,15 @@ long long mmvqa_engine_buf_floats(const mmvqa_engine* e) { return e ? e->n_bufs 
 long long mmvqa_engine_nbt_count(const mmvqa_engine* e) { return e ? e->n_nbt : 0; }
 size_t mmvqa_engine_plan(mmvqa_engine* e, int B, int T, int img_h, int img_w) {
   if (!e) { mmvqa_set_error(MMVQA_ERR_ARG, "plan: null engine"); return 0; }
-  return engine_plan(e, B, T, img_h, img_w);
+  return engine_plan(e, B, B, T, img_h, img_w, false);
+}
+size_t mmvqa_engine_plan_grouped(mmvqa_engine* e, int NI, int B, int T, int img_h, int img_w) {
+  if (!e) { mmvqa_set_error(MMVQA_ERR_ARG, "plan_grouped: null engine"); return 0; }
+  if (NI < 1 || NI > B) {
+    mmvqa_set_error(MMVQA_ERR_ARG, "plan_grouped: NI=%d images for B=%d questions (1 <= NI <= B)", NI, B);
+    return 0;
+  }
+  return engine_plan(e, NI, B, T, img_h, img_w, true);
 }
 int mmvqa_engine_bind(mmvqa_engine* e, float* params, float* grads, float* bufs, long long* nbt, void* workspace,
                       size_t workspace_bytes) {
@@ -68,6 +76,13 @@ int mmvqa_engine_forward(mmvqa_engine* e, mmvqa_stream_t s, const float* img, co
                          int training, uint32_t seed) {
   if (!e || !img || !ids || !seg || !mask || !logits) return mmvqa_set_error(MMVQA_ERR_ARG, "forward: null pointer");
   return engine_forward(e, ST(s), img, ids, seg, mask, logits, logits_ld, feat, training, seed);
+}
+int mmvqa_engine_forward_grouped(mmvqa_engine* e, mmvqa_stream_t s, const float* img, const int* group,
+                                 const int* offsets, const long long* ids, const long long* seg, const long long* mask,
+                                 float* logits, int logits_ld, float* feat, int training, uint32_t seed) {
+  if (!e || !img || !group || !offsets || !ids || !seg || !mask || !logits)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "forward_grouped: null pointer");
+  return engine_forward(e, ST(s), img, ids, seg, mask, logits, logits_ld, feat, training, seed, group, offsets);
 }
 int mmvqa_engine_backward(mmvqa_engine* e, mmvqa_stream_t s, const float* dlogits, int dlogits_ld,
                           const float* dfeat) {

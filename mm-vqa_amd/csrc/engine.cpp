@@ -285,7 +285,7 @@ void plan_bn(Arena& a, BNRef& bn, double count) {
 
 static inline int conv_out(int x, int k, int s, int p) { return (x + 2 * p - k) / s + 1; }
 
-size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
+size_t engine_plan(mmvqa_engine* e, int NI, int B, int T, int IH, int IW, bool grouped) {
   const mmvqa_model_desc& d = e->d;
   if (d.encoder == 2 && (T < 2 || T > MMVQA_FB_MAX_T)) {
     mmvqa_set_error(MMVQA_ERR_ARG, "plan: the feedback-transformer takes 2 <= T <= %d tokens (T=%d): one token has no keys, "
@@ -296,7 +296,11 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
     mmvqa_set_error(MMVQA_ERR_ARG, "plan: bad B=%d T=%d (max_pos %d, num_vis %d, T<=128)", B, T, d.max_pos, d.num_vis);
     return 0;
   }
-  e->B = B; e->T = T; e->IH = IH; e->IW = IW;
+  if (NI < 1 || NI > B || (!grouped && NI != B)) {
+    mmvqa_set_error(MMVQA_ERR_ARG, "plan: NI=%d images for B=%d text rows (1 <= NI <= B, NI == B unless grouped)", NI, B);
+    return 0;
+  }
+  e->B = B; e->NI = NI; e->grouped = grouped; e->T = T; e->IH = IH; e->IW = IW;
   e->pixmask_off.clear(); e->ws_ready = false;
   Arena a;
   const int H = d.hidden;
@@ -314,7 +318,7 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
     int ph = same(IH, 3, 2, &e->SH), pw = same(IW, 3, 2, &e->SW);
     if (ph != pw) { mmvqa_set_error(MMVQA_ERR_ARG, "plan: image %dx%d needs different SAME pads per axis", IH, IW); return 0; }
     e->stem_conv.pad = ph;
-    const size_t M0 = (size_t)B * e->SH * e->SW;
+    const size_t M0 = (size_t)NI * e->SH * e->SW;
     e->z0 = a.f(M0 * 24);
     e->eff_a0 = a.f(M0 * 24);
     plan_bn(a, e->stem_bn, (double)M0);
@@ -322,11 +326,11 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
     int h = e->SH, wd = e->SW;
     size_t max_se = 0, max_separt = 0;
     for (auto& blk : e->eff) {
-      blk.N = B; blk.H = h; blk.W = wd;
+      blk.N = NI; blk.H = h; blk.W = wd;
       int p1 = same(h, 3, blk.stride, &blk.OH), p2 = same(wd, 3, blk.stride, &blk.OW);
       if (p1 != p2) { mmvqa_set_error(MMVQA_ERR_ARG, "plan: map %dx%d needs different SAME pads per axis", h, wd); return 0; }
       blk.pad = p1;
-      const size_t Min = (size_t)B * h * wd, Mout = (size_t)B * blk.OH * blk.OW;
+      const size_t Min = (size_t)NI * h * wd, Mout = (size_t)NI * blk.OH * blk.OW;
       if (blk.type == 0) {
         blk.c_a.pad = p1;
         blk.za = a.f(Mout * blk.cout); plan_bn(a, blk.b_a, (double)Mout);
@@ -339,11 +343,11 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
         blk.za = a.f(Min * blk.mid); plan_bn(a, blk.b_a, (double)Min);
         blk.zdw = a.f(Mout * blk.mid); plan_bn(a, blk.b_dw, (double)Mout);
         blk.zp = a.f(Mout * blk.cout); plan_bn(a, blk.b_p, (double)Mout);
-        blk.pool = a.f((size_t)B * blk.mid); blk.gpre = a.f((size_t)B * blk.mid); blk.gate = a.f((size_t)B * blk.mid);
-        blk.rpre = a.f((size_t)B * blk.rd); blk.r = a.f((size_t)B * blk.rd);
+        blk.pool = a.f((size_t)NI * blk.mid); blk.gpre = a.f((size_t)NI * blk.mid); blk.gate = a.f((size_t)NI * blk.mid);
+        blk.rpre = a.f((size_t)NI * blk.rd); blk.r = a.f((size_t)NI * blk.rd);
         max_mid = std::max(max_mid, std::max(Min, Mout) * blk.mid);
-        max_se = std::max(max_se, (size_t)B * blk.mid);
-        max_separt = std::max(max_separt, mmvqa_se_fc_bwd_scratch_floats(B, blk.mid, blk.rd));
+        max_se = std::max(max_se, (size_t)NI * blk.mid);
+        max_separt = std::max(max_separt, mmvqa_se_fc_bwd_scratch_floats(NI, blk.mid, blk.rd));
         if (!k_se_fc_bwd_ok(blk.rd)) {   // refuse here, not at the first backward
           mmvqa_set_error(MMVQA_ERR_ARG, "plan: squeeze-excite reduce width %d exceeds what se_fc_bwd supports", blk.rd);
           return 0;
@@ -365,23 +369,23 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
   e->SH = conv_out(IH, 7, 2, 3); e->SW = conv_out(IW, 7, 2, 3);
   e->PH = conv_out(e->SH, 3, 2, 1); e->PW = conv_out(e->SW, 3, 2, 1);
   const int w = d.resnet_width;
-  const size_t M0 = (size_t)B * e->SH * e->SW;
+  const size_t M0 = (size_t)NI * e->SH * e->SW;
   e->z0 = a.f(M0 * w);
   plan_bn(a, e->stem_bn, (double)M0);
-  e->p0 = a.f((size_t)B * e->PH * e->PW * w);
-  e->pool_idx = a.f(((size_t)B * e->PH * e->PW * w + 3) / 4);
+  e->p0 = a.f((size_t)NI * e->PH * e->PW * w);
+  e->pool_idx = a.f(((size_t)NI * e->PH * e->PW * w + 3) / 4);
   int h = e->PH, wd = e->PW;
   max_io = M0 * w; max_tapM = M0;
   for (auto& blk : e->blocks) {
-    blk.N = B; blk.H = h; blk.W = wd;
+    blk.N = NI; blk.H = h; blk.W = wd;
     blk.OH = conv_out(h, 3, blk.c2.stride, 1); blk.OW = conv_out(wd, 3, blk.c2.stride, 1);
-    const size_t Min = (size_t)B * h * wd, Mout = (size_t)B * blk.OH * blk.OW;
+    const size_t Min = (size_t)NI * h * wd, Mout = (size_t)NI * blk.OH * blk.OW;
     blk.z1 = a.f(Min * blk.c1.Cout);
     if (blk.c2.stride == 1) {   // per-pixel tap-validity table of the 3x3 weight gradient: one per geometry, in the workspace
       char key[96];
-      snprintf(key, sizeof(key), "%d,%d,%d,%d,%d", B, blk.OH, blk.OW, blk.c2.KH, blk.c2.pad);
+      snprintf(key, sizeof(key), "%d,%d,%d,%d,%d", NI, blk.OH, blk.OW, blk.c2.KH, blk.c2.pad);
       if (!e->pixmask_off.count(key))
-        e->pixmask_off[key] = mmvqa_engine::PixGeom{B, blk.OH, blk.OW, h, wd, blk.c2.KH, blk.c2.stride, blk.c2.pad, a.f(Mout)};
+        e->pixmask_off[key] = mmvqa_engine::PixGeom{NI, blk.OH, blk.OW, h, wd, blk.c2.KH, blk.c2.stride, blk.c2.pad, a.f(Mout)};
     }
     blk.z2 = a.f(Mout * blk.c2.Cout);
     blk.z3 = a.f(Mout * blk.c3.Cout);
@@ -402,7 +406,7 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
   for (int k = 0; k < 4; ++k) {
     const BlockRef& blk = e->blocks[e->layer_end[3 - k]];
     e->taps[k].HW = blk.OH * blk.OW;
-    e->taps[k].M = (long)B * blk.OH * blk.OW;
+    e->taps[k].M = (long)NI * blk.OH * blk.OW;
   }
   e->taps[4].HW = e->SH * e->SW;
   e->taps[4].M = (long)M0;
@@ -411,10 +415,10 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
     e->tapgrad[k] = a.f((size_t)e->taps[k].M * e->taps[k].C);
   }
   }
-  e->vis = a.f((size_t)5 * B * H);
+  e->vis = a.f((size_t)5 * NI * H);
   for (int i = 0; i < 3; ++i) e->sk_ws[i] = a.f(SK_WS_FLOATS);   // split-K partial tiles (caller's / side / tap stream)
   for (int i = 0; i < 3; ++i) e->sk_cnt[i] = a.f(SK_CNT_N);      // arrival tickets of ticketed split-K launches
-  e->dvis = a.f((size_t)5 * B * H);
+  e->dvis = a.f((size_t)5 * NI * H);
   e->du = a.f(max_tapM * H);
   for (int i = 0; i < 3; ++i) e->gbuf[i] = a.f(max_io);
   e->g1buf = a.f(max_mid);
@@ -480,6 +484,14 @@ size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW) {
   if (sd != 2 * half) { mmvqa_set_error(MMVQA_ERR_STATE, "plan: stat zone mismatch"); return 0; }
   e->statzone_floats = sd * 2;
   a.f(e->statzone_floats);
+  // ---- grouped batches: the tokens / their gradients per question, and the engine's copy of group[B] | offsets[NI+1]
+  // (behind everything else: the ungrouped layout is the one it always was)
+  e->vis_q = e->dvis_q = e->grp = 0;
+  if (grouped) {
+    e->vis_q = a.f((size_t)5 * B * H);
+    e->dvis_q = a.f((size_t)5 * B * H);
+    e->grp = a.f((size_t)B + NI + 1);
+  }
   e->ws_floats = (a.cur + 63) & ~(size_t)63;
   e->planned = true;
   e->bound = false;
@@ -770,7 +782,7 @@ static int conv_dgrad(mmvqa_engine* e, hipStream_t st, const ConvRef& c, const f
 // KIND_WGRAD: dW += dz^T img, dz from g0 and z0 through the stem BatchNorm's backward coefficients.
 static GemmParams stem_desc(mmvqa_engine* e, int kind, const float* g0 = nullptr) {
   const ConvRef& c = e->stem_conv;
-  const int pixels = e->B * e->SH * e->SW, taps = c.KH * c.KH * c.Cin;
+  const int pixels = e->NI * e->SH * e->SW, taps = c.KH * c.KH * c.Cin;
   GemmParams g;
   memset(&g, 0, sizeof(g));
   g.g_nchw = 1;
@@ -819,7 +831,7 @@ static GemmParams tap_desc(mmvqa_engine* e, hipStream_t st, const TapRef& t, con
 static int tap_fwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, const BNRef* bn_in) {
   REG(REG_TAP);
   const TapRef& t = e->taps[k];
-  float* vis = WS(e->vis) + (size_t)k * e->B * e->d.hidden;
+  float* vis = WS(e->vis) + (size_t)k * e->NI * e->d.hidden;
   if (tap_is_thin(e, t)) {
     TRY(prof_begin(e, st, PROF_MATRIX, 2.0 * (double)t.M * e->d.hidden * t.C, HB_TAP_THIN_FWD, 4.0 * (double)t.M * t.C));
     TRY(mmvqa_tap_thin_fwd(st, fmap, bn_in ? WS(bn_in->scale) : nullptr, bn_in ? WS(bn_in->shift) : nullptr,
@@ -842,7 +854,7 @@ static int tap_bwd(mmvqa_engine* e, hipStream_t st, int k, const float* fmap, co
   REG(REG_TAP);
   const TapRef& t = e->taps[k];
   const int Hd = e->d.hidden;
-  const float* dv = WS(e->dvis) + (size_t)k * e->B * Hd;
+  const float* dv = WS(e->dvis) + (size_t)k * e->NI * Hd;
   if (tap_is_thin(e, t)) {
     TRY(prof_begin(e, st, PROF_MATRIX, 2.0 * (double)t.M * Hd * t.C, HB_TAP_THIN_BWD, 4.0 * (double)t.M * (t.C + Hd)));
     TRY(mmvqa_tap_thin_bwd(st, fmap, bn_in ? WS(bn_in->scale) : nullptr, bn_in ? WS(bn_in->shift) : nullptr,
@@ -1017,7 +1029,7 @@ static int notify(mmvqa_engine* e, SideCtx& sc, long long lo, long long hi) {
 // --------------------------------------------------------------------------- ResNet forward / backward
 static int resnet_forward(mmvqa_engine* e, hipStream_t st) {
   const mmvqa_model_desc& d = e->d;
-  const int B = e->B, w = d.resnet_width;
+  const int B = e->NI, w = d.resnet_width;   // the backbone's batch: the images
   if (e->bn_training)
     HIP_CHECK_RET(hipMemsetAsync(stat_ptr(e, 0), 0, e->statzone_floats / 2 * sizeof(float), st));
   HIP_CHECK_RET(hipMemsetAsync(WS(e->vis), 0, (size_t)5 * B * d.hidden * sizeof(float), st));
@@ -1099,7 +1111,7 @@ static int resnet_forward(mmvqa_engine* e, hipStream_t st) {
 }
 
 static int resnet_backward(mmvqa_engine* e, hipStream_t st) {
-  const int B = e->B, w = e->d.resnet_width;
+  const int B = e->NI, w = e->d.resnet_width;
   HIP_CHECK_RET(hipMemsetAsync(stat_ptr(e, 0) + e->statzone_floats / 4, 0,
                                e->statzone_floats / 2 * sizeof(float), st));
   SideCtx sc(e, st);
@@ -1243,7 +1255,7 @@ static int frozen_backbone_backward(mmvqa_engine* e, hipStream_t st) {
 // --------------------------------------------------------------------------- EfficientNetV2 forward / backward
 static int effnet_forward(mmvqa_engine* e, hipStream_t st) {
   const mmvqa_model_desc& d = e->d;
-  const int B = e->B;
+  const int B = e->NI;
   if (e->bn_training)
     HIP_CHECK_RET(hipMemsetAsync(stat_ptr(e, 0), 0, e->statzone_floats / 2 * sizeof(float), st));
   HIP_CHECK_RET(hipMemsetAsync(WS(e->vis), 0, (size_t)5 * B * d.hidden * sizeof(float), st));
@@ -1306,7 +1318,7 @@ static int effnet_forward(mmvqa_engine* e, hipStream_t st) {
 }
 
 static int effnet_backward(mmvqa_engine* e, hipStream_t st) {
-  const int B = e->B;
+  const int B = e->NI;
   HIP_CHECK_RET(hipMemsetAsync(stat_ptr(e, 0) + e->statzone_floats / 4, 0,
                                e->statzone_floats / 2 * sizeof(float), st));
   const int nb = (int)e->eff.size();
@@ -1920,8 +1932,14 @@ static int encoder_backward(mmvqa_engine* e, hipStream_t st, SideReads& sr) {
 }
 
 int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long long* ids, const long long* seg,
-                   const long long* mask, float* logits, int logits_ld, float* feat, int training, uint32_t seed) {
+                   const long long* mask, float* logits, int logits_ld, float* feat, int training, uint32_t seed,
+                   const int* group, const int* offsets) {
   if (!e->planned || !e->bound) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_forward: plan/bind first");
+  if (e->grouped != (group != nullptr))
+    return mmvqa_set_error(MMVQA_ERR_STATE, e->grouped ? "engine_forward: the plan is grouped (NI=%d images, B=%d rows): call "
+                                                         "mmvqa_engine_forward_grouped, or plan again"
+                                                       : "engine_forward_grouped: the plan is not grouped (NI=%d, B=%d): call "
+                                                         "mmvqa_engine_plan_grouped first", e->NI, e->B);
   TRY(prepare_workspace(e, st));
   const mmvqa_model_desc& d = e->d;
   const int out_w = d.head_kind == 2 ? d.hidden : d.n_classes;   // headless: the caller's buffer receives h
@@ -1938,12 +1956,23 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
   if (e->prec != MMVQA_PREC_F32 && d.cnn != 0)
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward: f16 operand mode covers the ResNet encoders only");
   StepScope scope(e, e->prec);
+  if (e->grouped) {   // the engine's own copy of the maps: the backward reads offsets long after the caller's buffers may be gone
+    int* grp = reinterpret_cast<int*>(WS(e->grp));
+    HIP_CHECK_RET(hipMemcpyAsync(grp, group, (size_t)e->B * sizeof(int), hipMemcpyDeviceToDevice, st));
+    HIP_CHECK_RET(hipMemcpyAsync(grp + e->B, offsets, ((size_t)e->NI + 1) * sizeof(int), hipMemcpyDeviceToDevice, st));
+  }
   if (d.cnn == 1) TRY(effnet_forward(e, st)); else TRY(resnet_forward(e, st));
   const float pe = training ? d.p_emb_drop : 0.f;
   e->prof_reg = REG_EMBED;
+  const float* vis = WS(e->vis);
+  if (e->grouped) {   // question b reads the tokens of image group[b]
+    RUNB(HB_NONE, 8.0 * d.num_vis * e->B * d.hidden,
+         mmvqa_vis_expand(st, WS(e->vis), reinterpret_cast<const int*>(WS(e->grp)), WS(e->vis_q), e->NI, e->B, d.hidden, d.num_vis));
+    vis = WS(e->vis_q);
+  }
   RUN(PROF_OTHER, 0,
       mmvqa_embed_fwd(st, ids, seg, PRM(e->emb_word), PRM(e->emb_pos), PRM(e->emb_type), PRM(e->emb_ln.g),
-                  PRM(e->emb_ln.b), WS(e->vis), WS(e->emb_out), WS(e->emb_xhat), WS(e->emb_rstd), e->B, e->T,
+                  PRM(e->emb_ln.b), vis, WS(e->emb_out), WS(e->emb_xhat), WS(e->emb_rstd), e->B, e->T,
                   d.hidden, d.num_vis, 1e-12f, pe, site_seed(e, 100, 0)));
   e->prof_reg = REG_BACKBONE;
   const float* h = nullptr;
@@ -1955,8 +1984,8 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
   return heads_forward(e, st, h);
 }
 
-// Where the last forward left the num_vis visual tokens: [num_vis][B][hidden] inside the bound workspace, as
-// mmvqa_embed_fwd reads them; valid until the next forward.
+// Where the last forward left the num_vis visual tokens: [num_vis][NI][hidden] inside the bound workspace (NI == B unless
+// the plan is grouped), as the taps write them; valid until the next forward.
 int engine_visual_tokens(mmvqa_engine* e, const float** vis) {
   if (!e->planned || !e->bound || (!e->img && !e->tokens_only))
     return mmvqa_set_error(MMVQA_ERR_STATE, "engine_visual_tokens: plan/bind and run a forward first");
@@ -1973,6 +2002,7 @@ int engine_forward_tokens(mmvqa_engine* e, hipStream_t st, const float* vis, con
   if (e->prec != MMVQA_PREC_F32)
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward_tokens: runs with fp32 operands, not in the f16 operand mode");
   if (!e->planned || !e->bound) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_forward_tokens: plan/bind first");
+  if (e->grouped) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_forward_tokens: the plan is grouped; plan again with mmvqa_engine_plan");
   const mmvqa_model_desc& d = e->d;
   const int out_w = d.head_kind == 2 ? d.hidden : d.n_classes;
   if (logits_ld < out_w || (logits_ld & 3))
@@ -2028,7 +2058,11 @@ int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int d
   RUN(PROF_OTHER, 0,
       mmvqa_embed_bwd(st, WS(e->t_a), e->ids, e->seg, WS(e->emb_xhat), WS(e->emb_rstd), PRM(e->emb_ln.g),
                   GRD(e->emb_word), GRD(e->emb_pos), GRD(e->emb_type), GRD(e->emb_ln.g), GRD(e->emb_ln.b),
-                  WS(e->dvis), e->B, e->T, d.hidden, d.num_vis, pe, site_seed(e, 100, 0), 0));
+                  WS(e->grouped ? e->dvis_q : e->dvis), e->B, e->T, d.hidden, d.num_vis, pe, site_seed(e, 100, 0), 0));
+  if (e->grouped)   // the gradient of an image's token: the sum over its questions
+    RUNB(HB_NONE, 4.0 * d.num_vis * (e->B + e->NI) * d.hidden,
+         mmvqa_dvis_group_sum(st, WS(e->dvis_q), reinterpret_cast<const int*>(WS(e->grp)) + e->B, WS(e->dvis), e->NI, e->B,
+                              d.hidden, d.num_vis));
   e->prof_reg = REG_BACKBONE;
   if (e->grad_cb) e->grad_cb(e->grad_cb_user, 0, e->emb_hi);            // embedding tables + LayerNorm
   if (e->frozen & MMVQA_FREEZE_BACKBONE) return frozen_backbone_backward(e, st);
@@ -2044,6 +2078,7 @@ static int feature_tap(const mmvqa_engine* e, size_t* off, int* H, int* W, int* 
 
 int engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, int* C) {
   if (!e->planned || !e->bound) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_feature_map: plan/bind and run a forward first");
+  if (e->grouped) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_feature_map: attribution on a grouped plan is not built; plan again with mmvqa_engine_plan");
   size_t off = 0; int h = 0, w = 0, c = 0;
   (void)feature_tap(e, &off, &h, &w, &c);
   if (A) *A = WS(off);
@@ -2059,6 +2094,9 @@ int engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, int* C)
 // forward is conditional on `training` except dropout probabilities and BatchNorm statistics).  Parameters, gradient
 // buffer and BatchNorm buffers are not written.
 int engine_backward_feature(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, float* dA) {
+  if (e->planned && e->grouped)
+    return mmvqa_set_error(MMVQA_ERR_STATE, "engine_backward_feature: attribution on a grouped plan is not built; plan again with "
+                                            "mmvqa_engine_plan and run an eval-mode forward");
   if (e->planned && e->bound && e->tokens_only)
     return mmvqa_set_error(MMVQA_ERR_STATE, "engine_backward_feature: the last forward ran from given visual tokens, so the "
                                             "feature map in the workspace is not theirs; run an eval-mode forward first");

@@ -141,6 +141,13 @@ struct mmvqa_engine {
 
   // ---- plan
   int B = 0, T = 0, IH = 0, IW = 0;
+  // grouped batches: NI images feed the B text rows.  The backbone, its taps, vis and dvis are
+  // sized by NI, everything from the embedding on by B; NI == B and grouped == false for the plan of mmvqa_engine_plan.
+  // vis_q / dvis_q [num_vis][B][hidden]: what the embed kernels read / write in a grouped step; grp: int32 group[B] then
+  // offsets[NI+1], the engine's own copy of the caller's maps
+  int NI = 0;
+  bool grouped = false;
+  size_t vis_q = 0, dvis_q = 0, grp = 0;
   bool planned = false, bound = false;
   size_t ws_floats = 0;
   int SH = 0, SW = 0, PH = 0, PW = 0;  // stem output dims / pooled dims
@@ -205,9 +212,12 @@ struct mmvqa_engine {
 };
 
 // engine.cpp: what the mmvqa_engine_* entry points of abi.cpp run behind their argument checks
-size_t engine_plan(mmvqa_engine* e, int B, int T, int IH, int IW);
+// (NI images feed B text rows; grouped = false is the plan of mmvqa_engine_plan, NI == B.  group / offsets: the grouped
+// forward's maps, null for the ungrouped one)
+size_t engine_plan(mmvqa_engine* e, int NI, int B, int T, int IH, int IW, bool grouped);
 int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long long* ids, const long long* seg,
-                   const long long* mask, float* logits, int logits_ld, float* feat, int training, uint32_t seed);
+                   const long long* mask, float* logits, int logits_ld, float* feat, int training, uint32_t seed,
+                   const int* group = nullptr, const int* offsets = nullptr);
 int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, const float* dfeat);
 int engine_visual_tokens(mmvqa_engine* e, const float** vis);
 int engine_forward_tokens(mmvqa_engine* e, hipStream_t st, const float* vis, const long long* ids, const long long* seg,

@@ -29,6 +29,11 @@ which has the GPU open -- they inherit none of its GPU state and never touch the
 Determinism: a batch is a function of (seed, epoch, batch index, rank) only.  The epoch order is a seeded
 permutation sharded across ranks like DistributedSampler (drop_last=False: the shard is padded from the head); the
 MLM masking rng is seeded per sample; worker count and timing do not enter.
+
+Grouped batches (VQA with --group_by_image): VqaGroupedDataset's item is an IMAGE with all of its
+questions, GroupedBatchSampler packs images in the same seeded order until the next one's questions would pass
+batch_size (which keeps counting questions), collate_grouped adds the host map `group`.  The augment parameters are drawn
+per image, so every question of an image sees the same view in a step.
 """
 from __future__ import annotations
 
@@ -606,6 +611,68 @@ def collate_category(items):
     return out
 
 
+# --------------------------------------------------------------------------- grouped batches
+def group_rows_by_image(rows):
+    """VQA-Med asks several questions of one image (four per train / val image in 2019).  -> [(image path, [row index])]
+    over data.vqa_tables rows: images in first-appearance order, an image's rows in table order."""
+    by = {}
+    for i, r in enumerate(rows):
+        by.setdefault(r[0], []).append(i)
+    return list(by.items())
+
+
+class VqaGroupedDataset(torch.utils.data.Dataset):
+    """VqaDataset with one item per IMAGE: item (epoch, image) -> (uint8 [H, W, 3], ids [n, T], seg, mask, answer
+    indices [n], table rows [n]) of the image's n questions, the image decoded once.  categories as VqaDataset's: the
+    item gains category ids [n].  Batches are packed by collate_grouped and drawn by GroupedBatchSampler, which counts
+    QUESTIONS: an image with more than batch_size of them is refused when the sampler is built."""
+
+    def __init__(self, rows, tokenizer, max_position_embeddings=28, categories=None):
+        self.rows, self.tok, self.T = list(rows), tokenizer, max_position_embeddings
+        self.images = group_rows_by_image(self.rows)
+        self.categories = None if categories is None else dict(categories)
+        if self.categories is not None:
+            missing = sorted({r[3] for r in self.rows} - set(self.categories))
+            if missing:
+                raise ValueError(f"VqaGroupedDataset: categories {missing} of the rows are not in the category map")
+        self.collate = collate_grouped
+
+    def __len__(self):
+        return len(self.images)
+
+    def counts(self):
+        return [len(idx) for _, idx in self.images]
+
+    def batch_sampler(self, batch_size, shuffle, seed=0, rank=0, world=1):
+        return GroupedBatchSampler(self.counts(), batch_size, shuffle, seed, rank, world)
+
+    def __getitem__(self, key):
+        _epoch, i = key
+        path, idx = self.images[i]
+        enc = [text.encode_text_vqa(self.rows[r][1], self.tok, self.T) for r in idx]
+        ids, seg, mask = (torch.tensor([e[k] for e in enc], dtype=torch.long) for k in range(3))
+        item = (decode(path), ids, seg, mask, torch.tensor([self.rows[r][2] for r in idx], dtype=torch.long),
+                torch.tensor(idx, dtype=torch.int64))
+        if self.categories is None:
+            return item
+        return item + (torch.tensor([self.categories[self.rows[r][3]] for r in idx], dtype=torch.int64),)
+
+
+def collate_grouped(items):
+    """-> dict: pixels / shapes [NI, 2] per IMAGE as collate packs them; ids / seg / mask [B, T], target, index [B]
+    (table rows) and, where the items carry it, category [B] per QUESTION, an image's questions adjacent and in table
+    order; group [B] int64 on the host, group[b] = the batch's image of question b (Model.forward_grouped)."""
+    imgs = [it[0] for it in items]
+    cat = lambda k: torch.cat([it[k] for it in items])   # noqa: E731
+    out = dict(pixels=torch.from_numpy(np.concatenate([np.ascontiguousarray(a).reshape(-1) for a in imgs])),
+               shapes=torch.tensor([a.shape[:2] for a in imgs], dtype=torch.int64),
+               ids=cat(1), seg=cat(2), mask=cat(3), target=cat(4), index=cat(5),
+               group=torch.repeat_interleave(torch.arange(len(items)), torch.tensor([it[1].shape[0] for it in items])))
+    if len(items[0]) > 6:
+        out["category"] = cat(6)
+    return out
+
+
 def collate_supcon(items):
     """RocoSupConDataset items -> collate's dict with n images and the text already in process_tensors' layout
     (supcon_utils.py:253-256): ids = (captions; translations), target = (caption targets; translation targets),
@@ -738,16 +805,79 @@ class EpochBatchSampler(torch.utils.data.Sampler):
         return -(-int(math.ceil(self.n / self.world)) // self.bs)
 
 
+class GroupedBatchSampler(EpochBatchSampler):
+    """EpochBatchSampler over IMAGES whose batches are sized in QUESTIONS: counts[i] = the questions of image i.  The
+    images come in the same seeded epoch order; a batch is closed when the next image's questions would push it past
+    batch_size, so no batch holds more than batch_size questions and none is empty.  An image with more questions than
+    batch_size cannot be placed and is refused here, when the loader is built.
+
+    Ranks: the WHOLE epoch order is packed first and whole batches are dealt to the ranks (batch j goes to rank
+    j % world), the list padded from its head to a multiple of world as the ungrouped shard pads its images.  Every rank
+    therefore runs the same number of steps, whatever the counts: a data-parallel step is one gradient all-reduce, and
+    ranks that packed their own image shards would close their batches at different places and fall out of step.  The
+    batches of an epoch are a function of (seed, epoch, rank) and the table alone."""
+
+    def __init__(self, counts, batch_size, shuffle, seed=0, rank=0, world=1):
+        self.counts = [int(c) for c in counts]
+        super().__init__(len(self.counts), batch_size, shuffle, seed, rank, world)
+        worst = max(self.counts, default=0)
+        if worst > batch_size:
+            raise ValueError(f"an image of the table has {worst} questions, more than --batch_size {batch_size} (which "
+                             "counts questions): it fits no grouped batch")
+
+    def order(self):
+        """the epoch's order of all images, the same on every rank"""
+        if self.shuffle:
+            g = torch.Generator().manual_seed(self.seed + self.epoch)
+            return torch.randperm(self.n, generator=g).tolist()
+        return list(range(self.n))
+
+    def all_batches(self):
+        """the epoch's batches before they are dealt to the ranks"""
+        out, cur, n = [], [], 0
+        for i in self.order():
+            if cur and n + self.counts[i] > self.bs:
+                out.append(cur)
+                cur, n = [], 0
+            cur.append(i)
+            n += self.counts[i]
+        if cur:
+            out.append(cur)
+        return out
+
+    def batches(self):
+        """this rank's batches: every world-th of all_batches, padded from the head so that all ranks have as many"""
+        allb = self.all_batches()
+        total = int(math.ceil(len(allb) / self.world)) * self.world
+        allb += (allb * int(math.ceil(total / max(len(allb), 1))))[:total - len(allb)]
+        return allb[self.rank:total:self.world]
+
+    def indices(self):
+        return [i for b in self.batches() for i in b]
+
+    def __iter__(self):
+        for b in self.batches():
+            yield [(self.epoch, i) for i in b]
+
+    def __len__(self):
+        return len(self.batches())
+
+
 class HostLoader:
     """iterates one epoch of host batches: (batch dict, augment params or None, {"epoch", "batch"}).  With views=V the
     params are V per image, sample_params(V * n, ...) from the batch's generator: params[i * V + v] is view v of
-    image i (TwoCropTransform's V calls in a row).  A dataset with a `collate` attribute packs its own batches."""
+    image i (TwoCropTransform's V calls in a row).  A dataset with a `collate` attribute packs its own batches, one with
+    a `batch_sampler` method draws them (VqaGroupedDataset: batch_size counts questions, the params stay one set per
+    IMAGE, so every question of an image sees the same view in a step)."""
 
     def __init__(self, dataset, batch_size, shuffle=True, seed=0, rank=0, world=1, num_workers=None, aug=None,
                  size=224, pin_memory=True, views=1):
         if int(views) < 1:
             raise ValueError("views must be >= 1")
-        self.sampler = EpochBatchSampler(len(dataset), batch_size, shuffle, seed, rank, world)
+        if hasattr(dataset, "batch_sampler"):
+            self.sampler = dataset.batch_sampler(batch_size, shuffle, seed, rank, world)
+        else:
+            self.sampler = EpochBatchSampler(len(dataset), batch_size, shuffle, seed, rank, world)
         self.seed, self.rank, self.aug, self.size, self.views = seed, rank, aug, size, int(views)
         self.num_workers = default_workers() if num_workers is None else int(num_workers)
         kw = {}
@@ -828,10 +958,16 @@ class DeviceFeeder:
     RocoSupConDataset(teacher_tokenizer=...)): the batch is a 6-tuple whose last element is the int64 device tensor
     [2n, 1 + L] of teacher rows (data.teacher_row: length, ids), in the slot like the rest.  Not together with pairs or
     category.  Whenever a host batch carries `teacher_T` (this one, or OnlineDistillDataset's, whose teacher rows are the
-    batch's fifth tensor) the log entry gains `teacher_T`, the batch's longest teacher input as a host integer."""
+    batch's fifth tensor) the log entry gains `teacher_T`, the batch's longest teacher input as a host integer.
+
+    grouped=True (VQA with --group_by_image; the host batches come from a VqaGroupedDataset): img holds the batch's NI
+    images, the text tensors and target its B >= NI questions, and the batch tuple ends with `group`, the int64 HOST
+    tensor [B] naming the image of each question (after category, where both are on).  The augment parameters are one
+    set per IMAGE, so every question of an image sees the same view in a step -- the ungrouped loop draws a view per
+    question.  The log entry gains `group`; `index` names the table rows of the questions."""
 
     def __init__(self, host: HostLoader, device, train=True, depth=2, mean=(0.5, 0.5, 0.5), std=(0.5, 0.5, 0.5),
-                 fused=True, pairs=False, category=False, teacher=False):
+                 fused=True, pairs=False, category=False, teacher=False, grouped=False):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("DeviceFeeder runs on the GPU only (no CPU fallback)")
@@ -842,6 +978,9 @@ class DeviceFeeder:
         self.pairs, self.category, self.teacher = bool(pairs), bool(category), bool(teacher)
         if self.pairs + self.category + self.teacher > 1:
             raise ValueError("DeviceFeeder: pairs, category and teacher are the sixth element of different loops' batches")
+        self.grouped = bool(grouped)
+        if self.grouped and (self.pairs or self.teacher or self.views != 1):
+            raise ValueError("DeviceFeeder: grouped batches are the VQA loop's (one view, no pairs, no teacher)")
         aug = host.aug or {}
         self.aug = DeviceAugment(size=host.size, train=train, mean=mean, std=std, device=device, **aug)
         self.stream, self.priority = low_priority_stream(device)
@@ -937,6 +1076,11 @@ class DeviceFeeder:
                 td = buf["teacher"][:tr.shape[0]]
                 td.copy_(tr, non_blocking=True)
                 out.append(td)
+            if self.grouped:
+                if "group" not in batch:
+                    raise ValueError("DeviceFeeder(grouped=True): the host batches carry no `group` "
+                                     "(VqaGroupedDataset reports it)")
+                out.append(batch["group"].clone())     # stays on the host: Model.forward_grouped validates it there
             slot.ready = torch.cuda.Event()
             slot.ready.record(s)
         entry = dict(meta, index=batch["index"].tolist(), params=params, shapes=batch["shapes"].tolist())
@@ -946,6 +1090,8 @@ class DeviceFeeder:
             entry["category"] = batch["category"].tolist()
         if "teacher_T" in batch:
             entry["teacher_T"] = int(batch["teacher_T"])
+        if self.grouped:
+            entry["group"] = batch["group"].tolist()
         self._queue.append((slot, tuple(out), entry))
         return True
 

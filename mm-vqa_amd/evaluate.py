@@ -70,13 +70,17 @@ def category_metrics(preds, targets, categories, idx2ans, prefix=""):
 
 
 @torch.no_grad()
-def _run(loader, model, criterion, categories, idx2ans, category, prefix):
+def _run(loader, model, criterion, categories, idx2ans, category, prefix, grouped=False):
     model.eval()
     if hasattr(criterion, "eval"):
         criterion.eval()                  # utils.py:693 / 772: a smoothing criterion evaluates as plain cross entropy
     losses, PREDS, TARGETS = [], [], []
-    for img, question_token, segment_ids, attention_mask, target in loader:
-        logits, _, _ = model(img, question_token, segment_ids, attention_mask)       # utils.py:711 / 789
+    for batch in loader:
+        img, question_token, segment_ids, attention_mask, target = batch[:5]
+        if grouped:             # --group_by_image: img holds each image once, the batch's LAST element maps questions to images
+            logits, _, _ = model.forward_grouped(img, batch[-1], question_token, segment_ids, attention_mask)
+        else:
+            logits, _, _ = model(img, question_token, segment_ids, attention_mask)   # utils.py:711 / 789
         loss = criterion(logits, target)
         losses.append(loss.detach().cpu().numpy())
         PREDS.append(logits.softmax(1).argmax(1).detach())                            # utils.py:721 / 800
@@ -94,9 +98,11 @@ def validate(loader, model, criterion, categories, idx2ans, category=None):
     return _run(loader, model, criterion, categories, idx2ans, category, "val_")
 
 
-def test(loader, model, criterion, categories, idx2ans, category=None):
-    """utils.py:769-843 -> (test_loss, PREDS, acc, bleu)"""
-    return _run(loader, model, criterion, categories, idx2ans, category, "")
+def test(loader, model, criterion, categories, idx2ans, category=None, grouped=False):
+    """utils.py:769-843 -> (test_loss, PREDS, acc, bleu).  grouped: the batches are grouped ones (train.py
+    --group_by_image), (img of the distinct images, ids, seg, mask, target, group), run through Model.forward_grouped;
+    PREDS and `categories` are in the loader's order"""
+    return _run(loader, model, criterion, categories, idx2ans, category, "", grouped)
 
 
 def write_test_files(rows, columns, predictions, idx2ans, out_dir, model_name):

@@ -136,6 +136,61 @@ class _ModelFn(torch.autograd.Function):
         return (None,) * 8
 
 
+class _GroupedModelFn(torch.autograd.Function):
+    """_ModelFn for a grouped batch: `maps` is the device copy of group | offsets (group_maps)"""
+
+    @staticmethod
+    def forward(ctx, model, anchor, img, maps, ids, seg, mask, prec, frozen):
+        ctx.model = model
+        ctx.prec = prec
+        ctx.frozen = frozen
+        return model._engine_forward(img, ids, seg, mask, prec, frozen[0], maps=maps)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        ctx.model._engine_backward(*grads, prec=ctx.prec, frozen=ctx.frozen)
+        return (None,) * 9
+
+
+def group_maps(group, n_images: int, n_rows: int):
+    """Validates the image-of-question map of a grouped batch on the host and returns one int32 CPU tensor
+    [n_rows + n_images + 1]: group, then offsets (the questions of image i are rows offsets[i] .. offsets[i+1]-1).
+    `group` is a host integer tensor or sequence of length n_rows: non-decreasing, starting at 0, rising by at most 1,
+    ending at n_images - 1 -- the questions of an image are adjacent and every image has one.  ValueError otherwise."""
+    if isinstance(group, torch.Tensor):
+        if group.is_cuda:
+            raise ValueError("group must be a host tensor or a sequence: it is validated before anything is launched")
+        if group.dtype.is_floating_point or group.dtype == torch.bool or group.dim() != 1:
+            raise ValueError(f"group must be a 1-d integer tensor, not {group.dtype} with shape {tuple(group.shape)}")
+        g = [int(v) for v in group.tolist()]
+    else:
+        g = list(group)
+        if any(isinstance(v, bool) or int(v) != v for v in g):
+            raise ValueError("group must hold integers")
+        g = [int(v) for v in g]
+    if n_images < 1 or n_rows < n_images:
+        raise ValueError(f"a grouped batch has 1 <= images <= questions, not {n_images} images for {n_rows} questions")
+    if len(g) != n_rows:
+        raise ValueError(f"group has {len(g)} entries for {n_rows} questions")
+    if min(g) < 0:
+        raise ValueError(f"group holds a negative image index ({min(g)})")
+    if g[0] != 0:
+        raise ValueError(f"group must start at image 0, not {g[0]}")
+    offsets = [0]
+    for b in range(1, n_rows):
+        step = g[b] - g[b - 1]
+        if step < 0:
+            raise ValueError(f"group decreases at question {b} ({g[b - 1]} -> {g[b]}): the questions of an image are adjacent")
+        if step > 1:
+            raise ValueError(f"group skips from image {g[b - 1]} to {g[b]} at question {b}: every image has a question")
+        if step:
+            offsets.append(b)
+    offsets.append(n_rows)
+    if g[-1] != n_images - 1:
+        raise ValueError(f"group ends at image {g[-1]}, the batch has {n_images} images (last index {n_images - 1})")
+    return torch.tensor(g + offsets, dtype=torch.int32)
+
+
 def autocast_precision(model_desc) -> int:
     """Operand precision of a forward run now: PREC_F16 inside torch.autocast("cuda", dtype=torch.float16) (what the
     reference's torch.cuda.amp.autocast() means), PREC_F32 outside autocast.  Any other autocast dtype, and an
@@ -414,11 +469,15 @@ class Model(nn.Module):
         return self
 
     # ------------------------------------------------------------------ engine calls
-    def _ensure_plan(self, B, T, IH, IW):
-        key = (B, T, IH, IW)
+    def _ensure_plan(self, B, T, IH, IW, NI=None):
+        """NI: the images of a grouped batch (forward_grouped); None: the ungrouped plan, one image per row"""
+        key = (B, T, IH, IW, NI)
         lib = L.lib()
         if self._plan_key != key:
-            nbytes = lib.mmvqa_engine_plan(self._handle, B, T, IH, IW)
+            if NI is None:
+                nbytes = lib.mmvqa_engine_plan(self._handle, B, T, IH, IW)
+            else:
+                nbytes = lib.mmvqa_engine_plan_grouped(self._handle, NI, B, T, IH, IW)
             if nbytes == 0:
                 L.check(-1)
             if self._ws is None or self._ws.numel() < nbytes:
@@ -432,7 +491,11 @@ class Model(nn.Module):
         """dropout stream for training-mode forwards (counter-based RNG in the kernels)"""
         self._seed_ctr = int(seed) & 0x7FFFFFFF
 
-    def _engine_forward(self, img, ids, seg, mask, prec=0, frozen_flags=0):
+    def _plan_is_grouped(self):
+        return self._plan_key is not None and self._plan_key[4] is not None
+
+    def _engine_forward(self, img, ids, seg, mask, prec=0, frozen_flags=0, maps=None):
+        """maps: None, or the device int32 group | offsets of a grouped batch (img then holds its NI images)"""
         d = self._desc
         if d.encoder == L.ENC_FEEDBACK and not 2 <= ids.shape[1] <= L.FB_MAX_T:
             raise ValueError(f"the feedback-transformer takes 2 <= T <= {L.FB_MAX_T} tokens, not T={ids.shape[1]}: one token "
@@ -443,7 +506,8 @@ class Model(nn.Module):
         img = img.contiguous().float()
         ids, seg, mask = (t.contiguous().long() for t in (ids, seg, mask))
         B, T = ids.shape
-        self._ensure_plan(B, T, img.shape[2], img.shape[3])
+        NI = None if maps is None else img.shape[0]
+        self._ensure_plan(B, T, img.shape[2], img.shape[3], NI)
         rows = B if d.head_kind == L.HEAD_VQA else B * T
         V = d.hidden if d.head_kind == L.HEAD_NONE else d.n_classes   # headless: the buffer receives h
         ld = (V + 3) & ~3
@@ -455,9 +519,15 @@ class Model(nn.Module):
         self._seed_ctr = (self._seed_ctr * 1103515245 + 12345) & 0x7FFFFFFF
         L.check(L.lib().mmvqa_engine_set_precision(self._handle, int(prec)))
         L.check(L.lib().mmvqa_engine_set_frozen(self._handle, int(frozen_flags)))   # recorded by the forward for its backward
-        L.check(L.lib().mmvqa_engine_forward(self._handle, L.stream_ptr(), L.ptr(img), L.ptr(ids), L.ptr(seg),
-                                             L.ptr(mask), L.ptr(buf), ld, L.ptr(feat), 1 if self.training else 0,
-                                             self._seed_ctr))
+        if maps is None:
+            L.check(L.lib().mmvqa_engine_forward(self._handle, L.stream_ptr(), L.ptr(img), L.ptr(ids), L.ptr(seg),
+                                                 L.ptr(mask), L.ptr(buf), ld, L.ptr(feat), 1 if self.training else 0,
+                                                 self._seed_ctr))
+        else:
+            L.check(L.lib().mmvqa_engine_forward_grouped(self._handle, L.stream_ptr(), L.ptr(img), L.ptr(maps),
+                                                         C.c_void_p(maps.data_ptr() + 4 * B), L.ptr(ids), L.ptr(seg),
+                                                         L.ptr(mask), L.ptr(buf), ld, L.ptr(feat),
+                                                         1 if self.training else 0, self._seed_ctr))
         self._fwd_state = (img, ids, seg, mask, rows, V, ld)
         logits = buf[:, :V]
         logits = logits.view(B, T, V) if d.head_kind != L.HEAD_VQA else logits
@@ -516,6 +586,7 @@ class Model(nn.Module):
         d = self._desc
         if d.head_kind != 1:
             raise NotImplementedError("feature_gradient needs the VQA head (dataset='VQA-Med'): one row of logits per sample")
+        self._refuse_after_grouped("feature_gradient / feature_map")
         lib = L.lib()
         was_training = self.training
         self.train(False)
@@ -531,6 +602,14 @@ class Model(nn.Module):
         off = ap.value - self._ws.data_ptr()
         A = self._ws[off:off + 4 * B * H * W * Cc].view(torch.float32).view(B, H, W, Cc).clone()   # (the next forward overwrites the workspace)
         return logits, A
+
+    def _refuse_after_grouped(self, who):
+        """attribution and cached-token forwards are not built for grouped batches: directly after forward_grouped the
+        engine's plan, its tokens and its feature maps are those of NI images for B rows, which these entries would
+        silently re-plan away.  A plain forward() in between (which re-plans) makes them valid again."""
+        if self._plan_is_grouped():
+            raise L.MMVQAError(f"{who}: the last step was a grouped one (forward_grouped); attribution and cached visual "
+                               "tokens are not built for grouped batches -- run forward() first")
 
     def deepest_tap(self):
         """-> (weight [hidden, C] of the 1x1 tap that the deepest feature map feeds, the visual-token row it fills, its
@@ -580,6 +659,7 @@ class Model(nn.Module):
             raise NotImplementedError("visual tokens (visual_tokens / forward_tokens) are fp32 in this version: call it "
                                       "outside torch.autocast")
         d = self._desc
+        self._refuse_after_grouped("forward_tokens")
         if not vis.is_cuda:
             raise L.MMVQAError("mm-vqa_amd runs on the GPU only: move the model and inputs to 'cuda' "
                                "(there is no CPU fallback by design)")
@@ -632,6 +712,34 @@ class Model(nn.Module):
         out = _ModelFn.apply(self, self._anchor, img, input_ids, segment_ids, input_mask, prec, frozen)
         if self.dataset == "VQA-Med":
             return out, 0, 0   # models/mmbert.py:167
+        return out
+
+    def forward_grouped(self, img, group, input_ids, segment_ids, input_mask):
+        """forward for a batch in which several text rows ask about one image (VQA-Med: four questions per image):
+        img [NI, 3, H, W] holds each image once, input_ids / segment_ids / input_mask are [B, T] with B >= NI, and
+        group[b] in [0, NI) names the image of row b.  The model is the reference's with one change: the visual-token
+        rows of sample b are those of image group[b].  The backbone and its taps run once on the NI images, forward and
+        backward; the gradient of an image's tokens is the sum over its rows.  Train-mode BatchNorm therefore sees each
+        image once.  Same return contract, autocast, requires_grad and frozen-backbone handling
+        as forward.
+
+        group is a HOST integer tensor or sequence of length B (what data.collate_grouped produces), non-decreasing from
+        0 to NI - 1 in steps of at most 1; it is validated before anything is launched (ValueError), nothing is read back
+        from the device."""
+        ids = input_ids
+        if ids.dim() != 2 or img.dim() != 4:
+            raise ValueError(f"forward_grouped takes img [NI, 3, H, W] and input_ids [B, T], not {tuple(img.shape)} and "
+                             f"{tuple(ids.shape)}")
+        maps = group_maps(group, img.shape[0], ids.shape[0])
+        if not img.is_cuda:
+            raise L.MMVQAError("mm-vqa_amd runs on the GPU only: move the model and inputs to 'cuda' "
+                               "(there is no CPU fallback by design)")
+        prec = autocast_precision(self._desc)
+        frozen = self._frozen_state() if torch.is_grad_enabled() else _NOT_FROZEN
+        maps = maps.to(img.device, non_blocking=True)                        # group and offsets go up in one copy
+        out = _GroupedModelFn.apply(self, self._anchor, img, maps, input_ids, segment_ids, input_mask, prec, frozen)
+        if self.dataset == "VQA-Med":
+            return out, 0, 0
         return out
 
     # ------------------------------------------------------------------ data-parallel overlap

@@ -39,6 +39,20 @@ def vqa_batch(B, T=32, hw=224, vocab=30522, n_classes=1552, seed=1234, device="c
     return tuple(t.to(device) for t in (img, ids, seg, mask, tgt))
 
 
+def vqa_grouped_batch(NI, counts, T=32, hw=224, vocab=30522, n_classes=1552, seed=1234, device="cpu"):
+    """A grouped VQA batch (Model.forward_grouped): NI images, counts[i] questions of image i, B = sum(counts) rows.
+    -> (img [NI,3,hw,hw], group [B] int64 on the HOST, ids, seg, mask [B,T], tgt [B]).  The text rows and targets are
+    those of vqa_batch(B, ...) at the same seed, the images its first NI."""
+    counts = [int(c) for c in counts]
+    if len(counts) != NI or min(counts, default=0) < 1:
+        raise ValueError(f"counts must name at least one question for each of the {NI} images, not {counts}")
+    B = sum(counts)
+    img, ids, seg, mask, tgt = vqa_batch(B, T, hw, vocab, n_classes, seed, "cpu")
+    group = torch.repeat_interleave(torch.arange(NI), torch.tensor(counts))
+    img = img[:NI].contiguous()
+    return (img.to(device), group) + tuple(t.to(device) for t in (ids, seg, mask, tgt))
+
+
 def distill_batch(B, T=32, hw=224, vocab=28996, D=768, seed=1234, device="cpu", num_vis=5):
     """A batch of the distillation task (pretrain/roco_utils.py:162-199, task 'distillation') and a small seeded teacher
     table: ((img, ids, seg, mask, start, count), table).  table [total, D] fp32 holds the per-token states of the batch's

@@ -30,6 +30,7 @@ torch.distributed (RCCL).
                                       --teacher_weights clinicalbert.pt --teacher_vocab_file clinicalbert_vocab.txt
     python -m mmvqa_amd.train vqa    --run_name r --loss ASLSingleLabel --batch_size 64
     python -m mmvqa_amd.train vqa    --run_name r --smoothing 0.1 --batch_size 64
+    python -m mmvqa_amd.train vqa    --run_name r --group_by_image --batch_size 64     # each image once for its questions
     python -m mmvqa_amd.train eval   --model_dir save/MLM/r.pt --num_classes 1552 --batch_size 16
     python -m mmvqa_amd.train mlm    --data_dir roco-dataset/data --vocab_file vocab.txt --num_workers 4
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --batch_size 32
@@ -49,6 +50,7 @@ import contextlib
 import os
 import sys
 
+import numpy as np
 import torch
 import torch.distributed as dist
 from torch.optim import lr_scheduler
@@ -120,12 +122,14 @@ def common_args(p):
     p.add_argument("--feeder_depth", type=int, default=2, help="device batches prepared ahead of the step")
 
 
-def feeder(args, ctx, dataset, train, aug=None, batch_size=None, views=1, pairs=False, category=False, teacher=False):
+def feeder(args, ctx, dataset, train, aug=None, batch_size=None, views=1, pairs=False, category=False, teacher=False,
+           grouped=False):
     """DeviceFeeder over one split (shuffled and augmented for training, file order and val transforms otherwise)"""
     host = D.HostLoader(dataset, batch_size or args.batch_size, shuffle=train, seed=args.seed, rank=ctx.rank,
                         world=ctx.world, num_workers=args.num_workers, aug=aug if train else None, size=args.image_size,
                         views=views)
-    return D.DeviceFeeder(host, ctx.dev, train=train, depth=args.feeder_depth, pairs=pairs, category=category, teacher=teacher)
+    return D.DeviceFeeder(host, ctx.dev, train=train, depth=args.feeder_depth, pairs=pairs, category=category, teacher=teacher,
+                          grouped=grouped)
 
 
 def tokenizer(args):
@@ -460,18 +464,38 @@ def supcon_step(model, opt, red, world, batch, words=None, teacher_T=None, bert_
     return loss, pred, stats
 
 
-def vqa_step(model, opt, red, world, batch, crit, clip=False, scaler=None):
+def vqa_forward(model, batch, group=None):
+    """logits of a VQA batch; group (--group_by_image): batch[0] holds each image once and group[b] names the image of
+    question b (Model.forward_grouped)"""
+    if group is None:
+        return model(*batch[:4])[0]                     # utils.py:646
+    return model.forward_grouped(batch[0], group, *batch[1:4])[0]
+
+
+def synthetic_vqa_grouped(args, ctx, seed, C, smooth=False):
+    """the synthetic batch of --group_by_image: --batch_size questions, four of each image as in VQA-Med 2019 (the last
+    image takes the rest), in the layout the grouped feeder hands out: (img, ids, seg, mask, target[, category], group)"""
+    B = args.batch_size
+    counts = [4] * (B // 4) + ([B % 4] if B % 4 else [])
+    img, group, ids, seg, mask, tgt = synth.vqa_grouped_batch(len(counts), counts, args.max_position_embeddings, args.image_size,
+                                                              args.emb_vocab, C, seed=seed, device=ctx.dev)
+    cat = (synth.vqa_categories(B, C, seed=seed, device=ctx.dev),) if smooth else ()
+    return (img, ids, seg, mask, tgt) + cat + (group,)
+
+
+def vqa_step(model, opt, red, world, batch, crit, clip=False, scaler=None, group=None):
     """vqamed2019/utils.py:633-673: logits, _, _ = model(...); loss = criterion(logits, target); backward;
     optional clip_grad_norm_(1.0) (:663-664); Adam; pred = softmax(1).argmax(1).
     With a scaler (--mixed_precision) the reference's sequence of utils.py:641-657: autocast
     forward + loss; scaler.scale(loss) is computed and DISCARDED; the backward is unscaled; the clip acts on those
     gradients; scaler.step then unscales them by 1/scale all the same (and skips on a non-finite gradient).
     A 6-tuple batch (--smoothing) ends with the category ids and the loss is criterion(logits, target, category)
-    (utils.py:648-649; also under a scaler, where the reference's call at :644 lacks the argument and raises)."""
-    img, ids, seg, mask, tgt = batch[:5]
+    (utils.py:648-649; also under a scaler, where the reference's call at :644 lacks the argument and raises).
+    group: the step of --group_by_image (vqa_forward); `batch` is then without its last element, the group itself."""
+    tgt = batch[4]
     opt.zero_grad()
     with torch.autocast("cuda", dtype=torch.float16, enabled=scaler is not None):
-        logits, _, _ = model(img, ids, seg, mask)       # utils.py:646
+        logits = vqa_forward(model, batch, group)
         loss = crit(logits, tgt, batch[5]) if len(batch) == 6 else crit(logits, tgt)
     _update(loss, model, opt, red, world, scaler, scaled_backward=False, clip=clip)   # utils.py:651: the scaled loss is not used
     return loss, logits.detach().softmax(1).argmax(1)
@@ -729,14 +753,18 @@ def run_vqa(args):
     args.dataset, args.task = "VQA-Med", "MLM"
     tr_fd = va_fd = None
     smooth = bool(getattr(args, "smoothing", None))
+    # --group_by_image: a batch holds each image once; its last element is the host map `group`
+    grouped = bool(getattr(args, "group_by_image", False))
+    split = (lambda b: (b[:-1], b[-1])) if grouped else (lambda b: (b, None))
     if args.data_dir:                                   # train.py:100-105: the classes are the answers of the tables
         tok = tokenizer(args)
         _cols, tabs, idx2ans = D.vqa_tables(args.data_dir)
         args.num_classes = len(idx2ans)
         crit = vqa_criterion(args, ctx, tabs["train"])
-        tr_ds = D.VqaDataset(tabs["train"], tok, args.max_position_embeddings, categories=crit.cat2idx if smooth else None)
-        tr_fd = feeder(args, ctx, tr_ds, True, D.VQA_AUG, category=smooth)
-        va_fd = feeder(args, ctx, D.VqaDataset(tabs["val"], tok, args.max_position_embeddings), False)
+        DS = D.VqaGroupedDataset if grouped else D.VqaDataset     # grouped: an item is an image with all of its questions
+        tr_ds = DS(tabs["train"], tok, args.max_position_embeddings, categories=crit.cat2idx if smooth else None)
+        tr_fd = feeder(args, ctx, tr_ds, True, D.VQA_AUG, category=smooth, grouped=grouped)
+        va_fd = feeder(args, ctx, DS(tabs["val"], tok, args.max_position_embeddings), False, grouped=grouped)
     else:
         crit = vqa_criterion(args, ctx)
     C = args.num_classes
@@ -746,11 +774,15 @@ def run_vqa(args):
 
     def synthetic_train(epoch):
         for sd in train_seeds(args, ctx, epoch):
+            if grouped:
+                yield synthetic_vqa_grouped(args, ctx, sd, C, smooth)
+                continue
             batch = synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=sd, device=ctx.dev)
             yield batch + (synth.vqa_categories(B, C, seed=sd, device=ctx.dev),) if smooth else batch
 
     def val_value(batch):                               # utils.py:708-715, 673
-        logits, _, _ = model(*batch[:4])
+        batch, group = split(batch)
+        logits = vqa_forward(model, batch, group)
         return float(crit(logits, batch[4])), batch[4].shape[0], int((logits.softmax(1).argmax(1) == batch[4]).sum())
     # (vqamed2019/train.py itself has no recorder / --resume; kept here like the two pre-training loops)
     start, kept = maybe_resume(args, model, opt, sched, "vqa")
@@ -762,11 +794,15 @@ def run_vqa(args):
             crit.train()        # every epoch: the reference leaves the criterion in eval mode after its first validate
         tl, steps = 0.0, 0
         for batch in epoch_batches(tr_fd, epoch, synthetic_train(epoch)):
-            loss, _ = vqa_step(model, opt, red, ctx.world, batch, crit, clip=args.clip, scaler=scaler)
+            batch, group = split(batch)
+            loss, _ = vqa_step(model, opt, red, ctx.world, batch, crit, clip=args.clip, scaler=scaler, group=group)
             tl, steps = tl + float(loss.detach()), steps + 1
         if smooth:
             crit.eval()         # utils.py:693: validation is plain cross entropy
-        synthetic = (synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=sd, device=ctx.dev) for sd in val_seeds(args))
+        if grouped:
+            synthetic = (synthetic_vqa_grouped(args, ctx, sd, C) for sd in val_seeds(args))
+        else:
+            synthetic = (synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=sd, device=ctx.dev) for sd in val_seeds(args))
         vl, acc = validate(ctx, model, epoch_batches(va_fd, epoch, synthetic), val_value, amp=args.mixed_precision)
         sched.step(vl)
         if ctx.rank == 0:
@@ -806,9 +842,18 @@ def run_eval(args):
         crit = LabelSmoothing(args.smoothing)
     else:
         crit = plain_criterion(args)
-    cats = [r[3] for r in rows]
+    # --group_by_image: the loader's order is the images' first appearance with an image's questions together (the batches'
+    # `index`); the metrics take the categories in that order, the files the predictions back in the table's
+    grouped = bool(getattr(args, "group_by_image", False))
+    order = [r for _, idx in D.group_rows_by_image(rows) for r in idx] if grouped else list(range(len(rows)))
+    cats = [rows[r][3] for r in order]
     with torch.autocast("cuda", dtype=torch.float16, enabled=args.mixed_precision):   # utils.py:786-792
-        test_loss, predictions, acc, bleu = evaluate.test(batches, model, crit, cats, idx2ans, category=args.category)
+        test_loss, predictions, acc, bleu = evaluate.test(batches, model, crit, cats, idx2ans, category=args.category,
+                                                          grouped=grouped)
+    if grouped:
+        in_table_order = np.empty_like(predictions)
+        in_table_order[np.asarray(order)] = predictions
+        predictions = in_table_order
     model_name = (args.model_dir or args.run_name).split("/")[-1]               # eval.py:68
     if ctx.rank == 0:
         paths = evaluate.write_test_files(rows, cols, predictions, idx2ans, args.save_dir, model_name)   # eval.py:171-178
@@ -848,9 +893,17 @@ def eval_setup(args):
             tgt = torch.tensor([r[2] for r in rows[lo:lo + n]], dtype=torch.long, device=ctx.dev)
             yield img, ids, seg, mask, tgt
 
+    grouped = bool(getattr(args, "group_by_image", False))
     if args.data_dir:            # file order, every row on every rank; test() keeps the targets, so they leave the slots
-        test_fd = feeder(args, argparse.Namespace(rank=0, world=1, dev=ctx.dev), D.VqaDataset(rows, tok, T), False)
-        batches = ((img, ids, seg, mask, tgt.clone()) for img, ids, seg, mask, tgt in epoch_batches(test_fd, 0, None))
+        one = argparse.Namespace(rank=0, world=1, dev=ctx.dev)
+        if grouped:              # every image once, with all of its questions: the batches end with the host map `group`
+            test_fd = feeder(args, one, D.VqaGroupedDataset(rows, tok, T), False, grouped=True)
+            batches = (b[:4] + (b[4].clone(), b[5]) for b in epoch_batches(test_fd, 0, None))
+        else:
+            test_fd = feeder(args, one, D.VqaDataset(rows, tok, T), False)
+            batches = ((img, ids, seg, mask, tgt.clone()) for img, ids, seg, mask, tgt in epoch_batches(test_fd, 0, None))
+    elif grouped:                # every synthetic row has an image of its own: the identity map, through the grouped step
+        batches = (b + (torch.arange(b[1].shape[0]),) for b in loader())
     else:
         batches = loader()
     return ctx, model, cols, rows, idx2ans, batches
@@ -980,6 +1033,13 @@ def parse_args(argv=None):
         p.add_argument("--resume_dir", type=str, default=None, help="fine-tuned Model state_dict to continue from")
         p.add_argument("--category", type=str, default=None, help="eval: one question category only (eval.py:29)")
         p.add_argument("--test_samples", type=int, default=64, help="eval: size of the synthetic test split")
+        p.add_argument("--group_by_image", action="store_true", default=False,
+                       help="vqa / eval: a batch holds each image once with all of its questions (VQA-Med asks four per "
+                            "image), so the CNN backbone runs once per image, forward and backward; --batch_size keeps "
+                            "counting questions.  Train-mode BatchNorm then sees each image once per step.  Under data "
+                            "parallelism whole batches are dealt to the ranks, so every rank runs as many steps.  Without "
+                            "--data_dir: vqa draws four synthetic questions per image; eval's synthetic table has one "
+                            "image per question, so the grouped step runs there but shares nothing")
         if mode == "gradcam":
             p.add_argument("--target", type=str, default="answer", choices=["answer", "predicted"],
                            help="the class each map explains: the row's answer (grad_cam2.py:141) or the model's prediction")
@@ -989,6 +1049,8 @@ def parse_args(argv=None):
                            help="attribution method (vqamed2019/grad_cam.py:30,65-72); other than gradcam, the index "
                                 "gains a `method` column")
     args = p.parse_args(argv)
+    if mode == "gradcam" and args.group_by_image:
+        p.error("--group_by_image is for vqa and eval: attribution over grouped batches is not built")
     if args.mixed_precision and args.overlap_adam:
         p.error("--overlap_adam cannot be combined with --mixed_precision: the whole gradient must be checked for "
                 "inf / nan before the first parameter update")
