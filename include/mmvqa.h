@@ -578,6 +578,48 @@ int mmvqa_amp_unscale(mmvqa_stream_t s, float* g, long n, const float* inv_scale
  * growth_interval, scale *= growth (unless that overflows fp32), tracker = 0 */
 int mmvqa_amp_update_scale(mmvqa_stream_t s, float* scale, int* growth_tracker, const float* found_inf,
                            double growth_factor, double backoff_factor, int growth_interval);
+/* Per-tensor statistics of a flat fp32 buffer in at most three launches, whatever the number of tensors (the view of a
+ * run that wandb.watch(model, log='all') gives the reference: pretrain/roco_train.py:80, vqamed2019/train.py:157).
+ * One record per segment [offset, offset + numel) of `base`, in floats; what lies between segments is never read.
+ *   counts  n_finite, n_nan, n_posinf, n_neginf; n_zero = finite values equal to +-0
+ *   min/max over the finite values, exact (+inf / -inf when there is none)
+ *   sum, sumsq over the finite values in fp64, each element converted first and squared in fp64 (exact)
+ *   hist    MMVQA_TENSOR_HIST_BINS counts over the finite values between min and max, the position in fp64 with every
+ *           operation rounded on its own:  scale = 64.0 / (double(max) - double(min))
+ *                                          pos   = (double(x) - double(min)) * scale
+ *                                          bin   = min(63, (int)pos)          x == max lands in bin 63
+ *           max == min: every finite value in bin 0.
+ * Results are bit-identical from call to call (no floating-point atomics; the sums are reduced in a fixed order).
+ * flags & MMVQA_TENSOR_STATS_MOMENTS_ONLY: everything but the histogram, whose words are left as they are (two launches).
+ * Table: nseg >= 1 entries, ascending and disjoint; numel == 0 is legal and gives zero counts and sums with min = +inf,
+ * max = -inf.  A segment is cut into chunks of MMVQA_TENSOR_STATS_CHUNK floats, one workgroup each, and chunk0 is the
+ * number of chunks before it (an empty segment counts as one): mmvqa_tensor_stats_workspace checks a host table, fills
+ * chunk0 in every entry and returns the bytes of workspace a call needs (0: the table was refused, see
+ * mmvqa_last_error).  The caller then uploads the table once: segs is the host copy, segs_dev the same bytes in device
+ * memory; out (nseg records) and ws are device memory; n is the length of the buffer at base in floats.  The call
+ * copies nothing and waits for nothing; one call at a time per workspace.
+ * Refused on the host with MMVQA_ERR_ARG before any HIP call: a null pointer, nseg <= 0, a negative offset or numel, a
+ * numel beyond 32 bits, a segment past n, segments that overlap or are unsorted, a chunk0 other than the query's, a
+ * workspace that is too small, unknown flags. */
+#define MMVQA_TENSOR_HIST_BINS 64
+#define MMVQA_TENSOR_STATS_CHUNK 8192
+#define MMVQA_TENSOR_STATS_MOMENTS_ONLY 1
+typedef struct mmvqa_stat_seg {
+  long long offset, numel;    /* in floats from base */
+  long long chunk0;           /* filled by mmvqa_tensor_stats_workspace */
+} mmvqa_stat_seg;
+typedef struct mmvqa_tensor_stat {
+  double sum, sumsq;
+  long long n_finite, n_nan, n_posinf, n_neginf, n_zero;
+  float min, max;
+  unsigned int hist[MMVQA_TENSOR_HIST_BINS];
+} mmvqa_tensor_stat;
+size_t mmvqa_sizeof_stat_seg(void);
+size_t mmvqa_sizeof_tensor_stat(void);
+size_t mmvqa_tensor_stats_workspace(mmvqa_stat_seg* segs, int nseg);
+int mmvqa_tensor_stats(mmvqa_stream_t s, const float* base, long long n, const mmvqa_stat_seg* segs,
+                       const mmvqa_stat_seg* segs_dev, int nseg, mmvqa_tensor_stat* out, void* ws, size_t ws_bytes,
+                       int flags);
 int mmvqa_axpy(mmvqa_stream_t s, float* y, const float* x, float a, long n);
 int mmvqa_colsum(mmvqa_stream_t s, const float* x, int ld, int rows, int cols, float* out);
 int mmvqa_dropout(mmvqa_stream_t s, float* x, long n, float p, uint32_t seed);

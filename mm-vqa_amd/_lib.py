@@ -26,6 +26,8 @@ ADAM_L2, ADAM_DECOUPLED, ADAM_FROZEN = 0, 1, 2   # mmvqa_adam_seg.mode
 ADAM_MAX_SEGS = 4096
 FREEZE_BACKBONE, FREEZE_BN_STATS = 1, 2   # mmvqa_engine_set_frozen
 STAT_SLOTS = 16
+ERR_ARG = -1   # MMVQA_ERR_ARG
+TENSOR_HIST_BINS, TENSOR_STATS_CHUNK, TENSOR_STATS_MOMENTS_ONLY = 64, 8192, 1   # mmvqa_tensor_stats
 
 
 class BnFold(C.Structure):
@@ -128,6 +130,19 @@ class AdamSeg(C.Structure):
     """mirror of mmvqa_adam_seg"""
     _fields_ = [("begin", C.c_longlong), ("end", C.c_longlong), ("lr", C.c_double), ("weight_decay", C.c_double),
                 ("mode", C.c_int), ("reserved", C.c_int)]
+
+
+class StatSeg(C.Structure):
+    """mirror of mmvqa_stat_seg"""
+    _fields_ = [("offset", C.c_longlong), ("numel", C.c_longlong), ("chunk0", C.c_longlong)]
+
+
+class TensorStat(C.Structure):
+    """mirror of mmvqa_tensor_stat"""
+    _fields_ = [("sum", C.c_double), ("sumsq", C.c_double),
+                ("n_finite", C.c_longlong), ("n_nan", C.c_longlong), ("n_posinf", C.c_longlong),
+                ("n_neginf", C.c_longlong), ("n_zero", C.c_longlong),
+                ("min", C.c_float), ("max", C.c_float), ("hist", C.c_uint32 * TENSOR_HIST_BINS)]
 
 
 class BertDesc(C.Structure):
@@ -260,6 +275,10 @@ SIGNATURES = {
     "mmvqa_engine_tune": (_i, [_P, _i]),
     "mmvqa_amp_unscale": (_i, [_P, _P, _l, _P, _P, _i]),
     "mmvqa_amp_update_scale": (_i, [_P, _P, _P, _P, _d, _d, _i]),
+    "mmvqa_sizeof_stat_seg": (_sz, []),
+    "mmvqa_sizeof_tensor_stat": (_sz, []),
+    "mmvqa_tensor_stats_workspace": (_sz, [_P, _i]),
+    "mmvqa_tensor_stats": (_i, [_P, _P, _ll, _P, _P, _i, _P, _P, _sz, _i]),
     "mmvqa_engine_set_precision": (_i, [_P, _i]),
     "mmvqa_engine_set_frozen": (_i, [_P, _i]),
     "mmvqa_engine_profile": (_i, [_P, _i]),
@@ -301,6 +320,10 @@ def lib():
             raise MMVQAError(f"ABI mismatch: sizeof(mmvqa_{nm}_desc) = {got} in the library, {C.sizeof(st)} in Python")
     if L.mmvqa_sizeof_adam_seg() != C.sizeof(AdamSeg):
         raise MMVQAError(f"ABI mismatch: sizeof(mmvqa_adam_seg) = {L.mmvqa_sizeof_adam_seg()} in the library, {C.sizeof(AdamSeg)} in Python")
+    for nm, st in (("stat_seg", StatSeg), ("tensor_stat", TensorStat)):
+        got = getattr(L, f"mmvqa_sizeof_{nm}")()
+        if got != C.sizeof(st):
+            raise MMVQAError(f"ABI mismatch: sizeof(mmvqa_{nm}) = {got} in the library, {C.sizeof(st)} in Python")
     _lib = L
     return L
 

@@ -32,6 +32,7 @@ torch.distributed (RCCL).
     python -m mmvqa_amd.train vqa    --run_name r --smoothing 0.1 --batch_size 64
     python -m mmvqa_amd.train vqa    --run_name r --group_by_image --batch_size 64     # each image once for its questions
     python -m mmvqa_amd.train eval   --model_dir save/MLM/r.pt --num_classes 1552 --batch_size 16
+    python -m mmvqa_amd.train mlm    --watch all --watch_freq 100     # per-tensor statistics -> save/watch_mlm.jsonl
     python -m mmvqa_amd.train mlm    --data_dir roco-dataset/data --vocab_file vocab.txt --num_workers 4
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --batch_size 32
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --supcon_mask jaccard
@@ -115,6 +116,15 @@ def common_args(p):
     p.add_argument("--freeze_backbone", action="store_true", help="the CNN body gets no gradient; its backward pass is not run")
     p.add_argument("--freeze_bn_stats", action="store_true",
                    help="with --freeze_backbone: its BatchNorms use and keep their running statistics (backbone.eval())")
+    p.add_argument("--watch", type=str, default=None, choices=["gradients", "parameters", "all"],
+                   help="mlm, supcon, distill, vqa: the reference's wandb.watch(model, log=...) (roco_train.py:80, "
+                        "train.py:157): every --watch_freq steps, per-tensor counts of non-finite and zero values, min, "
+                        "max, sum, sum of squares and a 64-bin histogram of the gradients Adam consumes and / or of the "
+                        "parameters before the update, one JSON line per logged step in <save_dir>/watch_<loop>.jsonl.  "
+                        "Under --mixed_precision a skipped step also names the tensors that overflowed.  All tensors "
+                        "in at most three launches per buffer, off the step's critical path.  Not gradients with "
+                        "--overlap_adam")
+    p.add_argument("--watch_freq", type=int, default=1000, help="with --watch: log every N-th step (wandb's log_freq)")
     p.add_argument("--data_dir", type=str, default=None,
                    help="ROCO (mlm, supcon) or VQA-Med 2019 (vqa, eval) tree on disk; without it the batches are synthetic")
     p.add_argument("--vocab_file", type=str, default=None, help="WordPiece vocab.txt (with --data_dir)")
@@ -352,11 +362,14 @@ def maybe_resume(args, model, opt, sched, mode):
 
 
 # ----------------------------------------------------------------------------------------- one training step each
-def _update(loss, model, opt, red, world, scaler=None, scaled_backward=True, clip=False):
+def _update(loss, model, opt, red, world, scaler=None, scaled_backward=True, clip=False, watch=None):
     """What every step does once it has its loss: backward -> gradient all-reduce -> Adam on the gradients over `world`
     (times the clip factor of clip_grad_norm_(1.0): global 2-norm over the averaged flat gradient buffer).  With a
     scaler: backward of scaler.scale(loss), scaler.step after the all-reduce, scaler.update.  scaled_backward=False is
-    vqa_step's: scale(loss) is still called (it creates the scale tensor update() asserts), the backward is unscaled."""
+    vqa_step's: scale(loss) is still called (it creates the scale tensor update() asserts), the backward is unscaled.
+    watch (--watch, rank 0): on a logged step the statistics of the gradients Adam is about to consume (with a scaler:
+    unscaled here, which scaler.step then does not repeat) and of the parameters before the update are enqueued between
+    the all-reduce and the optimizer step; a step the scaler skips reports which tensors overflowed."""
     scaled = loss if scaler is None else scaler.scale(loss)
     (scaled if scaled_backward else loss).backward()
     red.allreduce()
@@ -364,14 +377,30 @@ def _update(loss, model, opt, red, world, scaler=None, scaled_backward=True, cli
     if clip:
         gn = float(model.flat_grads.norm()) * scale
         scale *= min(1.0, 1.0 / (gn + 1e-6))
+    if watch is not None and watch.begin_step():
+        if scaler is not None and watch.wants_grads:
+            scaler.unscale_(opt)
+        watch.log(scale)
     if scaler is None:
         opt.step(grad_scale=scale, zero_grad=True)
     else:
         scaler.step(opt, grad_scale=scale, zero_grad=True)
+        if watch is not None:
+            watch.set_loss_scale(scaler.get_scale())    # (scaler.step has read the device: this waits for nothing more)
+            if scaler.found_inf():                      # skipped: Adam did not run, the gradients are still there
+                watch.log_skipped(scaler.get_scale())
         scaler.update()
 
 
-def mlm_step(model, opt, red, world, batch, scaler=None):
+def make_watcher(args, ctx, loop, model):
+    """the loop's Watcher (--watch, rank 0 only: after the all-reduce every rank holds the same gradients), or None"""
+    if not getattr(args, "watch", None) or ctx.rank != 0:
+        return None
+    from .watch import Watcher
+    return Watcher(model, args.watch, args.watch_freq, os.path.join(args.save_dir, f"watch_{loop}.jsonl"), loop)
+
+
+def mlm_step(model, opt, red, world, batch, scaler=None, watch=None):
     """pretrain/roco_utils.py:214-247,257-265: zero_grad -> forward -> log_softmax + NLLLoss -> backward ->
     (gradient all-reduce) -> Adam.  Returns (loss, pred[B,T], stats = {loss, #target>0, #correct}).
     With a scaler (--mixed_precision, roco_utils.py:224-245): autocast forward + loss, scaled backward, scaler.step
@@ -380,7 +409,7 @@ def mlm_step(model, opt, red, world, batch, scaler=None):
     opt.zero_grad()
     with torch.autocast("cuda", dtype=torch.float16) if scaler is not None else contextlib.nullcontext():
         loss, pred, stats = mlm_loss(model(img, ids, seg, mask), tgt)
-    _update(loss, model, opt, red, world, scaler)
+    _update(loss, model, opt, red, world, scaler, watch=watch)
     return loss, pred, stats
 
 
@@ -430,7 +459,7 @@ def teacher_bertscore_mask(teacher, rows, layer, baseline, teacher_T=None):
     return bertscore_mask_unit(xa, la, xb, lb, baseline)
 
 
-def supcon_step(model, opt, red, world, batch, words=None, teacher_T=None, bert_score=None):
+def supcon_step(model, opt, red, world, batch, words=None, teacher_T=None, bert_score=None, watch=None):
     """models/SupConLoss/supcon_utils.py:270-294: MLM loss over both views + SupCon(split_feat(feat)) (called without
     a mask => SimCLR, :287); under DDP the views of all ranks are gathered first.  Returns (loss, pred, stats).
     With `words` (--supcon_mask jaccard: the table's WordSets on the device) the batch is the feeder's 6-tuple and the
@@ -460,7 +489,7 @@ def supcon_step(model, opt, red, world, batch, words=None, teacher_T=None, bert_
         build_mask = embedding_mask if isinstance(words, D.CaptionEmbeddings) else jaccard_mask
         pos = build_mask(words, rows, torch.zeros_like(cols), rows, cols)
         loss = loss_mlm + supcon_loss(feat, mask=pos)
-    _update(loss, model, opt, red, world)
+    _update(loss, model, opt, red, world, watch=watch)
     return loss, pred, stats
 
 
@@ -483,7 +512,7 @@ def synthetic_vqa_grouped(args, ctx, seed, C, smooth=False):
     return (img, ids, seg, mask, tgt) + cat + (group,)
 
 
-def vqa_step(model, opt, red, world, batch, crit, clip=False, scaler=None, group=None):
+def vqa_step(model, opt, red, world, batch, crit, clip=False, scaler=None, group=None, watch=None):
     """vqamed2019/utils.py:633-673: logits, _, _ = model(...); loss = criterion(logits, target); backward;
     optional clip_grad_norm_(1.0) (:663-664); Adam; pred = softmax(1).argmax(1).
     With a scaler (--mixed_precision) the reference's sequence of utils.py:641-657: autocast
@@ -497,7 +526,7 @@ def vqa_step(model, opt, red, world, batch, crit, clip=False, scaler=None, group
     with torch.autocast("cuda", dtype=torch.float16, enabled=scaler is not None):
         logits = vqa_forward(model, batch, group)
         loss = crit(logits, tgt, batch[5]) if len(batch) == 6 else crit(logits, tgt)
-    _update(loss, model, opt, red, world, scaler, scaled_backward=False, clip=clip)   # utils.py:651: the scaled loss is not used
+    _update(loss, model, opt, red, world, scaler, scaled_backward=False, clip=clip, watch=watch)   # utils.py:651: the scaled loss is not used
     return loss, logits.detach().softmax(1).argmax(1)
 
 
@@ -516,19 +545,24 @@ def validate(ctx, model, batches, value, amp=False):
     return ctx.mean(vl / max(steps, 1)), 100.0 * nc / max(nm, 1)
 
 
-def pretrain(args, ctx, mode, model, opt, sched, batches, step, val, line, rank_mean=True):
+def pretrain(args, ctx, mode, model, opt, sched, batches, step, val, line, rank_mean=True, watch=None):
     """The epoch loop of mlm, distill and supcon (roco_train.py:155-197, roco_supcon_train.py:168-202).  A mode supplies
     batches(epoch) -> the epoch's train batches, step(batch) -> host numbers (loss, #targets, #correct) of one training
     step, val(epoch) -> (validation loss, accuracy) and the tail of its epoch line, a format string over tl, ta, vl, va.
-    rank_mean=False is synthetic SupCon's line: this rank's loss sum over --steps_per_epoch.  -> best validation loss"""
+    rank_mean=False is synthetic SupCon's line: this rank's loss sum over --steps_per_epoch.  watch: the loop's Watcher
+    (--watch), told the epoch and flushed at the end of each.  -> best validation loss"""
     start, kept = maybe_resume(args, model, opt, sched, mode)
     best = kept.get("best", float("inf"))
     for epoch in range(start, args.epochs):
         model.train()
         tl, nm, nc, steps = 0.0, 0, 0, 0
+        if watch is not None:
+            watch.epoch = epoch
         for batch in batches(epoch):
             s = step(batch)
             tl, nm, nc, steps = tl + s[0], nm + s[1], nc + s[2], steps + 1
+        if watch is not None:
+            watch.flush()
         vl, va = val(epoch)
         sched.step(vl)
         if (epoch + 1) % 5 == 0 and ctx.rank == 0:
@@ -540,6 +574,8 @@ def pretrain(args, ctx, mode, model, opt, sched, batches, step, val, line, rank_
             if vl < best:
                 save_model(args, model)
         best = min(best, vl)
+    if watch is not None:
+        watch.close()
     return best
 
 
@@ -562,10 +598,11 @@ def run_mlm(args):
     model, opt, sched, red = build(args, ctx)
     scaler = GradScaler() if args.mixed_precision else None
     tr_fd, va_fd = roco_feeders(args, ctx) if args.data_dir else (None, None)
+    watch = make_watcher(args, ctx, "mlm", model)
     return pretrain(
-        args, ctx, "mlm", model, opt, sched, line=MLM_LINE,
+        args, ctx, "mlm", model, opt, sched, line=MLM_LINE, watch=watch,
         batches=lambda epoch: epoch_batches(tr_fd, epoch, (synthetic_roco(args, ctx, sd) for sd in train_seeds(args, ctx, epoch))),
-        step=lambda batch: mlm_step(model, opt, red, ctx.world, batch, scaler=scaler)[2].tolist(),   # per-step host sync, as roco_utils.py:267
+        step=lambda batch: mlm_step(model, opt, red, ctx.world, batch, scaler=scaler, watch=watch)[2].tolist(),   # per-step host sync, as roco_utils.py:267
         val=lambda epoch: validate_mlm(args, ctx, model, va_fd, epoch, amp=args.mixed_precision))
 
 
@@ -634,7 +671,7 @@ def distill_targets(batch):
     return batch[4][:, 0].contiguous(), batch[4][:, 1].to(torch.int32)
 
 
-def distill_step(model, opt, red, world, batch, teacher, scaler=None, num_vis=5, teacher_T=None):
+def distill_step(model, opt, red, world, batch, teacher, scaler=None, num_vis=5, teacher_T=None, watch=None):
     """pretrain/roco_utils.py:214-247 with task 'distillation' (:230-231, 237-238): zero_grad -> forward (the model
     returns h) -> nn.MSELoss against the teacher's states -> backward -> (gradient all-reduce) -> Adam.  batch =
     (img, ids, seg, mask, start, count) or (img, ids, seg, mask, [B, 2] of both); teacher = the resident table of
@@ -651,7 +688,7 @@ def distill_step(model, opt, red, world, batch, teacher, scaler=None, num_vis=5,
     opt.zero_grad()
     with torch.autocast("cuda", dtype=torch.float16) if scaler is not None else contextlib.nullcontext():
         loss = distill_loss(model(img, ids, seg, mask), teacher, start, count, num_vis)
-    _update(loss, model, opt, red, world, scaler)
+    _update(loss, model, opt, red, world, scaler, watch=watch)
     return loss
 
 
@@ -680,12 +717,15 @@ def run_distill(args):
         tr_teacher = va_teacher = BertTeacher.random(args.teacher_layers, args.hidden_size, 4 * args.hidden_size, args.emb_vocab,
                                                      max(args.max_position_embeddings, 2), seed=args.seed).to(ctx.dev)
 
+    watch = make_watcher(args, ctx, "distill", model)
+
     def longest(fd, pair):       # the fed batch's longest teacher input, from the feeder's host-side log; synthetic: all of L
         return fd.log[-1]["teacher_T"] if fd is not None else pair[0][4].shape[1] - 1
 
     def step(pair):                                               # per-step host sync, as roco_utils.py:267
         tT = longest(tr_fd, pair) if isinstance(pair[1], BertTeacher) else None
-        return float(distill_step(model, opt, red, ctx.world, *pair, scaler=scaler, num_vis=args.num_vis, teacher_T=tT).detach()), 0, 0
+        return float(distill_step(model, opt, red, ctx.world, *pair, scaler=scaler, num_vis=args.num_vis, teacher_T=tT,
+                                  watch=watch).detach()), 0, 0
 
     def val_value(pair):    # roco_utils.py:292-372 with task 'distillation': no accuracy (total_acc is None)
         if isinstance(pair[1], BertTeacher):
@@ -694,7 +734,7 @@ def run_distill(args):
         return float(distill_loss(model(*pair[0][:4]), pair[1], *distill_targets(pair[0]), args.num_vis)), 0, 0
 
     return pretrain(
-        args, ctx, "distill", model, opt, sched, step=step, line="Train loss: {tl:.4f}, Val loss: {vl:.4f}",   # roco_train.py:190
+        args, ctx, "distill", model, opt, sched, step=step, watch=watch, line="Train loss: {tl:.4f}, Val loss: {vl:.4f}",   # roco_train.py:190
         batches=lambda epoch: distill_batches(args, ctx, tr_fd, tr_teacher, epoch, train_seeds(args, ctx, epoch)),
         val=lambda epoch: validate(ctx, model, distill_batches(args, ctx, va_fd, va_teacher, epoch, val_seeds(args, ctx.rank)),
                                    val_value, amp=args.mixed_precision))
@@ -712,6 +752,7 @@ def run_supcon(args):
     tr_fd, va_fd, words = roco_supcon_feeders(args, ctx, n) if args.data_dir else (None, None, None)
     bert_score = ((args.bert_score_layer, args.bert_score_baseline)
                   if getattr(args, "supcon_mask", "none") == "bert_score" else None)
+    watch = make_watcher(args, ctx, "supcon", model)
 
     def synthetic(epoch):
         for sd in train_seeds(args, ctx, epoch):
@@ -720,12 +761,13 @@ def run_supcon(args):
 
     def step(batch):
         tT = tr_fd.log[-1]["teacher_T"] if isinstance(words, BertTeacher) else None   # the feeder's host-side longest length
-        loss, _, stats = supcon_step(model, opt, red, ctx.world, batch, words=words, teacher_T=tT, bert_score=bert_score)
+        loss, _, stats = supcon_step(model, opt, red, ctx.world, batch, words=words, teacher_T=tT, bert_score=bert_score,
+                                     watch=watch)
         # fed: the MLM accuracy train_one_epoch returns (supcon_utils.py:296-318); synthetic: `stats` stays on the device
         return (float(loss.detach()), *(stats.tolist()[1:] if tr_fd is not None else (0, 0)))
 
     return pretrain(
-        args, ctx, "supcon", model, opt, sched, rank_mean=tr_fd is not None,
+        args, ctx, "supcon", model, opt, sched, rank_mean=tr_fd is not None, watch=watch,
         batches=lambda epoch: epoch_batches(tr_fd, epoch, synthetic(epoch)), step=step,
         val=lambda epoch: validate_mlm(args, ctx, model, va_fd, epoch),
         line=MLM_LINE if tr_fd is not None else "Train loss: {tl:.4f}, Val loss: {vl:.4f}, Val acc: {va:.4f}")   # roco_supcon_train.py:193
@@ -770,6 +812,7 @@ def run_vqa(args):
     C = args.num_classes
     model, opt, sched, red = build(args, ctx, n_classes=C)
     scaler = GradScaler() if args.mixed_precision else None
+    watch = make_watcher(args, ctx, "vqa", model)
     T, B = args.max_position_embeddings, args.batch_size
 
     def synthetic_train(epoch):
@@ -793,10 +836,15 @@ def run_vqa(args):
         if smooth:
             crit.train()        # every epoch: the reference leaves the criterion in eval mode after its first validate
         tl, steps = 0.0, 0
+        if watch is not None:
+            watch.epoch = epoch
         for batch in epoch_batches(tr_fd, epoch, synthetic_train(epoch)):
             batch, group = split(batch)
-            loss, _ = vqa_step(model, opt, red, ctx.world, batch, crit, clip=args.clip, scaler=scaler, group=group)
+            loss, _ = vqa_step(model, opt, red, ctx.world, batch, crit, clip=args.clip, scaler=scaler, group=group,
+                               watch=watch)
             tl, steps = tl + float(loss.detach()), steps + 1
+        if watch is not None:
+            watch.flush()
         if smooth:
             crit.eval()         # utils.py:693: validation is plain cross entropy
         if grouped:
@@ -828,6 +876,8 @@ def run_vqa(args):
             if ctx.rank == 0:
                 print("Counter expired, finishing.")
             break
+    if watch is not None:
+        watch.close()
     return best_loss
 
 
@@ -1054,6 +1104,11 @@ def parse_args(argv=None):
     if args.mixed_precision and args.overlap_adam:
         p.error("--overlap_adam cannot be combined with --mixed_precision: the whole gradient must be checked for "
                 "inf / nan before the first parameter update")
+    if args.watch in ("gradients", "all") and args.overlap_adam:
+        p.error(f"--watch {args.watch} cannot be combined with --overlap_adam: gradient ranges are consumed and zeroed "
+                "during backward, before the whole gradient can be looked at")
+    if args.watch_freq < 1:
+        p.error(f"--watch_freq {args.watch_freq} must be at least 1")
     try:
         check_optimizer_args(args)
     except ValueError as ex:
