@@ -571,6 +571,21 @@ size_t mmvqa_sizeof_adam_seg(void);
 int mmvqa_adam_groups(mmvqa_stream_t s, float* p, float* g, float* m, float* v, long lo, long n,
                       const mmvqa_adam_seg* segs, const mmvqa_adam_seg* segs_dev, int nseg, double b1, double b2,
                       double eps, int step, float gscale, int zero_grad);
+/* The two updates above with an exponential moving average of the parameters kept in the same pass: after an element's
+ * update, ema = fmaf(p_new - ema, omd, ema) with omd = (float)(1.0 - ema_decay), every rounding the same in whichever
+ * loop or ranged launch reaches the element.  p, g, m, v come out with the bits of the plain form.  ema is a flat
+ * buffer like the others (the groups form: its base, indexed like p).  In a MMVQA_ADAM_FROZEN segment ema is neither
+ * read nor written.  Checked as the plain forms are; refused in addition with MMVQA_ERR_ARG before any HIP call: a null
+ * ema, an ema_decay outside [0, 1) or NaN, an ema range of the launch ([ema, ema + n), the groups form
+ * [ema + lo, ema + lo + n)) that overlaps one of the other four buffers. */
+int mmvqa_adam_ema(mmvqa_stream_t s, float* p, float* g, float* m, float* v, float* ema, long n, double lr, double b1,
+                   double b2, double eps, int step, float gscale, int zero_grad, double ema_decay);
+int mmvqa_adam_groups_ema(mmvqa_stream_t s, float* p, float* g, float* m, float* v, float* ema, long lo, long n,
+                          const mmvqa_adam_seg* segs, const mmvqa_adam_seg* segs_dev, int nseg, double b1, double b2,
+                          double eps, int step, float gscale, int zero_grad, double ema_decay);
+/* exchange the contents of a[0..n) and b[0..n) in one launch, without a temporary buffer (16-byte accesses: n a
+ * multiple of 4, both pointers aligned to 16 bytes, the buffers disjoint; anything else is MMVQA_ERR_ARG) */
+int mmvqa_swap(mmvqa_stream_t s, float* a, float* b, long n);
 /* loss scaling (torch.amp.GradScaler semantics): found_inf[0] = 1 if any of g[0..n) is inf / nan (left as it is
  * otherwise); with multiply != 0 also g *= inv_scale[0] in place.  Device pointers. */
 int mmvqa_amp_unscale(mmvqa_stream_t s, float* g, long n, const float* inv_scale, float* found_inf, int multiply);

@@ -219,6 +219,9 @@ SIGNATURES = {
     "mmvqa_adam": (_i, [_P, _P, _P, _P, _P, _l, _d, _d, _d, _d, _i, _f, _i]),
     "mmvqa_sizeof_adam_seg": (_sz, []),
     "mmvqa_adam_groups": (_i, [_P, _P, _P, _P, _P, _l, _l, _P, _P, _i, _d, _d, _d, _i, _f, _i]),
+    "mmvqa_adam_ema": (_i, [_P, _P, _P, _P, _P, _P, _l, _d, _d, _d, _d, _i, _f, _i, _d]),
+    "mmvqa_adam_groups_ema": (_i, [_P, _P, _P, _P, _P, _P, _l, _l, _P, _P, _i, _d, _d, _d, _i, _f, _i, _d]),
+    "mmvqa_swap": (_i, [_P, _P, _P, _l]),
     "mmvqa_axpy": (_i, [_P, _P, _P, _f, _l]),
     "mmvqa_colsum": (_i, [_P, _P, _i, _i, _i, _P]),
     "mmvqa_dropout": (_i, [_P, _P, _l, _f, _u32]),

@@ -760,10 +760,14 @@ __global__ void l2norm_bwd_kernel(const float* __restrict__ dy, const float* __r
 }
 
 // =========================================================================== Adam (torch defaults; roco_train.py:90)
-template <int U>
+// EMA (mmvqa_adam_ema): the same pass also keeps an exponential moving average `ema` of the parameters, 40 bytes per
+// parameter instead of 32; everything it adds sits behind `if constexpr (EMA)`, so adam_kernel<U, false> is the kernel
+// without it.
+template <int U, bool EMA>
 __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                             float* __restrict__ v, long n4, float step_size, float b1, float omb1, float b2,
-                            float omb2, float eps, float bc2_sqrt, float gscale, int zero_grad) {
+                            float omb2, float eps, float bc2_sqrt, float gscale, int zero_grad,
+                            float* __restrict__ ema, float omd) {
   // 32 bytes of HBM traffic per parameter and nothing else: two float4 of each array in flight per thread
   // (one per iteration left the pass at 2.4 TB/s), m and v streamed past the caches (they are not touched
   // again before the next optimizer step; the parameters are: the forward re-reads them)
@@ -784,23 +788,37 @@ __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float*
     }
   };
   (void)inv_bc2;
+  // the average of the updated parameter, ema.lerp_(p_new, 1 - decay) with omd = float(1 - decay): the same two roundings
+  // in the unrolled loop, in the tail loop and in a ranged launch, for the reason given above `upd`.  Like m and v the
+  // average is not read again before the next optimizer step, so it is streamed past the caches as they are.
+  auto avg = [&](f32x4& ev, const f32x4& pv) __attribute__((always_inline)) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ev[e] = fmaf(pv[e] - ev[e], omd, ev[e]);
+  };
   f32x4* P4 = reinterpret_cast<f32x4*>(p); f32x4* G4 = reinterpret_cast<f32x4*>(g);
   f32x4* M4 = reinterpret_cast<f32x4*>(m); f32x4* V4 = reinterpret_cast<f32x4*>(v);
+  f32x4* E4 = reinterpret_cast<f32x4*>(ema);
   const f32x4 zero = {0, 0, 0, 0};
   long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i + (U - 1) * stride < n4; i += U * stride) {
-    f32x4 pv[U], gv[U], mv[U], vv[U];
+    f32x4 pv[U], gv[U], mv[U], vv[U], ev[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long j = i + u * stride;
       pv[u] = P4[j]; gv[u] = G4[j]; mv[u] = __builtin_nontemporal_load(M4 + j); vv[u] = __builtin_nontemporal_load(V4 + j);
+      if constexpr (EMA) ev[u] = __builtin_nontemporal_load(E4 + j);
     }
 #pragma unroll
-    for (int u = 0; u < U; ++u) upd(pv[u], gv[u], mv[u], vv[u]);
+    for (int u = 0; u < U; ++u) {
+      upd(pv[u], gv[u], mv[u], vv[u]);
+      if constexpr (EMA) avg(ev[u], pv[u]);
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long j = i + u * stride;
       P4[j] = pv[u]; __builtin_nontemporal_store(mv[u], M4 + j); __builtin_nontemporal_store(vv[u], V4 + j);
+      if constexpr (EMA) __builtin_nontemporal_store(ev[u], E4 + j);
       if (zero_grad) G4[j] = zero;
     }
   }
@@ -808,6 +826,11 @@ __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float*
     f32x4 p0 = P4[i], g0 = G4[i], m0 = M4[i], v0 = V4[i];
     upd(p0, g0, m0, v0);
     P4[i] = p0; M4[i] = m0; V4[i] = v0;
+    if constexpr (EMA) {
+      f32x4 e0 = E4[i];
+      avg(e0, p0);
+      E4[i] = e0;
+    }
     if (zero_grad) G4[i] = zero;
   }
 }
@@ -821,6 +844,8 @@ __global__ void adam_kernel(float* __restrict__ p, float* __restrict__ g, float*
 // is every wave but the few that straddle a boundary, that is the whole lookup.  A straddling wave walks forward from
 // there lane by lane.  The per-segment factors are derived where mmvqa_adam derives them, in double from the launch
 // arguments (step_size = float(lr / bc1), decay = float(1 - lr wd)), and kept while the thread stays in one segment.
+// EMA (mmvqa_adam_groups_ema): as in adam_kernel, behind `if constexpr`; in a MMVQA_ADAM_FROZEN segment the average is
+// neither read nor written, like p, m and v.
 struct AdamSegF { float step_size, wd, decay; int mode; };
 __device__ __forceinline__ AdamSegF adam_seg_factors(const mmvqa_adam_seg* __restrict__ segs, int s, double bc1) {
   const double lr = segs[s].lr, wd = segs[s].weight_decay;
@@ -831,10 +856,11 @@ __device__ __forceinline__ AdamSegF adam_seg_factors(const mmvqa_adam_seg* __res
   f.decay = f.mode == MMVQA_ADAM_DECOUPLED ? (float)(1.0 - lr * wd) : 1.f;
   return f;
 }
+template <bool EMA>
 __global__ void adam_groups_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                    float* __restrict__ v, long lo4, long n4, const mmvqa_adam_seg* __restrict__ segs,
                                    int nseg, double bc1, float b1, float omb1, float b2, float omb2, float eps,
-                                   float bc2_sqrt, float gscale, int zero_grad) {
+                                   float bc2_sqrt, float gscale, int zero_grad, float* __restrict__ ema, float omd) {
   constexpr int U = 2;
   const long stride = (long)gridDim.x * blockDim.x;
   const int lane = threadIdx.x & 63;
@@ -853,6 +879,11 @@ __global__ void adam_groups_kernel(float* __restrict__ p, float* __restrict__ g,
       const float denom = sqrtf(vv[e]) / bc2_sqrt + eps;
       pv[e] = fmaf(-f.step_size, mv[e] / denom, pp);
     }
+  };
+  auto avg = [&](f32x4& ev, const f32x4& pv) __attribute__((always_inline)) {   // adam_kernel's `avg`
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) ev[e] = fmaf(pv[e] - ev[e], omd, ev[e]);
   };
   // segment of float4 j (absolute); cs / cf: the segment this slot of the thread was in last and its factors
   auto lookup = [&](long j, int& cs, AdamSegF& cf) __attribute__((always_inline)) {
@@ -875,6 +906,7 @@ __global__ void adam_groups_kernel(float* __restrict__ p, float* __restrict__ g,
   };
   f32x4* P4 = reinterpret_cast<f32x4*>(p); f32x4* G4 = reinterpret_cast<f32x4*>(g);
   f32x4* M4 = reinterpret_cast<f32x4*>(m); f32x4* V4 = reinterpret_cast<f32x4*>(v);
+  f32x4* E4 = reinterpret_cast<f32x4*>(ema);
   const f32x4 zero = {0, 0, 0, 0};
   const long end4 = lo4 + n4;
   int cs[U];
@@ -883,23 +915,28 @@ __global__ void adam_groups_kernel(float* __restrict__ p, float* __restrict__ g,
   for (int u = 0; u < U; ++u) cs[u] = -1;
   long i = lo4 + (long)blockIdx.x * blockDim.x + threadIdx.x;
   for (; i + (U - 1) * stride < end4; i += U * stride) {
-    f32x4 pv[U], gv[U], mv[U], vv[U];
+    f32x4 pv[U], gv[U], mv[U], vv[U], ev[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long j = i + u * stride;
       lookup(j, cs[u], cf[u]);
       if (cf[u].mode != MMVQA_ADAM_FROZEN) {
         pv[u] = P4[j]; gv[u] = G4[j]; mv[u] = __builtin_nontemporal_load(M4 + j); vv[u] = __builtin_nontemporal_load(V4 + j);
+        if constexpr (EMA) ev[u] = __builtin_nontemporal_load(E4 + j);
       }
     }
 #pragma unroll
     for (int u = 0; u < U; ++u)
-      if (cf[u].mode != MMVQA_ADAM_FROZEN) upd(cf[u], pv[u], gv[u], mv[u], vv[u]);
+      if (cf[u].mode != MMVQA_ADAM_FROZEN) {
+        upd(cf[u], pv[u], gv[u], mv[u], vv[u]);
+        if constexpr (EMA) avg(ev[u], pv[u]);
+      }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long j = i + u * stride;
       if (cf[u].mode != MMVQA_ADAM_FROZEN) {
         P4[j] = pv[u]; __builtin_nontemporal_store(mv[u], M4 + j); __builtin_nontemporal_store(vv[u], V4 + j);
+        if constexpr (EMA) __builtin_nontemporal_store(ev[u], E4 + j);
       }
       if (zero_grad) G4[j] = zero;
     }
@@ -910,8 +947,23 @@ __global__ void adam_groups_kernel(float* __restrict__ p, float* __restrict__ g,
       f32x4 p0 = P4[i], g0 = G4[i], m0 = M4[i], v0 = V4[i];
       upd(cf[0], p0, g0, m0, v0);
       P4[i] = p0; M4[i] = m0; V4[i] = v0;
+      if constexpr (EMA) {
+        f32x4 e0 = E4[i];
+        avg(e0, p0);
+        E4[i] = e0;
+      }
     }
     if (zero_grad) G4[i] = zero;
+  }
+}
+
+// exchange two flat buffers in place (mmvqa_swap): a float4 of each per thread and iteration, both held in registers
+// between the loads and the stores, so no temporary buffer
+__global__ void swap_kernel(f32x4* __restrict__ a, f32x4* __restrict__ b, long n4) {
+  const long stride = (long)gridDim.x * blockDim.x;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
+    const f32x4 x = a[i], y = b[i];
+    a[i] = y; b[i] = x;
   }
 }
 
@@ -1232,10 +1284,31 @@ extern "C" int mmvqa_l2norm_bwd(mmvqa_stream_t s, const float* dy, const float* 
   return MMVQA_OK;
 }
 
-extern "C" int mmvqa_adam(mmvqa_stream_t s, float* p, float* g, float* m, float* v, long n, double lr, double b1,
-                          double b2, double eps, int step, float gscale, int zero_grad) {
+// what the two averaging entry points refuse beyond their plain forms, before any HIP call: a null average, a decay
+// outside [0, 1) (NaN included), an average [ema + lo, ema + lo + n) that overlaps [x, x + extent) of p, g, m or v
+static int adam_ema_check(const char* who, const float* p, const float* g, const float* m, const float* v,
+                          const float* ema, long lo, long n, long long extent, double ema_decay) {
+  if (!ema) return mmvqa_set_error(MMVQA_ERR_ARG, "%s: ema is null", who);
+  if (!(ema_decay >= 0.0 && ema_decay < 1.0))
+    return mmvqa_set_error(MMVQA_ERR_ARG, "%s: ema_decay=%g is outside [0, 1)", who, ema_decay);
+  const uintptr_t e0 = (uintptr_t)ema + 4 * (uintptr_t)lo, e1 = e0 + 4 * (uintptr_t)n;
+  const float* other[4] = {p, g, m, v};
+  const char* name = "pgmv";
+  for (int i = 0; i < 4; ++i) {
+    const uintptr_t x0 = (uintptr_t)other[i], x1 = x0 + 4 * (uintptr_t)extent;
+    if (e0 < x1 && x0 < e1) return mmvqa_set_error(MMVQA_ERR_ARG, "%s: ema overlaps %c", who, name[i]);
+  }
+  return MMVQA_OK;
+}
+
+// mmvqa_adam and mmvqa_adam_ema: one set of checks and one launch site
+template <bool EMA>
+static int adam_launch(mmvqa_stream_t s, float* p, float* g, float* m, float* v, float* ema, long n, double lr, double b1,
+                       double b2, double eps, int step, float gscale, int zero_grad, double ema_decay) {
   hipStream_t st = (hipStream_t)s;
   if (n % 4 != 0) return mmvqa_set_error(MMVQA_ERR_ARG, "adam: n must be a multiple of 4");
+  if (EMA)
+    if (int rc = adam_ema_check("adam_ema", p, g, m, v, ema, 0, n, n, ema_decay)) return rc;
   // bias corrections and (1 - beta) in double, as torch.optim.Adam computes them from Python floats
   const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
   // MMVQA_ADAM_WGS: cap on the workgroups of one launch (A/B: a ranged launch beside the backward pass takes wave slots
@@ -1245,20 +1318,35 @@ extern "C" int mmvqa_adam(mmvqa_stream_t s, float* p, float* g, float* m, float*
   // MMVQA_ADAM_UNROLL: float4 of each array in flight per thread (A/B; default 2: one per iteration left the pass at 2.4 TB/s)
   static const int unroll = getenv("MMVQA_ADAM_UNROLL") ? atoi(getenv("MMVQA_ADAM_UNROLL")) : 2;
 #define ADAM_GO(U_)                                                                                                       \
-  hipLaunchKernelGGL(adam_kernel<U_>, dim3(grid_for(n / 4, 256, cap > 0 ? cap : 16384)), dim3(256), 0, st, p, g, m, v, n / 4, \
-                     (float)(lr / bc1), (float)b1, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps,            \
-                     (float)sqrt(bc2), gscale, zero_grad)
-  if (unroll >= 4) ADAM_GO(4); else if (unroll == 3) ADAM_GO(3); else if (unroll == 1) ADAM_GO(1); else ADAM_GO(2);
+  hipLaunchKernelGGL((adam_kernel<U_, EMA>), dim3(grid_for(n / 4, 256, cap > 0 ? cap : 16384)), dim3(256), 0, st, p, g, m, v, \
+                     n / 4, (float)(lr / bc1), (float)b1, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)eps,     \
+                     (float)sqrt(bc2), gscale, zero_grad, ema, (float)(1.0 - ema_decay))
+  // (the averaging form is built for 1 and 2 only: with five arrays in flight 3 and 4 spill scalar registers)
+  if constexpr (EMA) {
+    if (unroll == 1) ADAM_GO(1); else ADAM_GO(2);
+  } else {
+    if (unroll >= 4) ADAM_GO(4); else if (unroll == 3) ADAM_GO(3); else if (unroll == 1) ADAM_GO(1); else ADAM_GO(2);
+  }
 #undef ADAM_GO
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }
+extern "C" int mmvqa_adam(mmvqa_stream_t s, float* p, float* g, float* m, float* v, long n, double lr, double b1,
+                          double b2, double eps, int step, float gscale, int zero_grad) {
+  return adam_launch<false>(s, p, g, m, v, nullptr, n, lr, b1, b2, eps, step, gscale, zero_grad, 0.0);
+}
+extern "C" int mmvqa_adam_ema(mmvqa_stream_t s, float* p, float* g, float* m, float* v, float* ema, long n, double lr,
+                              double b1, double b2, double eps, int step, float gscale, int zero_grad, double ema_decay) {
+  return adam_launch<true>(s, p, g, m, v, ema, n, lr, b1, b2, eps, step, gscale, zero_grad, ema_decay);
+}
 
 extern "C" size_t mmvqa_sizeof_adam_seg(void) { return sizeof(mmvqa_adam_seg); }
 
-extern "C" int mmvqa_adam_groups(mmvqa_stream_t s, float* p, float* g, float* m, float* v, long lo, long n,
-                                 const mmvqa_adam_seg* segs, const mmvqa_adam_seg* segs_dev, int nseg, double b1,
-                                 double b2, double eps, int step, float gscale, int zero_grad) {
+// mmvqa_adam_groups and mmvqa_adam_groups_ema: one set of checks and one launch site
+template <bool EMA>
+static int adam_groups_launch(mmvqa_stream_t s, float* p, float* g, float* m, float* v, float* ema, long lo, long n,
+                              const mmvqa_adam_seg* segs, const mmvqa_adam_seg* segs_dev, int nseg, double b1, double b2,
+                              double eps, int step, float gscale, int zero_grad, double ema_decay) {
   hipStream_t st = (hipStream_t)s;
   // everything the kernel's addressing relies on is checked here, on the host copy of the table, before any HIP call
   if (!p || !g || !m || !v || !segs || !segs_dev) return mmvqa_set_error(MMVQA_ERR_ARG, "adam_groups: null pointer");
@@ -1280,13 +1368,41 @@ extern "C" int mmvqa_adam_groups(mmvqa_stream_t s, float* p, float* g, float* m,
   }
   if ((long long)lo + n > pos)
     return mmvqa_set_error(MMVQA_ERR_ARG, "adam_groups: [%ld, %ld) reaches beyond the table's %lld floats", lo, lo + n, pos);
+  if (EMA)   // the average's range of this launch against the whole of the other four buffers (the table's extent)
+    if (int rc = adam_ema_check("adam_groups_ema", p, g, m, v, ema, lo, n, pos, ema_decay)) return rc;
   if (n == 0) return MMVQA_OK;
   const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);   // as mmvqa_adam
   const char* cap_s = getenv("MMVQA_ADAM_WGS");
   const int cap = cap_s ? atoi(cap_s) : 16384;
-  hipLaunchKernelGGL(adam_groups_kernel, dim3(grid_for(n / 4, 256, cap > 0 ? cap : 16384)), dim3(256), 0, st, p, g, m, v,
+  hipLaunchKernelGGL(adam_groups_kernel<EMA>, dim3(grid_for(n / 4, 256, cap > 0 ? cap : 16384)), dim3(256), 0, st, p, g, m, v,
                      lo / 4, n / 4, segs_dev, nseg, bc1, (float)b1, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2),
-                     (float)eps, (float)sqrt(bc2), gscale, zero_grad);
+                     (float)eps, (float)sqrt(bc2), gscale, zero_grad, ema, (float)(1.0 - ema_decay));
+  KERNEL_CHECK_RET();
+  return MMVQA_OK;
+}
+extern "C" int mmvqa_adam_groups(mmvqa_stream_t s, float* p, float* g, float* m, float* v, long lo, long n,
+                                 const mmvqa_adam_seg* segs, const mmvqa_adam_seg* segs_dev, int nseg, double b1,
+                                 double b2, double eps, int step, float gscale, int zero_grad) {
+  return adam_groups_launch<false>(s, p, g, m, v, nullptr, lo, n, segs, segs_dev, nseg, b1, b2, eps, step, gscale, zero_grad, 0.0);
+}
+extern "C" int mmvqa_adam_groups_ema(mmvqa_stream_t s, float* p, float* g, float* m, float* v, float* ema, long lo, long n,
+                                     const mmvqa_adam_seg* segs, const mmvqa_adam_seg* segs_dev, int nseg, double b1,
+                                     double b2, double eps, int step, float gscale, int zero_grad, double ema_decay) {
+  return adam_groups_launch<true>(s, p, g, m, v, ema, lo, n, segs, segs_dev, nseg, b1, b2, eps, step, gscale, zero_grad, ema_decay);
+}
+
+// exchange a[0..n) and b[0..n) in one launch; refused on the host: a null or misaligned pointer, n negative or no
+// multiple of 4 (16-byte accesses), buffers that overlap
+extern "C" int mmvqa_swap(mmvqa_stream_t s, float* a, float* b, long n) {
+  hipStream_t st = (hipStream_t)s;
+  if (!a || !b) return mmvqa_set_error(MMVQA_ERR_ARG, "swap: null pointer");
+  if (n < 0 || n % 4 != 0) return mmvqa_set_error(MMVQA_ERR_ARG, "swap: n=%ld must be a non-negative multiple of 4", n);
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b, bytes = 4 * (uintptr_t)n;
+  if ((a0 | b0) % 16 != 0) return mmvqa_set_error(MMVQA_ERR_ARG, "swap: the buffers must be aligned to 16 bytes");
+  if (a0 < b0 + bytes && b0 < a0 + bytes) return mmvqa_set_error(MMVQA_ERR_ARG, "swap: the buffers overlap");
+  if (n == 0) return MMVQA_OK;
+  hipLaunchKernelGGL(swap_kernel, dim3(grid_for(n / 4, 256, 16384)), dim3(256), 0, st, reinterpret_cast<f32x4*>(a),
+                     reinterpret_cast<f32x4*>(b), n / 4);
   KERNEL_CHECK_RET();
   return MMVQA_OK;
 }

@@ -16,6 +16,7 @@ decay, nothing frozen -- the optimizer calls ``mmvqa_adam`` as before.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import operator
 import re
@@ -68,14 +69,33 @@ def merge_segments(ranges):
     return [tuple(s) for s in out]
 
 
+def ema_decay_at(ema_decay, updates, warmup):
+    """decay of the averaging step after `updates` earlier ones: ema_decay, or with warm-up min(ema_decay, (1 + t) / (10 + t))
+    -- 0.1 at first, so that the average follows the first steps instead of remembering the initial weights, 0.5 after
+    8 updates, and ema_decay from t >= (10 ema_decay - 1) / (1 - ema_decay) on"""
+    return min(ema_decay, (1.0 + updates) / (10.0 + updates)) if warmup else ema_decay
+
+
 class FusedAdam:
-    def __init__(self, model, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, groups=None):
+    def __init__(self, model, lr=2e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=True, groups=None,
+                 ema_decay=None, ema_warmup=False):
         """groups: list of dicts {match: prefix | tuple of prefixes | callable(name), lr?, weight_decay?}; a parameter
         belongs to the first group that matches its name, the rest to the default group (lr, weight_decay), which is
         param_groups[0].  decoupled: weight decay as torch.optim.AdamW applies it (p *= 1 - lr wd), else as
         torch.optim.Adam(weight_decay=) does (g += wd p).  betas and eps are shared: a group that names its own is
         refused.  Parameters with requires_grad=False are skipped (read again at every step): they and their moments
-        keep their values, also when they were frozen after some steps."""
+        keep their values, also when they were frozen after some steps.
+        ema_decay in [0, 1): keep self.ema, a copy of the flat parameter buffer that follows it in every step,
+        ema += (p_new - ema) * (1 - decay), in the launch that updates the parameters; ema_warmup: the decay of
+        ema_decay_at.  A step that amp.GradScaler skips leaves the average and its counter alone.  A frozen tensor's
+        average is not touched: frozen from the start it stays equal to the tensor, frozen later it keeps the average it
+        had at that moment (it does not go on approaching the now constant weights).  Only parameters are averaged:
+        BatchNorm running statistics and num_batches_tracked are buffers, and averaged() evaluates the averaged weights
+        with the live buffers -- torch.optim.swa_utils.AveragedModel(use_buffers=False) without the update_bn pass."""
+        if ema_decay is None and ema_warmup:
+            raise ValueError("FusedAdam: ema_warmup without ema_decay")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:    # (NaN fails the comparison too)
+            raise ValueError(f"FusedAdam: ema_decay={ema_decay} is outside [0, 1)")
         self.model = model
         groups = [dict(g) for g in (groups or [])]
         for g in groups:
@@ -107,6 +127,11 @@ class FusedAdam:
         self._segs = None            # (host ctypes array, device tensor, nseg) or None: the plain mmvqa_adam path
         self._uploaded = None        # event behind the last upload: launches on other streams wait for it
         self._retired = []           # the table before this one: a launch still queued may read it
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema = None if ema_decay is None else model.flat_params.detach().clone()
+        self.ema_updates = 0         # steps the average has taken (skipped steps not counted): the warm-up's t
+        self._averaged = False       # inside averaged(): flat_params holds the average, self.ema the live weights
 
     # ------------------------------------------------------------------ segment table
     def group_spec(self):
@@ -176,19 +201,29 @@ class FusedAdam:
             self.model.set_grad_ready_hook(self._on_ready, with_event=True)
 
     def _adam(self, lo, hi, step, grad_scale, zero_grad, stream_ptr):
+        if self._averaged:
+            raise L.MMVQAError("FusedAdam: an update inside averaged() would train the averaged weights; leave the context first")
         self._plan(step)
         g = self.param_groups[0]
         p = self.model.flat_params
+        # the averaging forms take the step's decay by value: ema_updates moves at the end of step(), so every ranged
+        # launch of one step gets the same one
+        ema = self.ema is not None
+        decay = (ema_decay_at(self.ema_decay, self.ema_updates, self.ema_warmup),) if ema else ()
         if self._segs is None:
-            L.check(L.lib().mmvqa_adam(stream_ptr, L.ptr(p[lo:hi]), L.ptr(self.model.flat_grads[lo:hi]), L.ptr(self.m[lo:hi]),
-                                       L.ptr(self.v[lo:hi]), hi - lo, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
-                                       step, grad_scale, 1 if zero_grad else 0))
+            fn = L.lib().mmvqa_adam_ema if ema else L.lib().mmvqa_adam
+            avg = (L.ptr(self.ema[lo:hi]),) if ema else ()
+            L.check(fn(stream_ptr, L.ptr(p[lo:hi]), L.ptr(self.model.flat_grads[lo:hi]), L.ptr(self.m[lo:hi]),
+                       L.ptr(self.v[lo:hi]), *avg, hi - lo, g["lr"], g["betas"][0], g["betas"][1], g["eps"],
+                       step, grad_scale, 1 if zero_grad else 0, *decay))
             return
         host, dev, nseg = self._segs
         torch.cuda.current_stream().wait_event(self._uploaded)   # (a no-op on the stream that uploaded)
-        L.check(L.lib().mmvqa_adam_groups(stream_ptr, L.ptr(p), L.ptr(self.model.flat_grads), L.ptr(self.m), L.ptr(self.v),
-                                          lo, hi - lo, C.cast(host, C.c_void_p), L.ptr(dev), nseg, g["betas"][0],
-                                          g["betas"][1], g["eps"], step, grad_scale, 1 if zero_grad else 0))
+        fn = L.lib().mmvqa_adam_groups_ema if ema else L.lib().mmvqa_adam_groups
+        avg = (L.ptr(self.ema),) if ema else ()
+        L.check(fn(stream_ptr, L.ptr(p), L.ptr(self.model.flat_grads), L.ptr(self.m), L.ptr(self.v), *avg,
+                   lo, hi - lo, C.cast(host, C.c_void_p), L.ptr(dev), nseg, g["betas"][0],
+                   g["betas"][1], g["eps"], step, grad_scale, 1 if zero_grad else 0, *decay))
 
     def _early(self, lo, hi, ready=None, work=None, stream=None):
         if hi <= lo or any(a < hi and lo < b for a, b in self._done):
@@ -218,10 +253,13 @@ class FusedAdam:
         (1/world_size under DDP) and zeroed in the same pass when zero_grad is set."""
         if self.model.flat_params.data_ptr() != self._for:
             raise L.MMVQAError("FusedAdam: the model was re-laid out (.to()/re-head) after the optimizer was built")
+        if self._averaged:
+            raise L.MMVQAError("FusedAdam.step inside averaged(): the model holds the averaged weights; leave the context first")
         self.step_count += 1
         n = self.model.flat_params.numel()
         if not self._done:
             self._adam(0, n, self.step_count, grad_scale, zero_grad, L.stream_ptr())
+            self.ema_updates += 1 if self.ema is not None else 0
             return
         if not zero_grad or abs(grad_scale - self._grad_scale) > 1e-12 * abs(self._grad_scale):
             raise L.MMVQAError("FusedAdam.step: ranges were already updated during backward with zero_grad=True and "
@@ -235,9 +273,44 @@ class FusedAdam:
             self._adam(pos, n, self.step_count, grad_scale, True, L.stream_ptr())
         torch.cuda.current_stream().wait_stream(self._stream)   # the next forward reads the updated parameters
         self._done = []
+        self.ema_updates += 1 if self.ema is not None else 0
+
+    # ------------------------------------------------------------------ the averaged weights
+    def _swap(self):
+        p = self.model.flat_params
+        L.check(L.lib().mmvqa_swap(L.stream_ptr(), L.ptr(p), L.ptr(self.ema), p.numel()))
+
+    def averaged(self):
+        """with opt.averaged(): the model computes with the averaged weights.  The contents of model.flat_params and
+        self.ema are exchanged by one launch on the current stream (the engine stays bound to the same pointers, every
+        parameter view stays valid) and exchanged back on exit, also on an exception; step() inside raises.  Buffers are
+        not averaged: the averaged weights run with the live BatchNorm statistics (see __init__).  Without ema_decay
+        this is a null context."""
+        if self.ema is None:
+            return contextlib.nullcontext()
+        return self._averaged_weights()
+
+    @contextlib.contextmanager
+    def _averaged_weights(self):
+        if self._averaged:
+            raise L.MMVQAError("FusedAdam.averaged() is already active")
+        if self._done:
+            raise L.MMVQAError("FusedAdam.averaged() between a backward pass whose ranges were already updated and its step()")
+        self._swap()
+        self._averaged = True
+        try:
+            yield self
+        finally:
+            self._swap()
+            self._averaged = False
 
     def state_dict(self):
-        return dict(m=self.m, v=self.v, step=self.step_count, param_groups=self.param_groups, group_spec=self.group_spec())
+        sd = dict(m=self.m, v=self.v, step=self.step_count, param_groups=self.param_groups, group_spec=self.group_spec())
+        if self.ema is not None:
+            if self._averaged:
+                raise L.MMVQAError("FusedAdam.state_dict inside averaged(): self.ema holds the live weights there")
+            sd.update(ema=self.ema, ema_decay=self.ema_decay, ema_warmup=self.ema_warmup, ema_updates=self.ema_updates)
+        return sd
 
     def load_state_dict(self, sd):
         mine = self.group_spec()
@@ -255,3 +328,13 @@ class FusedAdam:
         for mine_g, theirs_g in zip(self.param_groups, sd["param_groups"]):
             mine_g.update(theirs_g)
         self._plan_step = None
+        if self.ema is None:         # a plain optimizer ignores a checkpoint's average
+            return
+        if "ema" in sd:
+            self.ema.copy_(sd["ema"])
+            self.ema_decay, self.ema_warmup = float(sd["ema_decay"]), bool(sd["ema_warmup"])
+            self.ema_updates = int(sd["ema_updates"])
+        else:
+            self.ema.copy_(self.model.flat_params)
+            self.ema_updates = 0
+            print("FusedAdam: the checkpoint holds no weight average; it starts from the current parameters", flush=True)

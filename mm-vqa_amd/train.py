@@ -33,6 +33,7 @@ torch.distributed (RCCL).
     python -m mmvqa_amd.train vqa    --run_name r --group_by_image --batch_size 64     # each image once for its questions
     python -m mmvqa_amd.train eval   --model_dir save/MLM/r.pt --num_classes 1552 --batch_size 16
     python -m mmvqa_amd.train mlm    --watch all --watch_freq 100     # per-tensor statistics -> save/watch_mlm.jsonl
+    python -m mmvqa_amd.train vqa    --ema_decay 0.999 --ema_warmup   # validate and save the averaged weights
     python -m mmvqa_amd.train mlm    --data_dir roco-dataset/data --vocab_file vocab.txt --num_workers 4
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --batch_size 32
     python -m mmvqa_amd.train supcon --data_dir roco-dataset/data --vocab_file vocab.txt --supcon_mask jaccard
@@ -116,6 +117,14 @@ def common_args(p):
     p.add_argument("--freeze_backbone", action="store_true", help="the CNN body gets no gradient; its backward pass is not run")
     p.add_argument("--freeze_bn_stats", action="store_true",
                    help="with --freeze_backbone: its BatchNorms use and keep their running statistics (backbone.eval())")
+    p.add_argument("--ema_decay", type=float, default=None, metavar="D",
+                   help="mlm, supcon, distill, vqa: keep an exponential moving average of the weights, avg += (w - avg)(1 - D) "
+                        "per optimizer step, in the launch that updates them (FusedAdam(ema_decay=)).  Every validation "
+                        "and every saved .pt file then uses the averaged weights with the live BatchNorm "
+                        "statistics, so the scheduler, the best-checkpoint choices and the early stop follow the "
+                        "averaged model; the recorder keeps the live weights and, in the optimizer state, the average")
+    p.add_argument("--ema_warmup", action="store_true", default=False,
+                   help="with --ema_decay: the decay of update t is min(D, (1 + t) / (10 + t))")
     p.add_argument("--watch", type=str, default=None, choices=["gradients", "parameters", "all"],
                    help="mlm, supcon, distill, vqa: the reference's wandb.watch(model, log=...) (roco_train.py:80, "
                         "train.py:157): every --watch_freq steps, per-tensor counts of non-finite and zero values, min, "
@@ -261,6 +270,11 @@ def check_optimizer_args(args):
         raise ValueError("--freeze_backbone with --backbone_lr: a frozen backbone has no learning rate")
     if getattr(args, "weight_decay", 0.0) < 0:
         raise ValueError("--weight_decay must not be negative")
+    ema = getattr(args, "ema_decay", None)
+    if ema is not None and not 0.0 <= ema < 1.0:
+        raise ValueError(f"--ema_decay {ema} is outside [0, 1)")
+    if getattr(args, "ema_warmup", False) and ema is None:
+        raise ValueError("--ema_warmup requires --ema_decay")
 
 
 def optimizer_groups(args):
@@ -278,6 +292,8 @@ def optimizer_groups(args):
         groups.append(dict(match=no_decay, weight_decay=0.0))
     if groups:
         kw["groups"] = groups
+    if getattr(args, "ema_decay", None) is not None:
+        kw.update(ema_decay=args.ema_decay, ema_warmup=bool(getattr(args, "ema_warmup", False)))
     return kw
 
 
@@ -316,6 +332,12 @@ def build(args, ctx, n_classes=None):
     if getattr(args, "overlap_adam", False) and not getattr(args, "clip", False):
         opt.overlap_backward(red, grad_scale=1.0 / ctx.world)
     return model, opt, sched, red
+
+
+def averaged(args, opt):
+    """--ema_decay: the context in which the model computes with, and saves, the averaged weights (FusedAdam.averaged);
+    without the option a null context"""
+    return opt.averaged() if getattr(args, "ema_decay", None) is not None else contextlib.nullcontext()
 
 
 class _SchedShim(torch.optim.Optimizer):
@@ -563,7 +585,8 @@ def pretrain(args, ctx, mode, model, opt, sched, batches, step, val, line, rank_
             tl, nm, nc, steps = tl + s[0], nm + s[1], nc + s[2], steps + 1
         if watch is not None:
             watch.flush()
-        vl, va = val(epoch)
+        with averaged(args, opt):        # --ema_decay: the averaged weights are what is validated
+            vl, va = val(epoch)
         sched.step(vl)
         if (epoch + 1) % 5 == 0 and ctx.rank == 0:
             save_recorder(args, epoch, model, opt, sched, mode, {"best": min(best, vl)})
@@ -572,7 +595,8 @@ def pretrain(args, ctx, mode, model, opt, sched, batches, step, val, line, rank_
             print(f"Epoch {epoch + 1}/{args.epochs} Learning rate: {opt.param_groups[0]['lr']:.7f}, "
                   + line.format(tl=tl, ta=100.0 * nc / max(nm, 1), vl=vl, va=va), flush=True)
             if vl < best:
-                save_model(args, model)
+                with averaged(args, opt):    # ... and saved
+                    save_model(args, model)
         best = min(best, vl)
     if watch is not None:
         watch.close()
@@ -851,16 +875,18 @@ def run_vqa(args):
             synthetic = (synthetic_vqa_grouped(args, ctx, sd, C) for sd in val_seeds(args))
         else:
             synthetic = (synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=sd, device=ctx.dev) for sd in val_seeds(args))
-        vl, acc = validate(ctx, model, epoch_batches(va_fd, epoch, synthetic), val_value, amp=args.mixed_precision)
+        with averaged(args, opt):        # --ema_decay: the averaged weights are what is validated
+            vl, acc = validate(ctx, model, epoch_batches(va_fd, epoch, synthetic), val_value, amp=args.mixed_precision)
         sched.step(vl)
         if ctx.rank == 0:
             print(f"Epoch {epoch + 1}/{args.epochs} lr {opt.param_groups[0]['lr']:.7f} train_loss {tl / max(steps, 1):.4f} "
                   f"val_loss {vl:.4f} val_total_acc {acc:.2f}", flush=True)
-        if ctx.rank == 0:
-            if vl < best_loss:                   # train.py:264-268 "save by val loss"
-                save_model(args, model, "_loss")
-            if acc > best_acc1:                  # train.py:270-276 "save by accuracy in val"
-                save_model(args, model)
+        if ctx.rank == 0 and (vl < best_loss or acc > best_acc1):
+            with averaged(args, opt):            # ... and saved: eval and gradcam load these files as they are
+                if vl < best_loss:               # train.py:264-268 "save by val loss"
+                    save_model(args, model, "_loss")
+                if acc > best_acc1:              # train.py:270-276 "save by accuracy in val"
+                    save_model(args, model)
         best_loss = min(best_loss, vl)
         best_acc1 = max(best_acc1, acc)
         expired = False
