@@ -3,19 +3,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/mmvqa.h"
+#include "host_defs.h"   // the public header, ACT_* / PRO_* / EPI_* / KIND_*, GemmParams, error codes (no HIP dependency)
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-enum { ACT_NONE = 0, ACT_RELU = 1, ACT_GELU = 2, ACT_SERF = 3, ACT_SILU = 4, ACT_SIGMOID = 5 };
-// A/B operand prologues (applied when a tile is written to LDS)
-enum { PRO_NONE = 0, PRO_AFFINE_RELU = 1, PRO_DZ = 2, PRO_AFFINE = 3, PRO_AFFINE_SILU = 4, PRO_SILU_GATE = 5 };
-// epilogue special modes
-enum { EPI_PLAIN = 0, EPI_TAP_FWD = 1, EPI_TAP_BWD = 2 };
-// contraction kinds of the implicit-GEMM family (MMVQA_KIND_* in the ABI)
-enum { KIND_FWD = 0, KIND_DGRAD = 1, KIND_WGRAD = 2 };
-
 
 // One descriptor drives the three implicit-GEMM kernels (forward / dgrad / wgrad); it is part of
 // the C ABI (include/mmvqa.h).  Geometry ("g_") describes the gathered operand: rows of the row
@@ -27,7 +18,7 @@ enum { KIND_FWD = 0, KIND_DGRAD = 1, KIND_WGRAD = 2 };
 //   g_nchw      : stem: source is NCHW [n][g_Cs][g_SH][g_SW], K index = (kh*KW+kw)*g_Cs + c
 //   epilogue order: +bias -> Cpre store -> *act'(Pre) -> act -> dropout -> +R -> ReLU mask (Mk)
 //                   -> store/atomicAdd -> column statistics (double, MMVQA_STAT_SLOTS replicas)
-typedef mmvqa_gemm_desc GemmParams;
+// (GemmParams itself is typedef'd in host_defs.h)
 typedef mmvqa_attn_desc AttnParams;
 
 // --------------------------------------------------------------------------- device math
@@ -131,7 +122,6 @@ __device__ __forceinline__ double wave_sum_d(double v) {
 // (mmvqa_bn_fold in the ABI).  The arithmetic is that of bn_coef_fwd_kernel / bn_coef_bwd_kernel (elementwise.hip):
 // sums in double over the replicas, torchvision BatchNorm2d semantics (biased variance for the batch, unbiased for the
 // running estimate, momentum applied `reps` times at once).
-typedef mmvqa_bn_fold BnFold;
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 // sums of channel c over the replicas in use: every load is issued before the first add (one memory round trip)
@@ -225,13 +215,7 @@ __device__ __forceinline__ void bn_coef_block_bwd(const float* __restrict__ P, c
 }
 
 // --------------------------------------------------------------------------- host side
-int mmvqa_set_error(int code, const char* fmt, ...);
-const char* mmvqa_get_error();
-#define MMVQA_OK 0
-#define MMVQA_ERR_ARG -1
-#define MMVQA_ERR_HIP -2
-#define MMVQA_ERR_STATE -3
-
+// (mmvqa_set_error and the MMVQA_OK / MMVQA_ERR_* codes: host_defs.h)
 #define HIP_CHECK_RET(expr)                                                               \
   do {                                                                                    \
     hipError_t _e = (expr);                                                               \

@@ -33,41 +33,16 @@
 // s for both operands; the MFMA is v_mfma_f32_32x32x16_f16 with fp32 accumulation, whose C/D layout is that of
 // the fp32 form, so the epilogues, split-K and the ticketed fix-up are shared.  The K loop is the plain one with
 // two register stages (loads of tile t+2 in flight while tile t is multiplied); no 8-wave form.
+#include <cstdlib>
+#include <cstring>
 #include <string>
 #include <type_traits>
 #include <vector>
 
 #include "kernels.h"
 
-struct FastDiv {  // q = n / d for 0 <= n < 2^31 (host-computed magic; CUTLASS FastDivmod scheme)
-  uint32_t mul, shr, d;
-};
-struct GemmAux {
-  FastDiv ohw, ow;
-  int fast;   // 0: general loaders | 1: uniform-tap loaders | 2: uniform-tap loaders with a halo mask (host-decided)
-  int stagger;   // 8-wave variant: the second wave group runs its VALU/LDS-write block first (0 = off, for A/B timing)
-  float* part;   // split-K over workgroups with a finishing launch: partial tiles [split][M][N] go here, no epilogue
-  int ldsc;      // the A-prologue coefficients are folded from raw BatchNorm sums into an LDS table in the setup phase
-                 // (mmvqa_bn_fold) and the K loop reads them there
-  // ticketed split-K (split over the grid's z WITHOUT a finishing launch): the sk_slots (= splits) workgroups of a tile
-  // publish their partial tiles to sk_part and draw a ticket each; the tile is completed by whichever of them arrives
-  // LAST (nobody waits): it sums the partial tiles and runs the epilogue.
-  int pad0;            // unused: keeps the kernel-argument offsets of the fields behind it (with sk_part 8 bytes lower the
-                       // compiler groups the argument loads differently and every kernel's register assignment shifts)
-  int sk_gx, sk_gy;    // tile grid
-  int sk_slots;        // partial tiles a tile receives (= splits)
-  float* sk_part;      // [tile][sk_slots][BM*BN]
-  unsigned* sk_cnt;    // [tile] arrival tickets, zero before and after every launch
-  int tick;            // 1: this launch is a ticketed split | 0: one workgroup per tile, or a split with a finishing launch (part)
-  int xcd;       // workgroup ids are dealt round-robin to the 8 XCDs: renumber so that an XCD gets a CONTIGUOUS run of
-                 // tiles (1: the N-tiles of an M-panel, 2: the M-tiles of an N-panel share that XCD's L2 instead of
-                 // pulling the panel into up to 8 of them)
-  // compact stride-2 data gradient (S2C instantiations only; appended so that every offset above stays where it was):
-  // the output pixels are split by parity (y&1, x&1) into four classes of s2_M = images * OH/2 * OW/2 rows; grid.y holds
-  // s2_tiles row tiles per class, class slot c = by / s2_tiles has parity bits (s2_ord >> 2c) & 3 = py*2 + px
-  FastDiv s2_hw, s2_w;   // row of a class -> (image, i, j): divisors OH/2 * OW/2 and OW/2
-  int s2_M, s2_tiles, s2_ord;
-};
+// FastDiv, GemmAux (the kernel's second argument), MAX_TAPS, SK_PART_MAX, SK_MAX, FOLD_MAX_FLOATS and the LDS geometry of
+// the operand tiles come from igemm_plan.h (through kernels.h): the host-only launch plan shares them with the kernel.
 
 // class row (n, i, j) of a compact stride-2 data gradient -> pixel row (n, 2i + py, 2j + px) of the output grid
 struct S2Map {
@@ -92,15 +67,11 @@ typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
-// LDS geometry of the operand tiles, in floats per buffer.  fp32: [row][k] rows of BK+4 floats, [k][row] rows of
-// R+4 floats.  f16: [row][k] rows of BK+8 halves (16-byte rows for ds_read_b128); [k][row] rows of R halves, +32
-// when R/2 is a multiple of 32 dwords, so that the four k-rows of one ds_read_b64_tr_b16 block fall on distinct
-// banks (row pitch = 16 or 48 dwords mod 64).
-__host__ __device__ constexpr int km_ld_h(int R) { return R + (((R / 2) % 64 == 16 || (R / 2) % 64 == 48) ? 0 : 32); }
+// LDS geometry of the operand tiles in floats per buffer (igemm_plan.h), by the kernel's template argument
 template <int PREC>
-__host__ __device__ constexpr int tile_rowk(int R, int BK) { return PREC == MMVQA_PREC_F16 ? R * (BK + 8) / 2 : R * (BK + 4); }
+__host__ __device__ constexpr int tile_rowk(int R, int BK) { return tile_rowk(PREC, R, BK); }
 template <int PREC>
-__host__ __device__ constexpr int tile_km(int R, int BK) { return PREC == MMVQA_PREC_F16 ? BK * km_ld_h(R) / 2 : BK * (R + 4); }
+__host__ __device__ constexpr int tile_km(int R, int BK) { return tile_km(PREC, R, BK); }
 
 // compile-time loops: the accumulator tiles must only ever be indexed with constants, otherwise the
 // compiler demotes them to scratch memory and re-stores them every K-tile
@@ -113,9 +84,7 @@ __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
-#define MAX_TAPS 32
 #define SC1_AUX 16       // cache-policy bits of the raw buffer builtins on gfx950: 1 = sc0, 2 = nt, 16 = sc1 (write-through / L1 bypass)
-#define SK_PART_MAX 8    // most splits of one tile in the ticketed split-K (host-checked)
 
 // Phase timestamps of every workgroup (tools/igemm_trace.py builds the library with -DIGEMM_TRACE):
 // [wg][8] = {entry, loader state ready, first tile in LDS, K loop done, end} in s_memtime ticks (per-XCD counter),
@@ -1639,8 +1608,6 @@ __global__ __launch_bounds__(256 * KS, 2) void igemm_kernel(const GemmParams p, 
   TRACE_MARK(4);
 }
 
-constexpr int FOLD_MAX_FLOATS = 3072;   // largest LDS table of folded BatchNorm coefficients (12 KB: 1024 channels x P, Q, R)
-constexpr int SK_MAX = 8;   // most workgroups one output tile's K range is split over (finishing-launch form)
 
 // Second launch of a split-K FWD / DGRAD product: sums the partial tiles [nsplit][M][N] and runs the general epilogue
 // (statistics included) exactly as the single-launch kernel does on its accumulators.
@@ -1677,160 +1644,110 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const GemmParams p, 
                                 });
 }
 
+
 // --------------------------------------------------------------------------- host launch
-static FastDiv make_fastdiv(int d) {
-  FastDiv f;
-  f.d = (uint32_t)d;
-  if (d <= 1) { f.mul = 0; f.shr = 0; f.d = 1; return f; }
-  int lg = 31;
-  while (lg > 0 && !((uint32_t)d >> lg)) --lg;   // floor(log2 d)
-  if (d & (d - 1)) ++lg;                         // ceil(log2 d)
-  const int pw = 31 + lg;
-  const uint64_t m = ((1ull << pw) + (uint64_t)d - 1) / (uint64_t)d;
-  f.mul = (uint32_t)m;
-  f.shr = (uint32_t)(pw - 32);
-  return f;
+// mmvqa_launch_igemm = validate_desc -> tuner -> igemm_plan (all igemm_plan.h: pure host code, tested without a GPU)
+// -> igemm_run, which looks the planned instance up in the table below and enqueues what the plan says.
+
+// every igemm_kernel instance the library contains: X(BM, BN, BK, KIND, NCHW, KS, PREC, S2C)
+#define IGEMM_NHWC_TILE(X, BM, BN, BK)                      \
+  X(BM, BN, BK, KIND_FWD, false, 1, MMVQA_PREC_F32, false)   \
+  X(BM, BN, BK, KIND_DGRAD, false, 1, MMVQA_PREC_F32, false) \
+  X(BM, BN, BK, KIND_DGRAD, false, 1, MMVQA_PREC_F32, true)  \
+  X(BM, BN, BK, KIND_WGRAD, false, 1, MMVQA_PREC_F32, false) \
+  X(BM, BN, BK, KIND_FWD, false, 1, MMVQA_PREC_F16, false)   \
+  X(BM, BN, BK, KIND_DGRAD, false, 1, MMVQA_PREC_F16, false) \
+  X(BM, BN, BK, KIND_WGRAD, false, 1, MMVQA_PREC_F16, false)
+#define IGEMM_INSTANCES(X)                                   \
+  IGEMM_NHWC_TILE(X, 128, 128, 32)                           \
+  IGEMM_NHWC_TILE(X, 128, 64, 32)                            \
+  IGEMM_NHWC_TILE(X, 64, 64, 64)                             \
+  IGEMM_NHWC_TILE(X, 64, 128, 32)                            \
+  IGEMM_NHWC_TILE(X, 64, 64, 32)                             \
+  X(64, 64, 64, KIND_FWD, false, 2, MMVQA_PREC_F32, false)   \
+  X(64, 64, 64, KIND_DGRAD, false, 2, MMVQA_PREC_F32, false) \
+  X(64, 64, 64, KIND_DGRAD, false, 2, MMVQA_PREC_F32, true)  \
+  X(64, 64, 64, KIND_WGRAD, false, 2, MMVQA_PREC_F32, false) \
+  X(128, 64, 32, KIND_FWD, true, 1, MMVQA_PREC_F32, false)   \
+  X(64, 64, 32, KIND_WGRAD, true, 1, MMVQA_PREC_F32, false)  \
+  X(128, 64, 32, KIND_FWD, true, 1, MMVQA_PREC_F16, false)   \
+  X(64, 64, 32, KIND_WGRAD, true, 1, MMVQA_PREC_F16, false)
+
+struct IgemmInstance {
+  IgemmShape shape;
+  const void* fn;
+  size_t smem_max;     // the instance's dynamic LDS with the largest fold table: its MaxDynamicSharedMemorySize attribute
+  int attr_dev_mask;   // devices the attribute is set on (a second device in the process needs it too; the call is cheap)
+};
+#define IGEMM_ROW(BM, BN, BK, KIND, NCHW, KS, PREC, S2C)                                      \
+  {IgemmShape{BM, BN, BK, KS, KIND, NCHW, PREC, S2C},                                         \
+   (const void*)igemm_kernel<BM, BN, BK, KIND, NCHW, KS, PREC, S2C>,                          \
+   igemm_smem_bytes(IgemmShape{BM, BN, BK, KS, KIND, NCHW, PREC, S2C}, FOLD_MAX_FLOATS), 0},
+static IgemmInstance g_instances[] = {IGEMM_INSTANCES(IGEMM_ROW)};
+#undef IGEMM_ROW
+
+// the A/B switches of the process, read once
+static const IgemmSwitches& igemm_switches() {
+  static const IgemmSwitches sw = [] {
+    IgemmSwitches s;
+    s.general = getenv("MMVQA_IGEMM_GENERAL") != nullptr;
+    s.no_stagger = getenv("MMVQA_IGEMM_NOSTAGGER") != nullptr;
+    s.sk_finish = getenv("MMVQA_SK_FINISH") != nullptr;
+    s.no_xcd = getenv("MMVQA_IGEMM_NOXCD") != nullptr;
+    s.s2_dense = getenv("MMVQA_DGRAD_S2_DENSE") != nullptr;
+    s.log = getenv("MMVQA_IGEMM_LOG") != nullptr;   // one line per launch: which loader family a shape gets (diagnostics)
+    // (0.85 with the finishing launch; the ticketed form has no second launch, but still takes CUs from the other stream)
+    s.sk_gain = getenv("MMVQA_SK_GAIN") ? (float)atof(getenv("MMVQA_SK_GAIN")) : (s.sk_finish ? 0.85f : 0.92f);
+    s.tune_reps = getenv("MMVQA_TUNE_REPS") ? atoi(getenv("MMVQA_TUNE_REPS")) : 3;
+    return s;
+  }();
+  return sw;
 }
 
-template <int BM, int BN, int BK, int KIND, bool NCHW, int KS = 1, int PREC = MMVQA_PREC_F32, bool S2C = false>
-static int launch_cfg(GemmParams p, hipStream_t stream) {
-  constexpr bool A_ROWK = (KIND != KIND_WGRAD);
-  constexpr bool B_ROWK = (KIND == KIND_FWD);
-  constexpr int A_TILE = A_ROWK ? tile_rowk<PREC>(BM, BK) : tile_km<PREC>(BM, BK);
-  constexpr int B_TILE = B_ROWK ? tile_rowk<PREC>(BN, BK) : tile_km<PREC>(BN, BK);
-  constexpr size_t tile_floats = (size_t)(2 * A_TILE + 2 * B_TILE + MAX_TAPS);
-  constexpr size_t epi_floats = (size_t)BM * (BN + 4) + 8 * BN;   // staged output tile + tap accumulators
-  constexpr size_t smem_max = (tile_floats + FOLD_MAX_FLOATS > epi_floats ? tile_floats + FOLD_MAX_FLOATS : epi_floats) * sizeof(float);
-  // (per device: a second device in the process needs the attribute too; the call is cheap)
-  static int attr_dev_mask = 0;
+// carries a plan out: [coefficient launch] -> igemm_kernel -> [finishing launch]
+static int igemm_run(const IgemmPlan& pl, hipStream_t stream) {
+  IgemmInstance* inst = nullptr;
+  for (IgemmInstance& r : g_instances)
+    if (!memcmp(&r.shape, &pl.shape, sizeof(IgemmShape))) { inst = &r; break; }
+  const IgemmShape& s = pl.shape;
+  if (!inst)
+    return mmvqa_set_error(MMVQA_ERR_STATE, "igemm: no kernel instance %dx%dx%d ks %d kind %d nchw %d prec %d compact %d",
+                           s.bm, s.bn, s.bk, s.ks, s.kind, s.nchw, s.prec, s.s2c);
   int dev = 0;
   (void)hipGetDevice(&dev);
-  if (!(attr_dev_mask >> (dev & 31) & 1)) {
-    HIP_CHECK_RET(hipFuncSetAttribute((const void*)igemm_kernel<BM, BN, BK, KIND, NCHW, KS, PREC, S2C>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem_max));
-    attr_dev_mask |= 1 << (dev & 31);
+  if (!(inst->attr_dev_mask >> (dev & 31) & 1)) {
+    HIP_CHECK_RET(hipFuncSetAttribute(inst->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)inst->smem_max));
+    inst->attr_dev_mask |= 1 << (dev & 31);
   }
-  GemmAux x;
-  x.ohw = make_fastdiv(p.g_OH * p.g_OW);
-  x.ow = make_fastdiv(p.g_OW);
-  // uniform-tap loaders: a K-tile never straddles a filter tap, nothing ragged, 31-bit byte offsets
-  x.fast = 0;
-  static const int stagger_on = getenv("MMVQA_IGEMM_NOSTAGGER") ? 0 : 1;
-  x.stagger = stagger_on;
-  x.part = (KIND != KIND_WGRAD && !NCHW && p.splitk > 1 && !p.c_atomic) ? p.sk_ws : nullptr;
-  if (!NCHW && (p.K % BK == 0 || (KIND == KIND_WGRAD && p.pixmask)) && !p.gate && !getenv("MMVQA_IGEMM_GENERAL")) {
-    const int taps = p.g_KH * p.g_KW;
-    const double lim = 2147483648.0 - 16777216.0;
-    if (KIND != KIND_WGRAD) {
-      const bool pro_ok = (KIND == KIND_FWD) ? (p.a_pro == PRO_NONE || p.a_pro == PRO_AFFINE_RELU)
-                                             : (p.a_pro == PRO_NONE || p.a_pro == PRO_DZ);
-      const double a_bytes = (KIND == KIND_FWD) ? (double)p.M * p.g_stride * p.g_stride * p.a_ld * 4.0 + (double)(p.g_SW + 2) * p.g_KH * p.a_ld * 4.0
-                                                : (double)p.M * p.a_ld * 4.0;
-      const double b_bytes = (KIND == KIND_FWD) ? (double)p.N * p.b_ld * 4.0 : (double)p.g_Cs * p.b_ld * 4.0;
-      if (pro_ok && p.b_pro == PRO_NONE && p.g_Cs % BK == 0 && p.g_stride <= 2 && a_bytes < lim && b_bytes < lim &&
-          (KIND == KIND_FWD || p.N % 4 == 0))
-        x.fast = (taps > 1 || (KIND == KIND_DGRAD && p.g_stride > 1)) ? 2 : 1;
-    } else {
-      const bool pro_ok = (p.a_pro == PRO_NONE || p.a_pro == PRO_DZ) && (p.b_pro == PRO_NONE || p.b_pro == PRO_AFFINE_RELU);
-      if (pro_ok && taps == 1 && p.K % BK == 0 && p.g_stride == 1 && p.g_pad == 0 && p.M % 4 == 0 && p.N % 4 == 0 &&
-          (double)p.K * p.a_ld * 4.0 < lim && (double)p.K * p.b_ld * 4.0 < lim)
-        x.fast = 1;
-      // 3x3-like "same" convolution, stride 1, with the caller's tap-validity table; pixels past K are masked by
-      // the table's range check, so K need not be a multiple of the K-tile here
-      else if (pro_ok && taps > 1 && taps <= 32 && p.pixmask && p.g_stride == 1 && p.g_OH == p.g_SH && p.g_OW == p.g_SW &&
-               2 * p.g_pad == p.g_KH - 1 && p.g_KH == p.g_KW && BM == 64 && BN == 64 && p.g_Cs % BN == 0 && p.M % 4 == 0 &&
-               (double)p.K * p.a_ld * 4.0 < lim && (double)(p.K + (double)p.g_SW * p.g_KH) * p.b_ld * 4.0 < lim)
-        x.fast = 2;
-    }
+  const GemmParams& p = pl.p;
+  if (pl.coef_launch) {
+    const BnFold& f = p.a_fold;
+    const int C = s.kind != KIND_WGRAD ? p.g_Cs : p.M;
+    if (pl.coef_launch == 2)
+      TRY(mmvqa_bn_coef_bwd(stream, pl.coef_stat, C, f.count, f.gamma, f.mean, f.invstd, 1, f.out0, f.out1, f.out2, f.dgamma, f.dbeta));
+    else
+      TRY(k_bn_coef_fwd_keep(stream, pl.coef_stat, C, f.count, f.eps, f.gamma, f.beta, f.run_mean, f.run_var, f.nbt, f.keep,
+                             f.reps, 1, f.out0, f.out1, f.out2, f.out3));
   }
-  if (S2C && x.fast != 2)
-    return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: the compact stride-2 data gradient needs the uniform-tap loaders");
-  // BatchNorm coefficients of the A prologue folded in the kernel's setup (mmvqa_bn_fold).  The K loop reads the LDS table
-  // only in its uniform-tap forms; the weight gradient keeps its (loop-invariant) coefficients in registers.  Anything
-  // else -- general loaders, a table beyond FOLD_MAX_FLOATS -- gets the coefficient launch in front, as before.
-  x.ldsc = 0;
-  size_t fold_floats = 0;
-  if (p.a_fold.stat) {
-    const int ncoef = p.a_fold.bwd ? 3 : 2;
-    const size_t need = A_ROWK ? (size_t)ncoef * p.g_Cs : (size_t)3 * BM;
-    const bool pro_ok = p.a_fold.bwd ? p.a_pro == PRO_DZ : p.a_pro == PRO_AFFINE_RELU;
-    if (pro_ok && need <= FOLD_MAX_FLOATS && (KIND == KIND_WGRAD || x.fast != 0)) {
-      x.ldsc = 1;
-      fold_floats = need;
-    } else {
-      const BnFold f = p.a_fold;
-      const int C = A_ROWK ? p.g_Cs : p.M;
-      if (!f.publish || !f.out0 || !f.out1 || !f.out2)
-        return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: this launch cannot fold its BatchNorm coefficients in the kernel and has nowhere to publish them");
-      if (f.bwd)
-        TRY(mmvqa_bn_coef_bwd(stream, f.stat, C, f.count, f.gamma, f.mean, f.invstd, 1, f.out0, f.out1, f.out2, f.dgamma, f.dbeta));
-      else
-        TRY(k_bn_coef_fwd_keep(stream, f.stat, C, f.count, f.eps, f.gamma, f.beta, f.run_mean, f.run_var, f.nbt, f.keep,
-                                   f.reps, 1, f.out0, f.out1, f.out2, f.out3));
-      p.a_c0 = f.out0; p.a_c1 = f.out1; p.a_c2 = f.out2;
-      p.a_fold.stat = nullptr;
-    }
-  }
-  const size_t smem = ((tile_floats + fold_floats > epi_floats ? tile_floats + fold_floats : epi_floats)) * sizeof(float);
-  dim3 grid((p.N + BN - 1) / BN, (p.M + BM - 1) / BM, p.splitk);
-  x.s2_hw = make_fastdiv(1); x.s2_w = make_fastdiv(1); x.s2_M = 0; x.s2_tiles = 0; x.s2_ord = 0;
-  if (S2C) {
-    // four parity classes of M / 4 rows each in one grid; the class with the most taps first (its tiles run longest)
-    x.s2_hw = make_fastdiv((p.g_OH / 2) * (p.g_OW / 2));
-    x.s2_w = make_fastdiv(p.g_OW / 2);
-    x.s2_M = p.M / 4;
-    x.s2_tiles = (x.s2_M + BM - 1) / BM;
-    grid.y = 4 * x.s2_tiles;
-    int cls[4] = {0, 1, 2, 3}, nt[4];
-    for (int c = 0; c < 4; ++c) {
-      const int h0 = ((c >> 1) + p.g_pad) & 1, w0 = ((c & 1) + p.g_pad) & 1;
-      nt[c] = (h0 < p.g_KH ? (p.g_KH - h0 + 1) / 2 : 0) * (w0 < p.g_KW ? (p.g_KW - w0 + 1) / 2 : 0);
-    }
-    for (int i = 1; i < 4; ++i)
-      for (int j = i; j > 0 && nt[cls[j]] > nt[cls[j - 1]]; --j) { const int t = cls[j]; cls[j] = cls[j - 1]; cls[j - 1] = t; }
-    for (int i = 0; i < 4; ++i) x.s2_ord |= cls[i] << (2 * i);
-  }
-  x.pad0 = 0; x.sk_gx = (int)grid.x; x.sk_gy = (int)grid.y; x.sk_slots = 0; x.sk_part = nullptr; x.sk_cnt = nullptr; x.tick = 0;
-  // split-K of a forward / data-gradient product: with the caller's tickets the last workgroup of a tile finishes it
-  // (no second launch); MMVQA_SK_FINISH=1 keeps the finishing launch (A/B switch)
-  static const bool finish_form = getenv("MMVQA_SK_FINISH") != nullptr;
-  if (x.part && !finish_form && p.sk_cnt && p.splitk <= SK_PART_MAX && p.epi_mode == EPI_PLAIN) {
-    const long long tiles = (long long)grid.x * grid.y;
-    if (tiles <= p.sk_cnt_n && tiles * p.splitk * (long long)(BM * BN) <= p.sk_ws_floats) {
-      x.tick = 1; x.part = nullptr; x.sk_slots = p.splitk; x.sk_part = p.sk_ws; x.sk_cnt = p.sk_cnt;
-    }
-  }
-  static const int xcd_on = getenv("MMVQA_IGEMM_NOXCD") ? 0 : 1;   // A/B switch
-  const long nwg = (long)grid.x * grid.y * grid.z;
-  x.xcd = 0;
-  if (xcd_on && nwg >= 32 && !NCHW) {
-    // bytes behind the row panels (A side) and the column panels (B side): keep the larger one XCD-local
-    double a_bytes, b_bytes;
-    if (KIND == KIND_WGRAD) { a_bytes = (double)p.K * p.M * (p.a_pro == PRO_DZ ? 2 : 1); b_bytes = (double)p.K * p.g_Cs; }
-    else if (KIND == KIND_FWD) { a_bytes = (double)p.M * p.g_stride * p.g_stride * p.g_Cs; b_bytes = (double)p.N * p.K; }
-    else { a_bytes = (double)p.M * p.g_Cs * (p.a_pro == PRO_DZ ? 2 : 1); b_bytes = (double)p.N * p.K; }
-    x.xcd = (b_bytes > a_bytes && x.sk_gy > 1) ? 2 : (x.sk_gx > 1 ? 1 : 0);
-  }
-  if (getenv("MMVQA_IGEMM_LOG"))   // one line per launch: which loader family a shape gets (diagnostics)
-    fprintf(stderr, "igemm kind %d fast %d tile %dx%dx%d ks %d M %d N %d K %d Cs %d taps %d stride %d apro %d bpro %d splitk %d fold %d tick %d prec %s%s\n", KIND, x.fast,
-            BM, BN, BK, KS, p.M, p.N, p.K, p.g_Cs, p.g_KH * p.g_KW, p.g_stride, p.a_pro, p.b_pro, p.splitk, x.ldsc, x.tick,
-            PREC == MMVQA_PREC_F16 ? "f16" : "f32", S2C ? " compact" : "");
-  hipLaunchKernelGGL((igemm_kernel<BM, BN, BK, KIND, NCHW, KS, PREC, S2C>), grid, dim3(256 * KS), smem, stream, p, x);
+  if (igemm_switches().log)
+    fprintf(stderr, "igemm kind %d fast %d tile %dx%dx%d ks %d M %d N %d K %d Cs %d taps %d stride %d apro %d bpro %d splitk %d fold %d tick %d prec %s%s\n", s.kind, pl.x.fast,
+            s.bm, s.bn, s.bk, s.ks, p.M, p.N, p.K, p.g_Cs, p.g_KH * p.g_KW, p.g_stride, p.a_pro, p.b_pro, p.splitk, pl.x.ldsc, pl.x.tick,
+            s.prec == MMVQA_PREC_F16 ? "f16" : "f32", s.s2c ? " compact" : "");
+  void* args[] = {(void*)&pl.p, (void*)&pl.x};
+  (void)hipLaunchKernel(inst->fn, dim3(pl.grid[0], pl.grid[1], pl.grid[2]), dim3(pl.threads), args, pl.smem, stream);
   KERNEL_CHECK_RET();
-  if (x.part) {
-    hipLaunchKernelGGL(splitk_finish_kernel, dim3((p.N + 63) / 64, (p.M + 63) / 64), dim3(256), 0, stream, p, x.part,
+  if (pl.finish) {
+    hipLaunchKernelGGL(splitk_finish_kernel, dim3((p.N + 63) / 64, (p.M + 63) / 64), dim3(256), 0, stream, p, pl.x.part,
                        p.splitk);
     KERNEL_CHECK_RET();
   }
   return MMVQA_OK;
 }
 
-static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
-
-// split-K of a forward / data-gradient product over workgroups (partial tiles + finishing launch): the caller gave a
-// scratch, the epilogue is the general one, nothing accumulates into C
-static bool sk_eligible(const GemmParams& p, int kind) {
-  return kind != KIND_WGRAD && p.sk_ws && p.sk_ws_floats > 0 && p.epi_mode == EPI_PLAIN && !p.c_atomic;
+static int plan_and_run(const GemmParams& p, int kind, int nchw, int tile, hipStream_t stream) {
+  IgemmPlan pl;
+  TRY(igemm_plan(p, kind, nchw, tile, igemm_switches(), &pl));
+  return igemm_run(pl, stream);
 }
 
 // --------------------------------------------------------------------------- per-shape tuner
@@ -1844,95 +1761,52 @@ void mmvqa_set_tuner(IgemmTuner* t) { g_tuner = t; }
 static thread_local int g_prec = MMVQA_PREC_F32;
 void mmvqa_set_igemm_precision(int prec) { g_prec = prec; }
 
-// Compact form of a stride-2 data gradient (igemm_kernel, S2C): the conditions of the uniform-tap loaders for both K-tile
-// depths, an output grid with even sides, a plain epilogue, fp32 operands.  Everything else -- and everything when
-// MMVQA_DGRAD_S2_DENSE is set (A/B switch) -- takes the dense walk over all KH*KW taps, as before.
-static bool s2c_eligible(const GemmParams& p, int kind, int nchw) {
-  static const bool dense = getenv("MMVQA_DGRAD_S2_DENSE") != nullptr;
-  if (dense || kind != KIND_DGRAD || nchw || p.g_KH <= 0 || p.g_KW <= 0 || p.g_stride != 2) return false;
-  if (p.reserved0 != MMVQA_PREC_F32 || p.epi_mode != EPI_PLAIN || p.c_atomic || p.gate || getenv("MMVQA_IGEMM_GENERAL")) return false;
-  if ((p.g_OH & 1) || (p.g_OW & 1) || p.M != (p.M / (p.g_OH * p.g_OW)) * p.g_OH * p.g_OW) return false;
-  if (((p.g_KH + 1) / 2) * ((p.g_KW + 1) / 2) > MAX_TAPS) return false;   // validity bits of one class
-  const double lim = 2147483648.0 - 16777216.0;
-  return (p.a_pro == PRO_NONE || p.a_pro == PRO_DZ) && p.b_pro == PRO_NONE && p.g_Cs % 64 == 0 && p.N % 4 == 0 &&
-         p.K == p.g_KH * p.g_KW * p.g_Cs && (double)p.M * p.a_ld * 4.0 < lim && (double)p.g_Cs * p.b_ld * 4.0 < lim;
-}
-
 static std::string tune_key(const GemmParams& p, int kind, int nchw) {
   char buf[176];
   snprintf(buf, sizeof(buf), "%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d", p.reserved0, kind, nchw, p.M, p.N, p.K,
            p.g_KH * p.g_KW, p.g_stride, p.g_Cs, p.a_pro, p.b_pro, p.epi_mode, p.act | (p.dact << 4),
            (p.stat1 ? 1 : 0) | (p.stat2 ? 2 : 0) | (p.Mk ? 4 : 0) | (p.R ? 8 : 0) | (p.Cpre ? 16 : 0) |
                (p.colsum ? 32 : 0) | (p.bias ? 64 : 0) | (p.sk_ws ? 128 : 0) | (p.a_fold.stat ? 256 : 0) | (p.sk_cnt ? 512 : 0),
-           p.c_atomic, p.splitk, s2c_eligible(p, kind, nchw) ? 1 : 0);
+           p.c_atomic, p.splitk, s2c_eligible(p, kind, nchw, igemm_switches()) ? 1 : 0);
   return buf;
 }
 
-static int launch_one(GemmParams p, int kind, int nchw, int tile, hipStream_t stream);
-
-// Host-side consistency check of a descriptor.  The loaders address the operands from (M, N, K, geometry, leading
-// dimensions) alone -- the uniform-tap path even lets the hardware range check of a 2 GB buffer window stand in for
-// per-element bounds tests -- so a descriptor whose dimensions disagree with each other (or a prologue / epilogue
-// option without its tensors) would read outside the caller's buffers.  Such a descriptor is refused here.
-#define BAD(...) return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: " __VA_ARGS__)
-// the part that does not depend on the product's size: mmvqa_igemm refuses these even for an empty product
-static int validate_operands(const GemmParams& p, int kind, int nchw) {
-  if (kind < KIND_FWD || kind > KIND_WGRAD) BAD("kind=%d", kind);
-  if (!p.A || !p.B || (!p.C && p.epi_mode != EPI_TAP_FWD)) BAD("null operand");
-  if (!nchw) {   // NHWC operands: rows of A and B, and every tap's channel run, start 16-byte aligned
-    if ((p.a_ld & 3) || (p.b_ld & 3) || (p.g_KH * p.g_KW > 1 && (p.g_Cs & 3)))
-      BAD("a_ld=%d b_ld=%d g_Cs=%d must be multiples of 4", p.a_ld, p.b_ld, p.g_Cs);
-    if (kind == KIND_DGRAD && (p.N & 3)) return mmvqa_set_error(MMVQA_ERR_ARG, "igemm dgrad: N=%d must be a multiple of 4", p.N);
+// times tune_candidates(p, kind) on the caller's operands; the fastest goes to *best
+static int tune_shape(const GemmParams& p, int kind, int nchw, hipStream_t stream, IgemmChoice* best_out) {
+  const IgemmSwitches& sw = igemm_switches();
+  const std::vector<IgemmChoice> cands = tune_candidates(p, kind);
+  hipEvent_t e0, e1;
+  HIP_CHECK_RET(hipEventCreate(&e0));
+  HIP_CHECK_RET(hipEventCreate(&e1));
+  float best = 1e30f, best_single = 1e30f;
+  IgemmChoice bc = cands[0], bc_single = cands[0];
+  for (const IgemmChoice& c : cands) {
+    GemmParams q = p;
+    q.splitk = c.splitk;
+    int r = plan_and_run(q, kind, nchw, c.tile, stream);  // warm-up (also sets the LDS attribute)
+    if (r != MMVQA_OK) continue;
+    // best of `tune_reps` batches of three launches (one batch left the choice between near-equal candidates to
+    // timing noise: the same build then measured 24.8 - 25.2 ms per config-2 step from run to run)
+    float ms = 1e30f;
+    for (int rep = 0; rep < (sw.tune_reps > 0 ? sw.tune_reps : 1); ++rep) {
+      HIP_CHECK_RET(hipEventRecord(e0, stream));
+      for (int i = 0; i < 3; ++i) plan_and_run(q, kind, nchw, c.tile, stream);
+      HIP_CHECK_RET(hipEventRecord(e1, stream));
+      HIP_CHECK_RET(hipEventSynchronize(e1));
+      float t = 0.f;
+      HIP_CHECK_RET(hipEventElapsedTime(&t, e0, e1));
+      if (t < ms) ms = t;
+    }
+    if (ms < best) { best = ms; bc = c; }
+    if (c.splitk <= 1 && ms < best_single) { best_single = ms; bc_single = c; }
   }
-  if (p.a_pro == PRO_DZ && (!p.A2 || (!p.a_fold.stat && (!p.a_c0 || !p.a_c1 || !p.a_c2))))
-    BAD("PRO_DZ needs A2 and three coefficient arrays (or a_fold)");
-  if (p.g_SH <= 0 || p.g_SW <= 0 || p.g_OH <= 0 || p.g_OW <= 0 || p.g_Cs <= 0) BAD("gather geometry not set");
-  return MMVQA_OK;
-}
-
-static int validate_desc(const GemmParams& p, int kind, int nchw) {
-  if (int r = validate_operands(p, kind, nchw)) return r;
-  if (p.reserved0 != MMVQA_PREC_F32 && p.reserved0 != MMVQA_PREC_F16) BAD("unknown operand precision %d (reserved0)", p.reserved0);
-  if (p.reserved1 != 0) BAD("reserved1=%d must be 0 (the persistent form was removed)", p.reserved1);
-  if (p.reserved0 == MMVQA_PREC_F16 && (p.a_pro == PRO_AFFINE_SILU || p.a_pro == PRO_SILU_GATE || p.b_pro == PRO_AFFINE_SILU ||
-                                        p.b_pro == PRO_SILU_GATE || p.gate))
-    BAD("the f16 operand family has no SiLU / gate prologues (a_pro %d, b_pro %d)", p.a_pro, p.b_pro);
-  const int KH = p.g_KH > 0 ? p.g_KH : 1, KW = p.g_KH > 0 ? p.g_KW : 1;
-  const long taps = (long)KH * KW;
-  if (KW <= 0 || (p.g_KH > 0 && (p.g_stride <= 0 || p.g_pad < 0))) BAD("bad geometry (KH=%d KW=%d Cs=%d stride=%d pad=%d)", p.g_KH, p.g_KW, p.g_Cs, p.g_stride, p.g_pad);
-  const long ohw = (long)p.g_OH * p.g_OW;
-  if (kind == KIND_WGRAD) {
-    if ((long)p.N != taps * p.g_Cs) BAD("wgrad: N=%d != taps*Cs=%ld", p.N, taps * p.g_Cs);
-    if (p.K % ohw) BAD("wgrad: K=%d is not a multiple of OH*OW=%ld", p.K, ohw);
-    if (p.a_ld < p.M || (!nchw && p.b_ld < p.g_Cs) || p.c_ld < p.N) BAD("wgrad: leading dimension too small (a_ld=%d M=%d b_ld=%d Cs=%d c_ld=%d N=%d)", p.a_ld, p.M, p.b_ld, p.g_Cs, p.c_ld, p.N);
-  } else {
-    if ((long)p.K != taps * p.g_Cs) BAD("K=%d != taps*Cs=%ld", p.K, taps * p.g_Cs);
-    if (p.M % ohw) BAD("M=%d is not a multiple of OH*OW=%ld", p.M, ohw);
-    if (!nchw && p.a_ld < p.g_Cs) BAD("a_ld=%d < Cs=%d", p.a_ld, p.g_Cs);
-    if (kind == KIND_FWD && p.b_ld < p.K) BAD("fwd: b_ld=%d < K=%d", p.b_ld, p.K);
-    if (kind == KIND_DGRAD && ((long)p.b_ld < (taps - 1) * p.b_tapstride + p.N)) BAD("dgrad: b_ld=%d < (taps-1)*tapstride+N", p.b_ld);
-    if (p.epi_mode == EPI_PLAIN && p.c_ld < p.N) BAD("c_ld=%d < N=%d", p.c_ld, p.N);
-  }
-  if (p.a_fold.stat) {
-    const mmvqa_bn_fold& f = p.a_fold;
-    if (f.slots <= 0 || f.slots > MMVQA_STAT_SLOTS || (f.slots & (f.slots - 1))) BAD("a_fold.slots=%d is not a power of two <= %d", f.slots, MMVQA_STAT_SLOTS);
-    if (!(f.count > 0.0) || !f.gamma) BAD("a_fold without count / gamma");
-    if (f.bwd ? (p.a_pro != PRO_DZ || !f.mean || !f.invstd) : (p.a_pro != PRO_AFFINE_RELU || !f.beta)) BAD("a_fold.bwd=%d does not match A prologue %d (or mean / invstd / beta missing)", f.bwd, p.a_pro);
-    if (f.publish && (!f.out0 || !f.out1 || !f.out2 || (f.bwd ? (!f.dgamma || !f.dbeta) : !f.out3))) BAD("a_fold.publish without output arrays");
-    if (nchw && kind != KIND_WGRAD) BAD("a_fold: not for the NCHW stem forward");
-  } else if (p.a_pro != PRO_NONE && (!p.a_c0 || !p.a_c1)) BAD("A prologue %d without coefficients", p.a_pro);
-  if (p.stat_slots < 0 || p.stat_slots > MMVQA_STAT_SLOTS || (p.stat_slots & (p.stat_slots - 1))) BAD("stat_slots=%d is not a power of two <= %d", p.stat_slots, MMVQA_STAT_SLOTS);
-  if (p.b_pro != PRO_NONE && (!p.b_c0 || !p.b_c1)) BAD("B prologue %d without coefficients", p.b_pro);
-  if ((p.a_pro == PRO_SILU_GATE || p.b_pro == PRO_SILU_GATE) && (!p.gate || p.gate_hw <= 0)) BAD("gate prologue without gate tensor");
-  if (p.dact != ACT_NONE && !p.Pre) BAD("act' epilogue without the saved pre-activation");
-  if (p.stat_bwd && p.stat1 && (!p.Z1 || !p.mean1 || !p.invstd1)) BAD("backward statistics without Z1 / mean / invstd");
-  if (p.stat2 && (!p.stat1 || !p.Z2 || !p.mean2 || !p.invstd2)) BAD("second statistics set incomplete");
-  if (p.epi_mode == EPI_TAP_FWD && (!p.tap_out || p.tap_HW <= 0)) BAD("tap epilogue without output / HW");
-  if (p.epi_mode == EPI_TAP_BWD && (!p.tap_dv || p.tap_HW <= 0)) BAD("tap backward epilogue without dv / HW");
-  if (p.Mk && p.mk_ld < p.N) BAD("mask tensor leading dimension %d < N=%d", p.mk_ld, p.N);
-  if (p.R && p.r_ld < p.N) BAD("residual leading dimension %d < N=%d", p.r_ld, p.N);
-  if (p.drop_p < 0.f || p.drop_p >= 1.f) BAD("dropout p=%g outside [0,1)", (double)p.drop_p);
-#undef BAD
+  // K split over workgroups is timed here on an empty chip; inside the step it takes the CUs the other stream would use
+  // (and, with a finishing launch, costs a second launch on the dependency chain): only worth it when clearly faster
+  const bool sk_partial = sk_eligible(p, kind) && p.splitk <= 0;
+  if (sk_partial && bc.splitk > 1 && best_single < 1e29f && best > sw.sk_gain * best_single) bc = bc_single;
+  hipEventDestroy(e0);
+  hipEventDestroy(e1);
+  *best_out = bc;
   return MMVQA_OK;
 }
 
@@ -1940,63 +1814,17 @@ int mmvqa_launch_igemm(GemmParams p, int kind, int nchw, int tile, hipStream_t s
   if (p.M <= 0 || p.N <= 0 || p.K <= 0) return MMVQA_OK;
   if (p.reserved0 == MMVQA_PREC_F32) p.reserved0 = g_prec;
   if (int r = validate_desc(p, kind, nchw)) return r;
-  if (tile != 0 || nchw || !g_tuner) return launch_one(p, kind, nchw, tile, stream);
+  if (tile != 0 || nchw || !g_tuner) return plan_and_run(p, kind, nchw, tile, stream);
   const std::string key = tune_key(p, kind, nchw);
   auto it = g_tuner->table.find(key);
   if (it == g_tuner->table.end()) {
-    if (!g_tuner->tuning) return launch_one(p, kind, nchw, 0, stream);
-    struct Cand { int tile, splitk; };
-    std::vector<Cand> cands;
-    const int tiles_f[] = {1, 2, 3, 4, 5, 6}, tiles_w[] = {1, 2, 3, 4, 5, 6};
-    if (kind == KIND_WGRAD && p.splitk <= 0) {
-      for (int t : tiles_w) for (int sk : {0, 1, 2, 3, 4, 6, 8, 12, 16}) cands.push_back({t, sk});
-    } else if (kind == KIND_WGRAD) {
-      for (int t : tiles_w) cands.push_back({t, p.splitk});
-    } else if (sk_eligible(p, kind) && p.splitk <= 0 && (long)cdiv(p.M, 64) * cdiv(p.N, 64) <= 320) {
-      // few output tiles: also try K split over workgroups with a finishing launch (needs the caller's scratch)
-      for (int t : {3, 5, 6}) for (int sk : {1, 2, 3, 4, 6, 8}) cands.push_back({t, sk});
-      for (int t : {1, 2, 4}) cands.push_back({t, 1});
-    } else {
-      for (int t : tiles_f) cands.push_back({t, p.splitk});
-    }
-    hipEvent_t e0, e1;
-    HIP_CHECK_RET(hipEventCreate(&e0));
-    HIP_CHECK_RET(hipEventCreate(&e1));
-    float best = 1e30f, best_single = 1e30f;
-    Cand bc = cands[0], bc_single = cands[0];
-    const bool sk_partial = kind != KIND_WGRAD && sk_eligible(p, kind) && p.splitk <= 0;
-    // (0.85 with the finishing launch; the ticketed form has no second launch, but still takes CUs from the other stream)
-    static const float sk_gain = getenv("MMVQA_SK_GAIN") ? (float)atof(getenv("MMVQA_SK_GAIN")) : (getenv("MMVQA_SK_FINISH") ? 0.85f : 0.92f);
-    for (const Cand& c : cands) {
-      GemmParams q = p;
-      q.splitk = c.splitk;
-      int r = launch_one(q, kind, nchw, c.tile, stream);  // warm-up (also sets the LDS attribute)
-      if (r != MMVQA_OK) continue;
-      // best of `tune_reps` batches of three launches (one batch left the choice between near-equal candidates to
-      // timing noise: the same build then measured 24.8 - 25.2 ms per config-2 step from run to run)
-      static const int tune_reps = getenv("MMVQA_TUNE_REPS") ? atoi(getenv("MMVQA_TUNE_REPS")) : 3;
-      float ms = 1e30f;
-      for (int rep = 0; rep < (tune_reps > 0 ? tune_reps : 1); ++rep) {
-        HIP_CHECK_RET(hipEventRecord(e0, stream));
-        for (int i = 0; i < 3; ++i) launch_one(q, kind, nchw, c.tile, stream);
-        HIP_CHECK_RET(hipEventRecord(e1, stream));
-        HIP_CHECK_RET(hipEventSynchronize(e1));
-        float t = 0.f;
-        HIP_CHECK_RET(hipEventElapsedTime(&t, e0, e1));
-        if (t < ms) ms = t;
-      }
-      if (ms < best) { best = ms; bc = c; }
-      if (c.splitk <= 1 && ms < best_single) { best_single = ms; bc_single = c; }
-    }
-    // K split with a finishing launch is timed here on an empty chip; inside the step it costs a second launch on the
-    // dependency chain and takes the CUs the other stream would use: only worth it when clearly faster
-    if (sk_partial && bc.splitk > 1 && best_single < 1e29f && best > sk_gain * best_single) { bc = bc_single; best = best_single; }
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    it = g_tuner->table.emplace(key, IgemmChoice{bc.tile, bc.splitk}).first;
+    if (!g_tuner->tuning) return plan_and_run(p, kind, nchw, 0, stream);
+    IgemmChoice best;
+    TRY(tune_shape(p, kind, nchw, stream, &best));
+    it = g_tuner->table.emplace(key, best).first;
   }
   p.splitk = it->second.splitk;
-  return launch_one(p, kind, nchw, it->second.tile, stream);
+  return plan_and_run(p, kind, nchw, it->second.tile, stream);
 }
 
 extern "C" int mmvqa_igemm(const mmvqa_gemm_desc* d, int kind, int nchw, int tile, mmvqa_stream_t s) {
@@ -2006,103 +1834,4 @@ extern "C" int mmvqa_igemm(const mmvqa_gemm_desc* d, int kind, int nchw, int til
   if (d->M <= 0 || d->N <= 0 || d->K <= 0)
     if (int r = validate_operands(*d, kind, nchw)) return r;
   return mmvqa_launch_igemm(*d, kind, nchw, tile, (hipStream_t)s);
-}
-
-// tile: 0 = auto, 1 = 128x128, 2 = 128x64, 3 = 64x64 (BK 64), 4 = 64x128, 5 = 64x64 with 8 waves (K-tile split in 2),
-//       6 = 64x64 with BK 32 (37 KB of LDS: four workgroups per CU for short contractions with many tiles)
-static int launch_one(GemmParams p, int kind, int nchw, int tile, hipStream_t stream) {
-  if (p.M <= 0 || p.N <= 0 || p.K <= 0) return MMVQA_OK;
-  if (p.g_KH <= 0) { p.g_KH = p.g_KW = 1; p.g_stride = 1; p.g_pad = 0; }
-  const bool s2c = s2c_eligible(p, kind, nchw);   // (a compact class has at most MAX_TAPS taps)
-  if (!nchw && p.g_KH * p.g_KW > MAX_TAPS && !s2c)
-    return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: at most %d taps in the NHWC gather", MAX_TAPS);
-  // 32-bit element offsets inside the loaders
-  if ((double)p.M * p.a_ld > 2.0e9 && kind != KIND_WGRAD)
-    return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: operand A exceeds 2^31 elements");
-  if (tile == 0) {
-    // enough workgroups to fill 256 CUs (2 resident per CU) before growing the tile
-    long t128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128);
-    long t12864 = (long)cdiv(p.M, 128) * cdiv(p.N, 64);
-    if (t128 >= 384) tile = 1;
-    else if (t12864 >= 384 || (p.N <= 64 && p.M >= 4096)) tile = 2;
-    else tile = 3;
-    // few workgroups and a long contraction: 8 waves per workgroup (two per SIMD)
-    if (tile == 3 && kind != KIND_WGRAD && (long)cdiv(p.M, 64) * cdiv(p.N, 64) < 400 && p.K >= 512) tile = 5;
-  }
-  if (nchw) tile = (kind == KIND_FWD) ? 2 : 3;
-  const bool f16 = p.reserved0 == MMVQA_PREC_F16;
-  if (f16 && tile == 5) tile = 3;   // the f16 family has no 8-wave variant
-  const int bm = (tile == 1 || tile == 2) ? 128 : 64;
-  const int bn = (tile == 1 || tile == 4) ? 128 : 64;
-  const int bk = ((tile == 3 || tile == 5) && !nchw) ? 64 : 32;
-  const int nkt = cdiv(p.K, bk);
-  if (p.splitk <= 0) {
-    p.splitk = 1;
-    if (kind == KIND_WGRAD) {
-      long tiles = (long)cdiv(p.M, bm) * cdiv(p.N, bn);
-      int want = (int)((512 + tiles - 1) / tiles);
-      int per = bk == 64 ? 2 : 4;                      // at least 128 rows of K per split
-      int maxs = nkt / per > 0 ? nkt / per : 1;
-      p.splitk = want < maxs ? want : maxs;
-      if (p.splitk < 1) p.splitk = 1;
-      if (p.splitk > 1) p.c_atomic = 1;
-    } else if (!nchw && sk_eligible(p, kind)) {
-      // untuned default: fill the chip when the tile grid is small and every split keeps >= 256 of K
-      const long tiles = (long)cdiv(p.M, bm) * cdiv(p.N, bn);
-      if (tiles <= 128 && p.K >= 1024) {
-        int want = (int)((256 + tiles - 1) / tiles);
-        const int maxs = p.K / 256;
-        if (want > maxs) want = maxs;
-        if (want > 8) want = 8;
-        if (want > 1) p.splitk = want;
-      }
-    }
-  }
-  if (kind != KIND_WGRAD && !nchw && p.splitk > 1 && !p.c_atomic) {
-    if (!sk_eligible(p, kind))
-      return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: split-K needs an accumulating epilogue or a scratch (sk_ws)");
-    const long long cap = p.sk_ws_floats / ((long long)p.M * p.N);
-    if (p.splitk > cap) p.splitk = (int)(cap < 1 ? 1 : cap);
-    if (p.splitk > SK_MAX) p.splitk = SK_MAX;
-  }
-  p.ktiles_per_split = cdiv(nkt, p.splitk);
-  p.splitk = cdiv(nkt, p.ktiles_per_split);
-  if (p.splitk > 1 && !p.c_atomic && !(kind != KIND_WGRAD && !nchw && sk_eligible(p, kind)))
-    return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: split-K needs an accumulating epilogue");
-#define GO(BM_, BN_, BK_)                                                                                          \
-  do {                                                                                                             \
-    if (f16) {                                                                                                     \
-      if (kind == KIND_FWD) return launch_cfg<BM_, BN_, BK_, KIND_FWD, false, 1, MMVQA_PREC_F16>(p, stream);     \
-      if (kind == KIND_DGRAD) return launch_cfg<BM_, BN_, BK_, KIND_DGRAD, false, 1, MMVQA_PREC_F16>(p, stream); \
-      return launch_cfg<BM_, BN_, BK_, KIND_WGRAD, false, 1, MMVQA_PREC_F16>(p, stream);                         \
-    }                                                                                                              \
-    if (kind == KIND_FWD) return launch_cfg<BM_, BN_, BK_, KIND_FWD, false>(p, stream);                            \
-    if (kind == KIND_DGRAD && s2c) return launch_cfg<BM_, BN_, BK_, KIND_DGRAD, false, 1, MMVQA_PREC_F32, true>(p, stream); \
-    if (kind == KIND_DGRAD) return launch_cfg<BM_, BN_, BK_, KIND_DGRAD, false>(p, stream);                        \
-    return launch_cfg<BM_, BN_, BK_, KIND_WGRAD, false>(p, stream);                                                \
-  } while (0)
-  if (nchw && f16) {
-    if (kind == KIND_FWD) return launch_cfg<128, 64, 32, KIND_FWD, true, 1, MMVQA_PREC_F16>(p, stream);
-    if (kind == KIND_WGRAD) return launch_cfg<64, 64, 32, KIND_WGRAD, true, 1, MMVQA_PREC_F16>(p, stream);
-    return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: no NCHW dgrad");
-  }
-  if (nchw) {
-    if (kind == KIND_FWD) return launch_cfg<128, 64, 32, KIND_FWD, true>(p, stream);
-    if (kind == KIND_WGRAD) return launch_cfg<64, 64, 32, KIND_WGRAD, true>(p, stream);
-    return mmvqa_set_error(MMVQA_ERR_ARG, "igemm: no NCHW dgrad");
-  }
-  switch (tile) {
-    case 1: GO(128, 128, 32);
-    case 2: GO(128, 64, 32);
-    case 4: GO(64, 128, 32);
-    case 6: GO(64, 64, 32);
-    case 5:
-      if (kind == KIND_FWD) return launch_cfg<64, 64, 64, KIND_FWD, false, 2>(p, stream);
-      if (kind == KIND_DGRAD && s2c) return launch_cfg<64, 64, 64, KIND_DGRAD, false, 2, MMVQA_PREC_F32, true>(p, stream);
-      if (kind == KIND_DGRAD) return launch_cfg<64, 64, 64, KIND_DGRAD, false, 2>(p, stream);
-      return launch_cfg<64, 64, 64, KIND_WGRAD, false, 2>(p, stream);
-    default: GO(64, 64, 64);
-  }
-#undef GO
-  return MMVQA_OK;
 }

@@ -4,13 +4,15 @@
 // is what the ABI does not have: launchers with arguments the ABI twin lacks, plan-time predicates, engine-only kernels.
 #pragma once
 #include "common.h"
+#include "igemm_plan.h"
 
 #include <string>
 #include <unordered_map>
 #include <utility>
 
-// per-shape (tile, split-K) choices of the implicit-GEMM launcher; see igemm.hip
-struct IgemmChoice { int tile, splitk; };
+// per-shape (tile, split-K) choices of the implicit-GEMM launcher.  The launcher is three steps: validate_desc and
+// igemm_plan (igemm_plan.h: pure host code, every per-launch decision) and igemm_run (igemm.hip: looks the planned
+// instance up in one table and enqueues it).
 struct IgemmTuner {
   bool tuning = false;
   std::unordered_map<std::string, IgemmChoice> table;
