@@ -735,6 +735,33 @@ int mmvqa_gradcam(mmvqa_stream_t s, const float* A, const float* dA, int B, int 
 int mmvqa_engine_visual_tokens(mmvqa_engine* e, const float** vis);
 int mmvqa_engine_forward_tokens(mmvqa_engine* e, mmvqa_stream_t s, const float* vis, const long long* ids,
                                 const long long* seg, const long long* mask, float* logits, int logits_ld, float* feat);
+/* The visual-token cache: cache is one fp32 device array [N][K][num_vis][hidden] (N images, K
+ * views of each); idx / view are int32 DEVICE arrays [B] whose contents the caller has validated on the host
+ * (0 <= idx[b] < N, 0 <= view[b] < K): the kernels do not range-check them.
+ * mmvqa_tokens_gather: out[t][b][:] = cache[idx[b]][view[b]][t][:], out in the engine's [num_vis][B][hidden] layout.
+ * mmvqa_tokens_scatter: its inverse for ONE view (a host scalar) and distinct idx[b]: cache[idx[b]][view][t][:] = vis[t][b][:].
+ * MMVQA_ERR_ARG before any HIP call for a null pointer, hidden % 8 != 0 or hidden > 1024, B / N / K / num_vis < 1, a
+ * cache / out / vis that is not 16-byte aligned, a scalar view outside [0, K). */
+int mmvqa_tokens_gather(mmvqa_stream_t s, const float* cache, int N, int K, const int* idx, const int* view, float* out,
+                        int B, int hidden, int num_vis);
+int mmvqa_tokens_scatter(mmvqa_stream_t s, const float* vis, const int* idx, int view, float* cache, int N, int K, int B,
+                         int hidden, int num_vis);
+/* Training from the cache.  mmvqa_engine_forward_cached: mmvqa_tokens_gather straight into the workspace's visual tokens,
+ * then exactly the launches of mmvqa_engine_forward after the backbone (embedding, encoder, heads or the headless copy)
+ * with the same dropout probabilities and per-site seeds, so `training` and `seed` mean what they mean there.  fp32
+ * operands only (MMVQA_ERR_ARG in the f16 mode), ungrouped plan only (MMVQA_ERR_STATE).  The backbone's activations in
+ * the workspace are not those of the tokens: mmvqa_engine_backward and mmvqa_engine_backward_feature answer
+ * MMVQA_ERR_STATE after it, as after mmvqa_engine_forward_tokens.
+ * mmvqa_engine_backward_cached: valid only directly after mmvqa_engine_forward_cached (MMVQA_ERR_STATE otherwise): heads,
+ * encoder and embedding backward, accumulated into grads as mmvqa_engine_backward does; the gradient of the visual
+ * tokens is computed into the workspace and dropped.  The backbone's and the five taps' range of grads and every
+ * BatchNorm buffer are not written.  With a gradient callback, [enc_lo, n) and [0, emb_hi) are announced as in
+ * mmvqa_engine_backward and the backbone + taps range [emb_hi, enc_lo) as it stands: one partition, as always. */
+int mmvqa_engine_forward_cached(mmvqa_engine* e, mmvqa_stream_t s, const float* cache, int N, int K, const int* idx,
+                                const int* view, const long long* ids, const long long* seg, const long long* mask,
+                                float* logits, int logits_ld, float* feat, int training, uint32_t seed);
+int mmvqa_engine_backward_cached(mmvqa_engine* e, mmvqa_stream_t s, const float* dlogits, int dlogits_ld,
+                                 const float* dfeat);
 /* Attribution methods beyond Grad-CAM (vqamed2019/grad_cam.py:65-72), maps as in mmvqa_gradcam
  * (H * W <= 256, C % 4 == 0, C <= 4096, else MMVQA_ERR_ARG before any HIP call).
  * mmvqa_cam_weights: w [B][C] of method 0 (gradcam: mean_p dA, bit-equal to mmvqa_gradcam's own), 1 (gradcam++:

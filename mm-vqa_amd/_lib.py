@@ -269,6 +269,10 @@ SIGNATURES = {
     "mmvqa_gradcam": (_i, [_P, _P, _P, _i, _i, _i, _i, _P, _P, _P, _i, _i, _P, _P, _f, _P]),
     "mmvqa_engine_visual_tokens": (_i, [_P, C.POINTER(_P)]),
     "mmvqa_engine_forward_tokens": (_i, [_P, _P, _P, _P, _P, _P, _P, _i, _P]),
+    "mmvqa_tokens_gather": (_i, [_P, _P, _i, _i, _P, _P, _P, _i, _i, _i]),
+    "mmvqa_tokens_scatter": (_i, [_P, _P, _P, _i, _P, _i, _i, _i, _i, _i]),
+    "mmvqa_engine_forward_cached": (_i, [_P, _P, _P, _i, _i, _P, _P, _P, _P, _P, _P, _i, _P, _i, _u32]),
+    "mmvqa_engine_backward_cached": (_i, [_P, _P, _P, _i, _P]),
     "mmvqa_cam_weights": (_i, [_P, _i, _P, _P, _i, _i, _i, _i, _P]),
     "mmvqa_cam_from_weights": (_i, [_P, _P, _P, _P, _i, _i, _i, _i, _P, _P, _P, _i, _i, _P, _P, _f, _P]),
     "mmvqa_eigencam_raw": (_i, [_P, _P, _i, _i, _i, _i, _P, _P, _P]),

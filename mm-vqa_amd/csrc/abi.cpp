@@ -69,6 +69,7 @@ int mmvqa_engine_bind(mmvqa_engine* e, float* params, float* grads, float* bufs,
   e->bound = true;
   e->img = nullptr;
   e->tokens_only = false;
+  e->cached = false;
   return MMVQA_OK;
 }
 int mmvqa_engine_forward(mmvqa_engine* e, mmvqa_stream_t s, const float* img, const long long* ids,
@@ -105,6 +106,18 @@ int mmvqa_engine_forward_tokens(mmvqa_engine* e, mmvqa_stream_t s, const float* 
                                 const long long* seg, const long long* mask, float* logits, int logits_ld, float* feat) {
   if (!e || !vis || !ids || !seg || !mask || !logits) return mmvqa_set_error(MMVQA_ERR_ARG, "forward_tokens: null pointer");
   return engine_forward_tokens(e, ST(s), vis, ids, seg, mask, logits, logits_ld, feat);
+}
+int mmvqa_engine_forward_cached(mmvqa_engine* e, mmvqa_stream_t s, const float* cache, int N, int K, const int* idx,
+                                const int* view, const long long* ids, const long long* seg, const long long* mask,
+                                float* logits, int logits_ld, float* feat, int training, uint32_t seed) {
+  if (!e || !cache || !idx || !view || !ids || !seg || !mask || !logits)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "forward_cached: null pointer");
+  return engine_forward_cached(e, ST(s), cache, N, K, idx, view, ids, seg, mask, logits, logits_ld, feat, training, seed);
+}
+int mmvqa_engine_backward_cached(mmvqa_engine* e, mmvqa_stream_t s, const float* dlogits, int dlogits_ld,
+                                 const float* dfeat) {
+  if (!e || !dlogits) return mmvqa_set_error(MMVQA_ERR_ARG, "backward_cached: null pointer");
+  return engine_backward_cached(e, ST(s), dlogits, dlogits_ld, dfeat);
 }
 int mmvqa_engine_set_grad_callback(mmvqa_engine* e, mmvqa_grad_cb cb, void* user) {
   if (!e) return mmvqa_set_error(MMVQA_ERR_ARG, "set_grad_callback: null engine");

@@ -1948,7 +1948,7 @@ int engine_forward(mmvqa_engine* e, hipStream_t st, const float* img, const long
                            d.head_kind == 2 ? "hidden" : "n_classes", out_w);
   e->img = img; e->ids = ids; e->seg = seg; e->mask = mask;
   e->logits = logits; e->logits_ld = logits_ld; e->feat = feat;
-  e->training = training; e->seed = seed; e->tokens_only = false;
+  e->training = training; e->seed = seed; e->tokens_only = false; e->cached = false;
   e->frozen = e->frozen_next;
   // `training` means dropout everywhere and batch statistics in the backbone's BatchNorms; the two part only under
   // MMVQA_FREEZE_BN_STATS (backbone.eval() inside model.train())
@@ -2009,7 +2009,7 @@ int engine_forward_tokens(mmvqa_engine* e, hipStream_t st, const float* vis, con
     return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward_tokens: logits_ld=%d must be >= %s=%d and %%4==0", logits_ld,
                            d.head_kind == 2 ? "hidden" : "n_classes", out_w);
   TRY(prepare_workspace(e, st));
-  e->img = nullptr; e->tokens_only = true;   // no backward of any kind after this forward
+  e->img = nullptr; e->tokens_only = true; e->cached = false;   // no backward of any kind after this forward
   e->ids = ids; e->seg = seg; e->mask = mask;
   e->logits = logits; e->logits_ld = logits_ld; e->feat = feat;
   e->training = 0; e->bn_training = 0; e->seed = 0;
@@ -2028,6 +2028,91 @@ int engine_forward_tokens(mmvqa_engine* e, hipStream_t st, const float* vis, con
   if (d.head_kind == 2)
     return copy_rows(st, logits, (size_t)logits_ld, h, (size_t)d.hidden, (size_t)e->B * e->T, (size_t)d.hidden);
   return heads_forward(e, st, h);
+}
+
+// The forward of a training step from the token cache: the gather writes the workspace's visual
+// tokens, then exactly the launches of engine_forward after the backbone, with its dropout probabilities and site seeds.
+// Like engine_forward_tokens it leaves the backbone's activations foreign to these tokens (tokens_only: engine_backward and
+// engine_backward_feature refuse); unlike it, it keeps `training` and allows engine_backward_cached.
+int engine_forward_cached(mmvqa_engine* e, hipStream_t st, const float* cache, int N, int K, const int* idx, const int* view,
+                          const long long* ids, const long long* seg, const long long* mask, float* logits, int logits_ld,
+                          float* feat, int training, uint32_t seed) {
+  if (e->prec != MMVQA_PREC_F32)
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward_cached: runs with fp32 operands, not in the f16 operand mode");
+  if (!e->planned || !e->bound) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_forward_cached: plan/bind first");
+  if (e->grouped) return mmvqa_set_error(MMVQA_ERR_STATE, "engine_forward_cached: the plan is grouped; plan again with mmvqa_engine_plan");
+  const mmvqa_model_desc& d = e->d;
+  const int out_w = d.head_kind == 2 ? d.hidden : d.n_classes;
+  if (logits_ld < out_w || (logits_ld & 3))
+    return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward_cached: logits_ld=%d must be >= %s=%d and %%4==0", logits_ld,
+                           d.head_kind == 2 ? "hidden" : "n_classes", out_w);
+  if (N < 1 || K < 1) return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward_cached: N=%d K=%d must both be at least 1", N, K);
+  if ((uintptr_t)cache & 15) return mmvqa_set_error(MMVQA_ERR_ARG, "engine_forward_cached: cache must be 16-byte aligned");
+  TRY(prepare_workspace(e, st));
+  e->img = nullptr; e->tokens_only = true; e->cached = false;   // (cached: set once every launch below is queued)
+  e->ids = ids; e->seg = seg; e->mask = mask;
+  e->logits = logits; e->logits_ld = logits_ld; e->feat = feat;
+  e->training = training; e->bn_training = 0; e->seed = seed;
+  StepScope scope(e, MMVQA_PREC_F32);
+  // (the gather belongs to none of the profiler's regions: the regions above the tokens count what they count in a full
+  // step; tools/cached_bench.py times it alone)
+  TRY(mmvqa_tokens_gather(st, cache, N, K, idx, view, WS(e->vis), e->B, d.hidden, d.num_vis));
+  const float pe = training ? d.p_emb_drop : 0.f;
+  e->prof_reg = REG_EMBED;
+  RUN(PROF_OTHER, 0,
+      mmvqa_embed_fwd(st, ids, seg, PRM(e->emb_word), PRM(e->emb_pos), PRM(e->emb_type), PRM(e->emb_ln.g),
+                  PRM(e->emb_ln.b), WS(e->vis), WS(e->emb_out), WS(e->emb_xhat), WS(e->emb_rstd), e->B, e->T,
+                  d.hidden, d.num_vis, 1e-12f, pe, site_seed(e, 100, 0)));
+  e->prof_reg = REG_BACKBONE;
+  const float* h = nullptr;
+  TRY(encoder_forward(e, st, &h));
+  e->enc_out_final = (size_t)(h - e->ws);
+  if (d.head_kind == 2)
+    TRY(copy_rows(st, logits, (size_t)logits_ld, h, (size_t)d.hidden, (size_t)e->B * e->T, (size_t)d.hidden));
+  else
+    TRY(heads_forward(e, st, h));
+  e->cached = true;
+  return MMVQA_OK;
+}
+
+// The backward of engine_forward_cached: engine_backward up to and including the embedding, then nothing.  The gradient of
+// the visual tokens lands in the workspace and is dropped; the backbone + taps range [emb_hi, enc_lo) of the gradient
+// buffer is announced as it stands (as frozen_backbone_backward announces the backbone), so every range is announced once.
+int engine_backward_cached(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, const float* dfeat) {
+  if (!e->planned || !e->bound || !e->cached)
+    return mmvqa_set_error(MMVQA_ERR_STATE, "engine_backward_cached: run mmvqa_engine_forward_cached first");
+  const mmvqa_model_desc& d = e->d;
+  StepScope scope(e, MMVQA_PREC_F32);
+  const float* h = WS(e->enc_out_final);
+  SideCtx sc_enc(e, st);
+  SideReads sr(sc_enc);
+  if (d.head_kind == 2) {
+    if (dl_ld < d.hidden)
+      return mmvqa_set_error(MMVQA_ERR_ARG, "engine_backward_cached: dlogits_ld=%d < hidden=%d", dl_ld, d.hidden);
+    TRY(copy_rows(st, WS(e->t_a), (size_t)d.hidden, dlogits, (size_t)dl_ld, (size_t)e->B * e->T, (size_t)d.hidden));
+  } else {
+    TRY(heads_backward(e, st, h, dlogits, dl_ld, dfeat, sr));
+  }
+  TRY(encoder_backward(e, st, sr));
+  if (e->grad_cb) {
+    TRY(sr.join());   // the weight gradients of the range may still be queued on the side stream
+    e->grad_cb(e->grad_cb_user, e->enc_lo, e->n_params);   // heads + encoder gradients are final
+  }
+  const float pe = e->training ? d.p_emb_drop : 0.f;
+  e->prof_reg = REG_EMBED;
+  RUN(PROF_OTHER, 0,
+      mmvqa_embed_bwd(st, WS(e->t_a), e->ids, e->seg, WS(e->emb_xhat), WS(e->emb_rstd), PRM(e->emb_ln.g),
+                  GRD(e->emb_word), GRD(e->emb_pos), GRD(e->emb_type), GRD(e->emb_ln.g), GRD(e->emb_ln.b),
+                  WS(e->dvis), e->B, e->T, d.hidden, d.num_vis, pe, site_seed(e, 100, 0), 0));
+  e->prof_reg = REG_BACKBONE;
+  // nothing follows that would join the side stream (engine_backward's backbone does): whatever comes after this
+  // backward (Adam, a reduction) sees the weight gradients; the embedding backward above ran beside the last of them
+  TRY(sr.join());
+  if (e->grad_cb) {
+    e->grad_cb(e->grad_cb_user, 0, e->emb_hi);            // embedding tables + LayerNorm
+    e->grad_cb(e->grad_cb_user, e->emb_hi, e->enc_lo);    // backbone and taps, as they stand: this backward wrote none of it
+  }
+  return MMVQA_OK;
 }
 
 int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, const float* dfeat) {

@@ -165,6 +165,7 @@ struct mmvqa_engine {
   const long long *ids = nullptr, *seg = nullptr, *mask = nullptr;
   const float* img = nullptr;
   bool tokens_only = false;   // the last forward was engine_forward_tokens: the backbone's activations are not its own
+  bool cached = false;        // ... or engine_forward_cached (tokens_only is set too): engine_backward_cached may follow
   int training = 0;      // dropout (and everything else outside the backbone's BatchNorms) of the last forward
   int bn_training = 0;   // the backbone's BatchNorms used batch statistics: = training unless MMVQA_FREEZE_BN_STATS
   int frozen = 0;        // MMVQA_FREEZE_* of the last forward: its backward reads them here
@@ -222,6 +223,10 @@ int engine_backward(mmvqa_engine* e, hipStream_t st, const float* dlogits, int d
 int engine_visual_tokens(mmvqa_engine* e, const float** vis);
 int engine_forward_tokens(mmvqa_engine* e, hipStream_t st, const float* vis, const long long* ids, const long long* seg,
                           const long long* mask, float* logits, int logits_ld, float* feat);
+int engine_forward_cached(mmvqa_engine* e, hipStream_t st, const float* cache, int N, int K, const int* idx, const int* view,
+                          const long long* ids, const long long* seg, const long long* mask, float* logits, int logits_ld,
+                          float* feat, int training, uint32_t seed);
+int engine_backward_cached(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, const float* dfeat);
 int engine_backward_feature(mmvqa_engine* e, hipStream_t st, const float* dlogits, int dl_ld, float* dA);
 int engine_feature_map(mmvqa_engine* e, const float** A, int* H, int* W, int* C);
 int engine_profile_collect(mmvqa_engine* e);

@@ -673,6 +673,73 @@ def collate_grouped(items):
     return out
 
 
+# --------------------------------------------------------------------------- cached visual tokens
+def image_of_rows(rows):
+    """-> (image paths in first-appearance order, image index of every table row): the index <-> table-row map of a
+    token cache over data.vqa_tables rows (row r asks about image image_of[r]; group_rows_by_image's numbering)"""
+    images = group_rows_by_image(rows)
+    image_of = [0] * len(rows)
+    for i, (_, idx) in enumerate(images):
+        for r in idx:
+            image_of[r] = i
+    return [p for p, _ in images], image_of
+
+
+class VqaImageDataset(torch.utils.data.Dataset):
+    """The distinct images of a VQA table, for the fill of a token cache: item (epoch, i) -> image i decoded, in the item
+    layout `collate` packs, with one-token dummy text (the fill runs the backbone alone) and index = i, the row of the
+    cache the image's tokens go to."""
+
+    def __init__(self, rows):
+        self.paths, self.image_of = image_of_rows(rows)
+
+    def __len__(self):
+        return len(self.paths)
+
+    def __getitem__(self, key):
+        _epoch, i = key
+        z = torch.zeros(1, dtype=torch.long)
+        return decode(self.paths[i]), z, z, z, torch.tensor(0, dtype=torch.long), i
+
+
+class VqaTextDataset(torch.utils.data.Dataset):
+    """VqaDataset without its images, for steps from a token cache: item (epoch, row) -> (ids, seg, mask, answer index,
+    image index, row[, category id]).  Nothing is decoded: the workers tokenise only.  image index is image_of_rows'
+    numbering, the one VqaImageDataset fills the cache in.  categories as VqaDataset's."""
+
+    def __init__(self, rows, tokenizer, max_position_embeddings=28, categories=None):
+        self.rows, self.tok, self.T = list(rows), tokenizer, max_position_embeddings
+        self.paths, self.image_of = image_of_rows(self.rows)
+        self.categories = None if categories is None else dict(categories)
+        if self.categories is not None:
+            missing = sorted({r[3] for r in self.rows} - set(self.categories))
+            if missing:
+                raise ValueError(f"VqaTextDataset: categories {missing} of the rows are not in the category map")
+        self.collate = collate_text
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __getitem__(self, key):
+        _epoch, idx = key
+        _path, question, ans = self.rows[idx][:3]
+        ids, seg, mask = (torch.tensor(v, dtype=torch.long) for v in text.encode_text_vqa(question, self.tok, self.T))
+        item = ids, seg, mask, torch.tensor(ans, dtype=torch.long), self.image_of[idx], idx
+        return item if self.categories is None else item + (self.categories[self.rows[idx][3]],)
+
+
+def collate_text(items):
+    """VqaTextDataset items -> dict: ids / seg / mask [B, T], target [B], image [B] int64 (cache rows, stays on the
+    host), index [B] (table rows) and, where the items carry it, category [B]"""
+    out = dict(ids=torch.stack([it[0] for it in items]), seg=torch.stack([it[1] for it in items]),
+               mask=torch.stack([it[2] for it in items]), target=torch.stack([it[3] for it in items]),
+               image=torch.tensor([it[4] for it in items], dtype=torch.int64),
+               index=torch.tensor([it[5] for it in items], dtype=torch.int64))
+    if len(items[0]) > 6:
+        out["category"] = torch.tensor([it[6] for it in items], dtype=torch.int64)
+    return out
+
+
 def collate_supcon(items):
     """RocoSupConDataset items -> collate's dict with n images and the text already in process_tensors' layout
     (supcon_utils.py:253-256): ids = (captions; translations), target = (caption targets; translation targets),
@@ -902,6 +969,31 @@ class HostLoader:
                 params = sample_params(self.views * n, self.size, generator=batch_generator(self.seed, epoch, b, self.rank),
                                        **self.aug)
             yield batch, params, dict(epoch=epoch, batch=b)
+
+
+def view_params(seed, image, view, size, aug):
+    """the training-augmentation parameters of view `view` >= 1 of cache image `image`: a function of (seed, image,
+    view) alone, whatever batch the image is filled in"""
+    g = torch.Generator().manual_seed(mix_seed(seed, image, view, 0x746F6B))
+    return sample_params(1, size, generator=g, **aug)[0]
+
+
+class ViewLoader(HostLoader):
+    """HostLoader over a VqaImageDataset in file order for the fill of one view of a token cache: view 0 carries no
+    augment parameters (the feeder applies the evaluation transform), view v >= 1 carries view_params(seed, i, v) for
+    every image i of the batch -- not a draw from the batch's generator, so a view does not depend on the batch size."""
+
+    def __init__(self, dataset, batch_size, view, seed=0, num_workers=None, aug=None, size=224):
+        super().__init__(dataset, batch_size, shuffle=False, seed=seed, num_workers=num_workers,
+                         aug=aug if view else None, size=size)
+        self.view = int(view)
+
+    def __iter__(self):
+        for b, batch in enumerate(self.loader):
+            params = None
+            if self.aug is not None:
+                params = [view_params(self.seed, i, self.view, self.size, self.aug) for i in batch["index"].tolist()]
+            yield batch, params, dict(epoch=self.view, batch=b)
 
 
 def low_priority_stream(device):

@@ -152,6 +152,51 @@ class _GroupedModelFn(torch.autograd.Function):
         return (None,) * 9
 
 
+class _CachedModelFn(torch.autograd.Function):
+    """_ModelFn for a step from the token cache: `maps` is the device copy of index | view (cached_maps)"""
+
+    @staticmethod
+    def forward(ctx, model, anchor, tokens, maps, ids, seg, mask, frozen):
+        ctx.model = model
+        ctx.frozen = frozen
+        return model._engine_forward_cached(tokens, maps, ids, seg, mask)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        ctx.model._engine_backward_cached(*grads, frozen=ctx.frozen)
+        return (None,) * 8
+
+
+def _host_ints(what, values):
+    """a host integer tensor or sequence -> list of int; ValueError for a device tensor, a float, a bool"""
+    if isinstance(values, torch.Tensor):
+        if values.is_cuda:
+            raise ValueError(f"{what} must be a host tensor or a sequence: it is validated before anything is launched")
+        if values.dtype.is_floating_point or values.dtype == torch.bool or values.dim() != 1:
+            raise ValueError(f"{what} must be a 1-d integer tensor, not {values.dtype} with shape {tuple(values.shape)}")
+        return [int(v) for v in values.tolist()]
+    out = list(values)
+    for b, v in enumerate(out):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) and not hasattr(v, "__index__") or int(v) != v:
+            raise ValueError(f"{what} must hold integers, not {v!r} at position {b}")
+    return [int(v) for v in out]
+
+
+def cached_maps(index, view, n_images: int, n_views: int, n_rows: int):
+    """Validates the (image, view) choice of a step from a TokenCache on the host and returns one int32 CPU tensor
+    [2 * n_rows]: index, then view.  Both are host integer tensors or sequences of length n_rows with
+    0 <= index[b] < n_images and 0 <= view[b] < n_views; ValueError names the first offending position otherwise.  The
+    kernels that read them do not check ranges."""
+    idx, vw = _host_ints("index", index), _host_ints("view", view)
+    for what, vals, bound, of in (("index", idx, n_images, "images"), ("view", vw, n_views, "views")):
+        if len(vals) != n_rows:
+            raise ValueError(f"{what} has {len(vals)} entries for {n_rows} rows")
+        for b, v in enumerate(vals):
+            if not 0 <= v < bound:
+                raise ValueError(f"{what}[{b}] = {v} is outside the cache's {bound} {of} (0 .. {bound - 1})")
+    return torch.tensor(idx + vw, dtype=torch.int32)
+
+
 def group_maps(group, n_images: int, n_rows: int):
     """Validates the image-of-question map of a grouped batch on the host and returns one int32 CPU tensor
     [n_rows + n_images + 1]: group, then offsets (the questions of image i are rows offsets[i] .. offsets[i+1]-1).
@@ -468,6 +513,28 @@ class Model(nn.Module):
         self._bn_stats_running = False
         return self
 
+    def freeze_visual(self):
+        """freeze_backbone(bn_stats="running") extended to the five tap convolutions: requires_grad_(False) on every
+        parameter under transformer.trans., the state in which an image's visual tokens depend on the image alone
+        (tokens.TokenCache).  The taps cannot train from cached tokens: their activation sits between the 1x1
+        convolution and the pooling, so the token is not a function of anything a cache could hold short of the whole
+        feature map."""
+        for name, p in self._params_by_name.items():
+            if name.startswith("transformer.trans."):
+                p.requires_grad_(False)
+                p.grad = None
+        self._bn_stats_running = True
+        return self
+
+    def unfreeze_visual(self):
+        """undoes freeze_visual (and freeze_backbone): every parameter under transformer.trans. requires a gradient again
+        and the backbone's BatchNorms are back on batch statistics.  unfreeze_backbone alone leaves the taps frozen."""
+        for name, p in self._params_by_name.items():
+            if name.startswith("transformer.trans."):
+                p.requires_grad_(True)
+        self._bn_stats_running = False
+        return self
+
     # ------------------------------------------------------------------ engine calls
     def _ensure_plan(self, B, T, IH, IW, NI=None):
         """NI: the images of a grouped batch (forward_grouped); None: the ungrouped plan, one image per row"""
@@ -626,6 +693,11 @@ class Model(nn.Module):
         if torch.is_autocast_enabled("cuda"):
             raise NotImplementedError("visual tokens (visual_tokens / forward_tokens) are fp32 in this version: call it "
                                       "outside torch.autocast")
+        self._run_backbone_eval(img)
+        return self._read_visual_tokens(img.shape[0])
+
+    def _run_backbone_eval(self, img):
+        """visual_tokens' forward: afterwards the tokens of `img` are in the workspace (mmvqa_engine_visual_tokens)"""
         B = img.shape[0]
         T = self._desc.num_vis + 2
         ids = torch.zeros(B, T, dtype=torch.long, device=img.device)
@@ -638,7 +710,6 @@ class Model(nn.Module):
         finally:
             self.train(was_training)
             self._seed_ctr = seed_ctr                                        # an eval forward draws nothing: later training steps see the same stream
-        return self._read_visual_tokens(B)
 
     def _read_visual_tokens(self, B):
         """the tokens the last forward left in the workspace, copied out as [B, num_vis, hidden]"""
@@ -689,6 +760,107 @@ class Model(nn.Module):
         if self.dataset == "VQA-Med":
             return out, 0, 0
         return out
+
+    # ------------------------------------------------------------------ training from cached visual tokens
+    def token_range(self):
+        """[lo, hi) of the flat parameter / gradient buffers that holds transformer.trans.*: the CNN body and the five tap
+        convolutions, everything in front of the visual tokens (the engine's [emb_hi, enc_lo))"""
+        rows = [(lo, hi) for name, _, lo, hi in self._param_ranges() if name.startswith("transformer.trans.")]
+        lo, hi = min(r[0] for r in rows), max(r[1] for r in rows)
+        assert sum(h - l for l, h in rows) == hi - lo, "transformer.trans.* is one contiguous range of the engine's layout"
+        return lo, hi
+
+    def forward_cached(self, cache, index, view, input_ids, segment_ids, input_mask):
+        """forward for a batch whose visual tokens come from a tokens.TokenCache instead of the backbone: row b reads
+        cache.tokens[index[b], view[b]].  Returns the same tuple as forward, honours self.training (dropout with the
+        probabilities and the stream of forward: the same seed gives the same masks) and advances the dropout counter
+        as forward does.  With grad enabled, backward reaches the heads, the encoder and the embeddings; parameters
+        under transformer.trans. (backbone and taps) receive nothing: their .grad and their range of flat_grads are
+        untouched, and no BatchNorm buffer is written.  Every other parameter behaves as under forward.
+
+        index / view are HOST integer tensors or sequences of length B, validated before anything is launched
+        (ValueError names the offending position) and uploaded from pinned memory without waiting for the device.
+        fp32 only (NotImplementedError inside torch.autocast)."""
+        if torch.is_autocast_enabled("cuda"):
+            raise NotImplementedError("visual tokens (visual_tokens / forward_tokens) are fp32 in this version: call it "
+                                      "outside torch.autocast")
+        d = self._desc
+        ids = input_ids
+        if ids.dim() != 2:
+            raise ValueError(f"forward_cached takes input_ids [B, T], not {tuple(ids.shape)}")
+        tokens = cache.tokens
+        if tuple(tokens.shape[2:]) != (d.num_vis, d.hidden):
+            raise ValueError(f"the cache holds tokens of [{tokens.shape[2]}, {tokens.shape[3]}], the model's are "
+                             f"[{d.num_vis}, {d.hidden}]")
+        maps = cached_maps(index, view, tokens.shape[0], tokens.shape[1], ids.shape[0])
+        self._refuse_after_grouped("forward_cached")
+        if not (tokens.is_cuda and ids.is_cuda):
+            raise L.MMVQAError("mm-vqa_amd runs on the GPU only: move the model and inputs to 'cuda' "
+                               "(there is no CPU fallback by design)")
+        pinned = torch.empty(maps.numel(), dtype=torch.int32, pin_memory=True)   # (the caching host allocator: no
+        pinned.copy_(maps)                                                       # allocation after the first steps)
+        maps = pinned.to(tokens.device, non_blocking=True)                       # index and view go up in one copy
+        frozen = self._frozen_state() if torch.is_grad_enabled() else _NOT_FROZEN
+        out = _CachedModelFn.apply(self, self._anchor, tokens, maps, input_ids, segment_ids, input_mask, frozen)
+        if self.dataset == "VQA-Med":
+            return out, 0, 0
+        return out
+
+    def _engine_forward_cached(self, tokens, maps, ids, seg, mask):
+        d = self._desc
+        ids, seg, mask = (t.contiguous().long() for t in (ids, seg, mask))
+        B, T = ids.shape
+        if d.encoder == L.ENC_FEEDBACK and not 2 <= T <= L.FB_MAX_T:
+            raise ValueError(f"the feedback-transformer takes 2 <= T <= {L.FB_MAX_T} tokens, not T={T}")
+        self._ensure_plan(B, T, _TOKEN_PLAN_HW, _TOKEN_PLAN_HW)    # the backbone is not run: forward_tokens' layout
+        rows = B if d.head_kind == L.HEAD_VQA else B * T
+        V = d.hidden if d.head_kind == L.HEAD_NONE else d.n_classes
+        ld = (V + 3) & ~3
+        buf = torch.empty(rows, ld, dtype=torch.float32, device=ids.device)
+        if ld != V:
+            buf[:, V:].zero_()
+        feat = torch.empty(B, d.feat_dim, dtype=torch.float32, device=ids.device) if d.supcon else None
+        self._seed_ctr = (self._seed_ctr * 1103515245 + 12345) & 0x7FFFFFFF
+        N, K = tokens.shape[0], tokens.shape[1]
+        L.check(L.lib().mmvqa_engine_set_precision(self._handle, L.PREC_F32))
+        L.check(L.lib().mmvqa_engine_forward_cached(self._handle, L.stream_ptr(), L.ptr(tokens), N, K, L.ptr(maps),
+                                                    C.c_void_p(maps.data_ptr() + 4 * B), L.ptr(ids), L.ptr(seg),
+                                                    L.ptr(mask), L.ptr(buf), ld, L.ptr(feat), 1 if self.training else 0,
+                                                    self._seed_ctr))
+        self._fwd_state = (None, ids, seg, mask, rows, V, ld)
+        logits = buf[:, :V]
+        logits = logits.view(B, T, V) if d.head_kind != L.HEAD_VQA else logits
+        return (logits, feat) if d.supcon else logits
+
+    def _engine_backward_cached(self, dlogits, dfeat=None, frozen=_NOT_FROZEN):
+        _, ids, seg, mask, rows, V, ld = self._fwd_state
+        t_lo, t_hi = self.token_range()
+        live = [(n, p) for n, p in self._params_by_name.items()
+                if not n.startswith(_NEVER_USED) and not n.startswith("transformer.trans.") and p.requires_grad]
+        if live and live[0][1].grad is None:                    # zero_grad(set_to_none=True): everything this backward adds to
+            self._flat_grad[:t_lo].zero_()
+            self._flat_grad[t_hi:].zero_()
+        g = dlogits.reshape(rows, V) if dlogits.dim() == 3 else dlogits
+        if not (g.stride(1) == 1 and g.stride(0) % 4 == 0 and g.stride(0) >= ld and g.data_ptr() % 16 == 0):
+            pad = torch.zeros(rows, ld, dtype=torch.float32, device=g.device)
+            pad[:, :V] = g
+            g = pad
+        if dfeat is not None:
+            dfeat = dfeat.contiguous()
+        L.check(L.lib().mmvqa_engine_set_precision(self._handle, L.PREC_F32))
+        L.check(L.lib().mmvqa_engine_backward_cached(self._handle, L.stream_ptr(), L.ptr(g), g.stride(0), L.ptr(dfeat)))
+        if getattr(self, "_cb_error", None) is not None:
+            err, self._cb_error = self._cb_error, None
+            raise err
+        for lo, hi in frozen[1]:         # frozen outside transformer.trans.: computed, then discarded, as under forward
+            if lo < t_lo:
+                self._flat_grad[lo:min(hi, t_lo)].zero_()
+            if hi > t_hi:
+                self._flat_grad[max(lo, t_hi):hi].zero_()
+        shapes = {name: (shp, off, cl) for name, kind, shp, off, cl in self._table if kind == 0}
+        for name, p in live:
+            if p.grad is None:
+                p.grad = self._view(self._flat_grad, *shapes[name])
 
     def forward(self, img, input_ids, segment_ids, input_mask):
         """Inside torch.autocast("cuda", dtype=torch.float16) the forward and its backward run in the mixed-precision

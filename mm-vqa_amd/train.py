@@ -31,6 +31,8 @@ torch.distributed (RCCL).
     python -m mmvqa_amd.train vqa    --run_name r --loss ASLSingleLabel --batch_size 64
     python -m mmvqa_amd.train vqa    --run_name r --smoothing 0.1 --batch_size 64
     python -m mmvqa_amd.train vqa    --run_name r --group_by_image --batch_size 64     # each image once for its questions
+    python -m mmvqa_amd.train vqa    --run_name r --cache_tokens --cache_views 4       # frozen backbone: encode every image once
+    python -m mmvqa_amd.train vqa    --cache_tokens --cache_views 4 --data_dir VQA-Med --vocab_file vocab.txt
     python -m mmvqa_amd.train eval   --model_dir save/MLM/r.pt --num_classes 1552 --batch_size 16
     python -m mmvqa_amd.train mlm    --watch all --watch_freq 100     # per-tensor statistics -> save/watch_mlm.jsonl
     python -m mmvqa_amd.train vqa    --ema_decay 0.999 --ema_warmup   # validate and save the averaged weights
@@ -117,6 +119,17 @@ def common_args(p):
     p.add_argument("--freeze_backbone", action="store_true", help="the CNN body gets no gradient; its backward pass is not run")
     p.add_argument("--freeze_bn_stats", action="store_true",
                    help="with --freeze_backbone: its BatchNorms use and keep their running statistics (backbone.eval())")
+    p.add_argument("--cache_tokens", action="store_true", default=False,
+                   help="vqa: freeze the CNN body and the five taps, encode every image once into a device-resident "
+                        "cache of visual tokens (mmvqa_amd.tokens.TokenCache) and train the fusion encoder, the heads and "
+                        "the embeddings from it (Model.forward_cached): no image is touched after the fill.  Not with "
+                        "--mixed_precision, --group_by_image or more than one process")
+    p.add_argument("--cache_views", type=int, default=None, metavar="K",
+                   help="with --cache_tokens: K views per train image (default 1): view 0 is the evaluation transform, "
+                        "views 1..K-1 are draws of the training augmentation; every sample of a step takes one at random")
+    p.add_argument("--cache_images", type=int, default=None, metavar="N",
+                   help="with --cache_tokens and without --data_dir: the synthetic train set has N images (default 8 x "
+                        "--batch_size); with --data_dir the caches hold every distinct image of the train and validation tables")
     p.add_argument("--ema_decay", type=float, default=None, metavar="D",
                    help="mlm, supcon, distill, vqa: keep an exponential moving average of the weights, avg += (w - avg)(1 - D) "
                         "per optimizer step, in the launch that updates them (FusedAdam(ema_decay=)).  Every validation "
@@ -320,6 +333,8 @@ def build(args, ctx, n_classes=None):
     cs = sync_replicas(model)              # rank 0's replica everywhere, checksum compared across ranks
     if getattr(args, "freeze_backbone", False):
         model.freeze_backbone("running" if args.freeze_bn_stats else "batch")
+    if getattr(args, "cache_tokens", False):   # requires_grad = False: FusedAdam marks them ADAM_FROZEN, weight decay cannot move them
+        model.freeze_visual()
     opt = FusedAdam(model, **optimizer_groups(args))
     sched = lr_scheduler.ReduceLROnPlateau(_SchedShim(opt), patience=args.patience, factor=args.factor)
     red = GradReducer(model.flat_grads, bucket_mb=getattr(args, "bucket_mb", 64.0))
@@ -515,9 +530,12 @@ def supcon_step(model, opt, red, world, batch, words=None, teacher_T=None, bert_
     return loss, pred, stats
 
 
-def vqa_forward(model, batch, group=None):
+def vqa_forward(model, batch, group=None, cache=None):
     """logits of a VQA batch; group (--group_by_image): batch[0] holds each image once and group[b] names the image of
-    question b (Model.forward_grouped)"""
+    question b (Model.forward_grouped); cache (--cache_tokens): batch[0] is the host pair (index, view) into that
+    TokenCache instead of images (Model.forward_cached)"""
+    if cache is not None:
+        return model.forward_cached(cache, batch[0][0], batch[0][1], *batch[1:4])[0]
     if group is None:
         return model(*batch[:4])[0]                     # utils.py:646
     return model.forward_grouped(batch[0], group, *batch[1:4])[0]
@@ -534,7 +552,7 @@ def synthetic_vqa_grouped(args, ctx, seed, C, smooth=False):
     return (img, ids, seg, mask, tgt) + cat + (group,)
 
 
-def vqa_step(model, opt, red, world, batch, crit, clip=False, scaler=None, group=None, watch=None):
+def vqa_step(model, opt, red, world, batch, crit, clip=False, scaler=None, group=None, watch=None, cache=None):
     """vqamed2019/utils.py:633-673: logits, _, _ = model(...); loss = criterion(logits, target); backward;
     optional clip_grad_norm_(1.0) (:663-664); Adam; pred = softmax(1).argmax(1).
     With a scaler (--mixed_precision) the reference's sequence of utils.py:641-657: autocast
@@ -542,11 +560,12 @@ def vqa_step(model, opt, red, world, batch, crit, clip=False, scaler=None, group
     gradients; scaler.step then unscales them by 1/scale all the same (and skips on a non-finite gradient).
     A 6-tuple batch (--smoothing) ends with the category ids and the loss is criterion(logits, target, category)
     (utils.py:648-649; also under a scaler, where the reference's call at :644 lacks the argument and raises).
-    group: the step of --group_by_image (vqa_forward); `batch` is then without its last element, the group itself."""
+    group: the step of --group_by_image (vqa_forward); `batch` is then without its last element, the group itself.
+    cache: the step of --cache_tokens (vqa_forward); batch[0] is then (index, view) instead of images."""
     tgt = batch[4]
     opt.zero_grad()
     with torch.autocast("cuda", dtype=torch.float16, enabled=scaler is not None):
-        logits = vqa_forward(model, batch, group)
+        logits = vqa_forward(model, batch, group, cache)
         loss = crit(logits, tgt, batch[5]) if len(batch) == 6 else crit(logits, tgt)
     _update(loss, model, opt, red, world, scaler, scaled_backward=False, clip=clip, watch=watch)   # utils.py:651: the scaled loss is not used
     return loss, logits.detach().softmax(1).argmax(1)
@@ -814,6 +833,128 @@ def vqa_criterion(args, ctx, train_rows=None):
     return plain_criterion(args)
 
 
+class SyntheticTokenSource:
+    """--cache_tokens without --data_dir: a synthetic train set of --cache_images images and a validation set of
+    --val_steps x --batch_size, both from fixed seeds (chunks of --batch_size images, synth.vqa_batch), encoded once into
+    two TokenCaches.  View 0 of an image is the image as it stands (a synthetic image is already what the evaluation
+    transform hands out); view v >= 1 is DeviceAugment's training chain with VQA_AUG on the image's 8-bit pixels, its
+    parameters drawn per image from (seed, image, view) alone.  A train step draws --batch_size (image, question, answer)
+    triples from its seed and a view per sample from (seed, epoch, batch, rank); a validation batch is view 0 of the images
+    of the uncached synthetic validation batch of the same seed, with questions and answers drawn from that seed without
+    the images (other draws than the uncached batch's: its generator makes the images first)."""
+
+    def __init__(self, args, ctx, model, n_classes, smooth=False):
+        from .augment import DeviceAugment, sample_params
+        from .tokens import TokenCache
+        self.args, self.ctx, self.C, self.smooth = args, ctx, n_classes, smooth
+        B = args.batch_size
+        self.N = args.cache_images or 8 * B
+        self.K = args.cache_views or 1
+        self.train = TokenCache(model, self.N, self.K)
+        self.val = TokenCache(model, max(1, args.val_steps) * B, 1)
+        aug = DeviceAugment(size=args.image_size, train=True, device=ctx.dev, **D.VQA_AUG) if self.K > 1 else None
+        for lo in range(0, self.N, B):
+            n = min(B, self.N - lo)
+            img = self.images("train", lo, n)
+            self.train.fill(range(lo, lo + n), img.to(ctx.dev), 0)
+            if aug is None:
+                continue
+            pixels = list(self.pixels(img))
+            for v in range(1, self.K):
+                params = [sample_params(1, args.image_size, generator=torch.Generator().manual_seed(
+                    D.mix_seed(args.seed, lo + i, v, 0x746F6B)), **D.VQA_AUG)[0] for i in range(n)]
+                self.train.fill(range(lo, lo + n), aug(pixels, params=params), v)
+        for i in range(args.val_steps):
+            self.val.fill(range(i * B, (i + 1) * B), self.images("val", i * B, B).to(ctx.dev), 0)
+
+    def images(self, split, lo, n):
+        """images lo .. lo + n - 1 of a split (lo a multiple of --batch_size) -> fp32 [n, 3, S, S] on the host"""
+        a = self.args
+        seed = (a.seed + 15485863 + lo) if split == "train" else list(val_seeds(a))[lo // a.batch_size]
+        return synth.vqa_batch(n, a.max_position_embeddings, a.image_size, a.emb_vocab, self.C, seed=seed)[0]
+
+    @staticmethod
+    def pixels(img):
+        """fp32 [n, 3, S, S] in [-1, 1] -> uint8 [n, S, S, 3], what a decoder would hand to the augment"""
+        return ((img + 1.0) * 127.5).round().clamp(0, 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
+
+    def text(self, seed, smooth):
+        """(ids, seg, mask, target[, category]) of synth.vqa_batch at `seed`, on the device, without its images"""
+        a, dev = self.args, self.ctx.dev
+        out = synth.vqa_batch(a.batch_size, a.max_position_embeddings, 1, a.emb_vocab, self.C, seed=seed, device=dev)[1:]
+        return out + (synth.vqa_categories(a.batch_size, self.C, seed=seed, device=dev),) if smooth else out
+
+    def train_batches(self, epoch):
+        a, B = self.args, self.args.batch_size
+        for b, sd in enumerate(train_seeds(a, self.ctx, epoch)):
+            index = torch.randint(0, self.N, (B,), generator=torch.Generator().manual_seed(D.mix_seed(sd, 0x696478)))
+            view = torch.randint(0, self.K, (B,), generator=D.batch_generator(a.seed, epoch, b, self.ctx.rank))
+            yield ((index, view),) + self.text(sd, self.smooth)
+
+    def val_batches(self):
+        B = self.args.batch_size
+        for i, sd in enumerate(val_seeds(self.args)):     # validation is plain cross entropy: no category
+            yield ((torch.arange(i * B, (i + 1) * B), torch.zeros(B, dtype=torch.int64)),) + self.text(sd, False)
+
+    def check(self, model):
+        self.train.check(model)
+        if self.args.val_steps:                           # (--val_steps 0 fills no validation cache)
+            self.val.check(model)
+
+
+class TableTokenSource:
+    """--cache_tokens with --data_dir: the distinct images of the VQA-Med train and validation tables, encoded once into
+    two TokenCaches (row i = image i of data.image_of_rows), through the DeviceFeeder / DeviceAugment path in file order:
+    view 0 is the evaluation transform, view v >= 1 the training augmentation with data.view_params(seed, image, v).
+    After the fill no image is decoded: the worker processes tokenise only (data.VqaTextDataset), a batch carries the
+    cache rows of its questions on the host, and every sample of a train step takes a view drawn from
+    (seed, epoch, batch, rank).  Validation reads view 0 of its own cache in table order."""
+
+    def __init__(self, args, ctx, model, tok, tabs, categories=None):
+        from .tokens import TokenCache
+        self.args, self.ctx = args, ctx
+        self.K = args.cache_views or 1
+        T = args.max_position_embeddings
+        self.tr_ds = D.VqaTextDataset(tabs["train"], tok, T, categories=categories)
+        self.va_ds = D.VqaTextDataset(tabs["val"], tok, T)
+        self.train = TokenCache(model, len(self.tr_ds.paths), self.K)
+        self.val = TokenCache(model, len(self.va_ds.paths), 1)
+        for split, cache, views in (("train", self.train, self.K), ("val", self.val, 1)):
+            images = D.VqaImageDataset(tabs[split])
+            for v in range(views):
+                host = D.ViewLoader(images, args.batch_size, v, seed=args.seed, num_workers=args.num_workers, aug=D.VQA_AUG,
+                                    size=args.image_size)
+                fd = D.DeviceFeeder(host, ctx.dev, train=v > 0, depth=args.feeder_depth)
+                for batch in fd:
+                    cache.fill(fd.log[-1]["index"], batch[0], v)
+                del fd, host
+        loader = lambda ds, train: D.HostLoader(ds, args.batch_size, shuffle=train, seed=args.seed, rank=ctx.rank,   # noqa: E731
+                                                world=ctx.world, num_workers=args.num_workers, size=args.image_size)
+        self.tr_host, self.va_host = loader(self.tr_ds, True), loader(self.va_ds, False)
+
+    def _batches(self, host, epoch, views, category):
+        dev = self.ctx.dev
+        host.set_epoch(epoch)
+        for batch, _params, meta in host:
+            n = batch["image"].shape[0]
+            if views > 1:
+                view = torch.randint(0, views, (n,), generator=D.batch_generator(self.args.seed, epoch, meta["batch"], self.ctx.rank))
+            else:
+                view = torch.zeros(n, dtype=torch.int64)
+            out = ((batch["image"], view),) + tuple(batch[k].to(dev, non_blocking=True) for k in ("ids", "seg", "mask", "target"))
+            yield out + (batch["category"].to(dev, non_blocking=True),) if category else out
+
+    def train_batches(self, epoch):
+        return self._batches(self.tr_host, epoch, self.K, self.tr_ds.categories is not None)
+
+    def val_batches(self):
+        return self._batches(self.va_host, 0, 1, False)
+
+    def check(self, model):
+        self.train.check(model)
+        self.val.check(model)
+
+
 def run_vqa(args):
     ctx = Ctx(args)
     args.dataset, args.task = "VQA-Med", "MLM"
@@ -828,9 +969,10 @@ def run_vqa(args):
         args.num_classes = len(idx2ans)
         crit = vqa_criterion(args, ctx, tabs["train"])
         DS = D.VqaGroupedDataset if grouped else D.VqaDataset     # grouped: an item is an image with all of its questions
-        tr_ds = DS(tabs["train"], tok, args.max_position_embeddings, categories=crit.cat2idx if smooth else None)
-        tr_fd = feeder(args, ctx, tr_ds, True, D.VQA_AUG, category=smooth, grouped=grouped)
-        va_fd = feeder(args, ctx, DS(tabs["val"], tok, args.max_position_embeddings), False, grouped=grouped)
+        if not getattr(args, "cache_tokens", False):             # (--cache_tokens reads the tables itself, below)
+            tr_ds = DS(tabs["train"], tok, args.max_position_embeddings, categories=crit.cat2idx if smooth else None)
+            tr_fd = feeder(args, ctx, tr_ds, True, D.VQA_AUG, category=smooth, grouped=grouped)
+            va_fd = feeder(args, ctx, DS(tabs["val"], tok, args.max_position_embeddings), False, grouped=grouped)
     else:
         crit = vqa_criterion(args, ctx)
     C = args.num_classes
@@ -838,6 +980,7 @@ def run_vqa(args):
     scaler = GradScaler() if args.mixed_precision else None
     watch = make_watcher(args, ctx, "vqa", model)
     T, B = args.max_position_embeddings, args.batch_size
+    src = tr_cache = va_cache = None
 
     def synthetic_train(epoch):
         for sd in train_seeds(args, ctx, epoch):
@@ -849,29 +992,41 @@ def run_vqa(args):
 
     def val_value(batch):                               # utils.py:708-715, 673
         batch, group = split(batch)
-        logits = vqa_forward(model, batch, group)
+        logits = vqa_forward(model, batch, group, va_cache)
         return float(crit(logits, batch[4])), batch[4].shape[0], int((logits.softmax(1).argmax(1) == batch[4]).sum())
     # (vqamed2019/train.py itself has no recorder / --resume; kept here like the two pre-training loops)
     start, kept = maybe_resume(args, model, opt, sched, "vqa")
+    # --cache_tokens: batch[0] is (index, view) into a TokenCache, filled here, once, from the
+    # weights the run trains with (after --resume has loaded them)
+    if getattr(args, "cache_tokens", False):
+        if args.data_dir:
+            src = TableTokenSource(args, ctx, model, tok, tabs, crit.cat2idx if smooth else None)
+        else:
+            src = SyntheticTokenSource(args, ctx, model, C, smooth)
+        tr_cache, va_cache = src.train, src.val
     best_loss, best_acc1 = kept.get("best_loss", float("inf")), kept.get("best_acc1", 0.0)
     best_acc2, counter = kept.get("best_acc2", 0.0), kept.get("counter", 0)
     for epoch in range(start, args.epochs):
         model.train()
+        if src is not None:
+            src.check(model)    # a cache is only as good as the backbone it was filled from
         if smooth:
             crit.train()        # every epoch: the reference leaves the criterion in eval mode after its first validate
         tl, steps = 0.0, 0
         if watch is not None:
             watch.epoch = epoch
-        for batch in epoch_batches(tr_fd, epoch, synthetic_train(epoch)):
+        for batch in epoch_batches(tr_fd, epoch, synthetic_train(epoch) if src is None else src.train_batches(epoch)):
             batch, group = split(batch)
             loss, _ = vqa_step(model, opt, red, ctx.world, batch, crit, clip=args.clip, scaler=scaler, group=group,
-                               watch=watch)
+                               watch=watch, cache=tr_cache)
             tl, steps = tl + float(loss.detach()), steps + 1
         if watch is not None:
             watch.flush()
         if smooth:
             crit.eval()         # utils.py:693: validation is plain cross entropy
-        if grouped:
+        if src is not None:
+            synthetic = src.val_batches()
+        elif grouped:
             synthetic = (synthetic_vqa_grouped(args, ctx, sd, C) for sd in val_seeds(args))
         else:
             synthetic = (synth.vqa_batch(B, T, args.image_size, args.emb_vocab, C, seed=sd, device=ctx.dev) for sd in val_seeds(args))
@@ -1125,6 +1280,23 @@ def parse_args(argv=None):
                            help="attribution method (vqamed2019/grad_cam.py:30,65-72); other than gradcam, the index "
                                 "gains a `method` column")
     args = p.parse_args(argv)
+    if args.cache_tokens:
+        if mode != "vqa":
+            p.error(f"--cache_tokens is for vqa: caching visual tokens for {mode} is not built")
+        if args.mixed_precision:
+            p.error("--cache_tokens cannot be combined with --mixed_precision: cached visual tokens and the step from them are fp32")
+        if args.group_by_image:
+            p.error("--cache_tokens cannot be combined with --group_by_image: a cached step runs no backbone to share")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            p.error("--cache_tokens runs in one process: a cache sharded over data-parallel ranks is not built")
+        if args.data_dir and args.cache_images is not None:
+            p.error("--cache_images sizes the synthetic train set: with --data_dir the cache holds the images of the tables")
+        if args.cache_views is not None and args.cache_views < 1:
+            p.error(f"--cache_views {args.cache_views} must be at least 1")
+        if args.cache_images is not None and args.cache_images < 1:
+            p.error(f"--cache_images {args.cache_images} must be at least 1")
+    elif args.cache_views is not None or args.cache_images is not None:
+        p.error(f"--{'cache_views' if args.cache_views is not None else 'cache_images'} is read with --cache_tokens only")
     if mode == "gradcam" and args.group_by_image:
         p.error("--group_by_image is for vqa and eval: attribution over grouped batches is not built")
     if args.mixed_precision and args.overlap_adam:
